@@ -14,8 +14,12 @@ in HBM before the timed region.  Multi-GPU: instances are sharded, one process p
 one rank; started plainly (`python bench.py --gpus N`) this process only starts N rank processes of itself -- before
 torch is imported, so nothing here has touched a GPU -- waits for them and exits with their status.
 
-Prints ONE JSON line on rank 0 (contract in the task description); `roofline`, `cpu_baseline`, `nn_distance` and
-`emd` are extra objects.
+Prints ONE JSON line on rank 0 (`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, ...).  A
+plain run sets up, warms up, times `--steps` steps and prints the headline; the side measurements (`roofline`,
+`cpu_baseline`, `nn_distance`, `emd`, the other precisions and policies, the training steps, the N > 1 rank proof and
+per-rank times, ...) run only with `--full`.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32): the same arguments give
+the same seeded inputs on every run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -1088,6 +1092,32 @@ def gather_rank_objects(dist, world, fn):
 _OUT = None  # the stream the ONE JSON line goes to (main(): the process's original stdout)
 
 
+OUTPUT_NAMES = ("centroids", "chamfer_dist1", "chamfer_dist2", "chamfer_grad_pred", "chamfer_grad_gt")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outs, directory, rank):
+    """--dump-outputs: what one step returned to its caller -- Step: centroids (B, 3), the Chamfer distances (B, n)
+    both ways and the Chamfer gradients w.r.t. the predicted and the GT cloud (B, n, 3); MultiStreamStep: the same per
+    shard, joined along the instance axis -- as float32 DIR/<name>.npy (rank r > 0: DIR/rank<r>_<name>.npy).  Beyond
+    DUMP_LIMIT_BYTES in all, a seeded sample of instances (the same rows of every array) is written, with its indices
+    in sampled_instances.npy."""
+    if isinstance(outs, list):
+        outs = [torch.cat(parts) for parts in zip(*outs)]
+    arrays = [t.detach().float().cpu().numpy() for t in outs]
+    B = arrays[0].shape[0]
+    per_instance = sum(a.nbytes for a in arrays) // B
+    prefix = "" if rank == 0 else "rank%d_" % rank
+    os.makedirs(directory, exist_ok=True)
+    if B * per_instance > DUMP_LIMIT_BYTES:
+        k = max(1, DUMP_LIMIT_BYTES // (per_instance + 8))
+        idx = np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+        arrays = [a[idx] for a in arrays]
+        np.save(os.path.join(directory, prefix + "sampled_instances.npy"), idx.astype(np.float64))
+    for name, a in zip(OUTPUT_NAMES, arrays):
+        np.save(os.path.join(directory, prefix + name + ".npy"), np.ascontiguousarray(a))
+
+
 def claim_stdout():
     """The contract is ONE JSON line on stdout.  Libraries write there too: RCCL prints a five-line version block
     ("RCCL version : ...", HIP / ROCm version, hostname, library path) to the C stdout when a communicator is created
@@ -1182,10 +1212,11 @@ class Emitter:
         self.timer.cancel()
 
 
-def rendezvous_only(rank, world):
+def rendezvous_only(rank, world, full):
     """Test hook (tests/test_bench_launch.py): the whole N-rank plumbing of this file on CPU over gloo -- launch,
-    rendezvous, max-over-ranks timing, rank proof, per-rank gathers, the reducer-driven training-step object and the
-    all-rank EMD object -- with stand-in workloads where the hot path would run (it has no CPU form)."""
+    rendezvous, max-over-ranks timing and, with `full` (--full), rank proof, per-rank gathers, the reducer-driven
+    training-step object and the all-rank EMD object -- with stand-in workloads where the hot path would run (it has no
+    CPU form)."""
     import torch.distributed as dist
     from monopsr_amd.core.trainer import ReverseBucketReducer
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -1196,6 +1227,11 @@ def rendezvous_only(rank, world):
     dist.all_reduce(seen, op=dist.ReduceOp.MAX)
     result = {"rendezvous_only": True, "n_gpus": world, "max_rank_plus_1": float(seen.item())}
     em.arm(result)
+    if not full:
+        em.emit(result)
+        dist.barrier()
+        dist.destroy_process_group()
+        return
     if os.environ.get("MPSR_BENCH_TEST_HANG_EXTRAS"):  # test hook: an extra that never returns
         time.sleep(3600)
     result["rank_proof"] = rank_proof(dist, rank, world, "gloo", cpu)
@@ -1288,7 +1324,16 @@ def main():
     ap.add_argument("--extras-deadline", type=float, default=900.0,
                     help="seconds after the headline is measured before the watchdog prints it without the "
                          "unfinished extra objects")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side measurements (roofline, CPU baseline, other precisions "
+                         "and policies, training steps, N > 1 rank objects, ...); the --no-* options and --cpu-sample "
+                         "choose among them.  Off: the line holds the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (centroids, Chamfer distances and gradients) as "
+                         "DIR/<name>.npy in float32, at most 64 MB in all (a seeded sample of instances beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     claim_stdout()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1302,7 +1347,7 @@ def main():
     if os.environ.get("MPSR_BENCH_TEST_HANG"):
         time.sleep(600)
     if os.environ.get("MPSR_BENCH_RENDEZVOUS_ONLY"):
-        return rendezvous_only(rank, world)
+        return rendezvous_only(rank, world, args.full)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the hot path has no CPU fallback")
     # MPSR_BENCH_SHARE_GPU: test hook for 1-GPU boxes -- every rank computes on cuda:0 and the ranks meet over gloo
@@ -1355,8 +1400,9 @@ def main():
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         one_step()
+    last = one_step()  # (kept for --dump-outputs)
     torch.cuda.synchronize()
     t_own = time.perf_counter() - t0  # this rank's own K steps, before it waits for the others
     barrier()
@@ -1387,7 +1433,18 @@ def main():
                    "sharding": "instances/%d, no data-path collective" % n_gpus +
                                (" + all-reduce(401 MB synthetic grad buffer)" if args.allreduce_grads else "")},
     }
+    if args.dump_outputs:
+        dump_outputs(last, args.dump_outputs, rank)
     emitter.arm(result)  # from here on a hang in a side measurement costs the extras, not the line
+
+    def finish():
+        emitter.emit(result)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:  # a plain run: the headline alone
+        return finish()
 
     if multi:
         # ---- N > 1 only: who took part, and how evenly
@@ -1598,11 +1655,7 @@ def main():
             result["cpu_baseline"], _ = cpu_baseline(weights, host, min(args.cpu_sample, args.batch), args.points)
         except Exception as e:
             result["cpu_baseline"] = {"error": repr(e)}
-
-    emitter.emit(result)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

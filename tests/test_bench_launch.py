@@ -28,7 +28,7 @@ def _json_lines(out):
 
 @pytest.mark.parametrize("n", [2, 3, 8])  # (8: the node the driver's scaling run uses)
 def test_gpus_n_starts_n_ranks(n):
-    r = _run(["--gpus", str(n)], {"MPSR_BENCH_RENDEZVOUS_ONLY": "1"})
+    r = _run(["--gpus", str(n), "--full"], {"MPSR_BENCH_RENDEZVOUS_ONLY": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout  # rank 0 only
@@ -48,6 +48,16 @@ def test_gpus_n_starts_n_ranks(n):
     assert ts["loss_per_step"][-1] == pytest.approx(sum(range(1, n + 1)) / n, abs=0.06)
     emd = res["emd"]["all_ranks"]
     assert emd["ranks_ok"] == n and emd["fused_clouds_per_s_sum"] == 10.0 * sum(range(1, n + 1))
+
+
+def test_a_plain_run_carries_no_side_objects():
+    # without --full the N-rank line holds what the headline needs and nothing that takes runs of its own
+    r = _run(["--gpus", "2"], {"MPSR_BENCH_RENDEZVOUS_ONLY": "1"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1 and lines[0]["n_gpus"] == 2 and lines[0]["max_rank_plus_1"] == 2
+    for key in ("rank_proof", "per_rank_ms", "training_step", "emd"):
+        assert key not in lines[0], key
 
 
 def test_under_a_launcher_each_process_is_one_rank():
@@ -94,8 +104,8 @@ def test_a_rank_that_dies_early_does_not_leave_its_peers_waiting():
 def test_a_hanging_extra_does_not_cost_the_headline():
     # once `value` exists a watchdog is armed: extras that do not finish by the deadline are dropped, the line is
     # printed as it stands (marked), every rank exits 0
-    r = _run(["--gpus", "2"], {"MPSR_BENCH_RENDEZVOUS_ONLY": "1", "MPSR_BENCH_TEST_HANG_EXTRAS": "1",
-                               "MPSR_BENCH_TEST_DEADLINE": "3"}, timeout=120)
+    r = _run(["--gpus", "2", "--full"], {"MPSR_BENCH_RENDEZVOUS_ONLY": "1", "MPSR_BENCH_TEST_HANG_EXTRAS": "1",
+                                         "MPSR_BENCH_TEST_DEADLINE": "3"}, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1 and lines[0]["n_gpus"] == 2 and lines[0]["extras_timed_out_after_s"] == 3.0
@@ -111,7 +121,7 @@ def test_a_rank_dying_during_the_extras_does_not_cost_the_headline():
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     env.update(MPSR_BENCH_RENDEZVOUS_ONLY="1", MPSR_BENCH_TEST_HANG_EXTRAS="1", MPSR_BENCH_TEST_DEADLINE="300",
                RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29631")
-    p = subprocess.Popen([sys.executable, BENCH, "--gpus", "1"], env=env, stdout=subprocess.PIPE,
+    p = subprocess.Popen([sys.executable, BENCH, "--gpus", "1", "--full"], env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True)
     try:
         time.sleep(12)  # rendezvous + headline, then the extras "hang"
@@ -156,8 +166,8 @@ def test_sigterm_to_the_launcher_stops_the_ranks():
 
 @pytest.mark.gpu
 def test_two_ranks_of_the_real_step_on_one_gpu():
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--points", "256", "--cpu-sample", "0"],
-             {"MPSR_BENCH_SHARE_GPU": "1"}, timeout=1800)
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--points", "256", "--cpu-sample", "0",
+              "--full"], {"MPSR_BENCH_SHARE_GPU": "1"}, timeout=1800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1
@@ -178,3 +188,34 @@ def test_two_ranks_of_the_real_step_on_one_gpu():
     emd = res["emd"]
     assert "error" not in emd and emd["all_ranks"]["ranks_ok"] == 2, emd
     assert 0 < res["roofline"]["frac"] <= 1.0
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_steps_outputs(tmp_path):
+    import numpy as np
+    out = tmp_path / "outputs"
+    runs = []
+    for steps in (1, 3):
+        d = out / str(steps)
+        r = _run(["--gpus", "1", "--steps", str(steps), "--warmup", "1", "--batch", "8", "--points", "256",
+                  "--dump-outputs", str(d)], {}, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1
+        res = lines[0]
+        assert res["steps"] == steps and res["warmup"] == 1 and res["ms_per_step"] > 0
+        assert abs(res["value"] - 8 * 1e3 / res["ms_per_step"]) < 0.01 * res["value"]
+        for key in ("metric", "unit", "higher_is_better", "dtype"):
+            assert key in res, key
+        for key in ("roofline", "cpu_baseline", "bf16x3_mode", "training_step", "emd"):  # --full only
+            assert key not in res, key
+        arrays = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        shapes = {"centroids": (8, 3), "chamfer_dist1": (8, 256), "chamfer_dist2": (8, 256),
+                  "chamfer_grad_pred": (8, 256, 3), "chamfer_grad_gt": (8, 256, 3)}
+        assert {k: a.shape for k, a in arrays.items()} == shapes
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert (arrays["chamfer_dist1"] >= 0).all() and np.abs(arrays["centroids"]).max() > 0
+        runs.append(arrays)
+    # seeded inputs: another run with other step counts computes the same step
+    for k in runs[0]:
+        np.testing.assert_allclose(runs[0][k], runs[1][k], rtol=1e-4, atol=1e-5 * np.abs(runs[0][k]).max(), err_msg=k)

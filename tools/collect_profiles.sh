@@ -9,7 +9,7 @@
 TAG=${1:-r02}; COMMIT=${2:-unknown}
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG; mkdir -p $OUT
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 bench.py --steps 10 --warmup 3 --cpu-sample 0 --no-fast-mode --no-train-step --no-full-image > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/stats.err || echo "stats pass failed"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 bench.py --full --steps 10 --warmup 3 --cpu-sample 0 --no-fast-mode --no-train-step --no-full-image > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/stats.err || echo "stats pass failed"
 cp $OUT/stats/*kernel_stats.csv $OUT/${TAG}_bench_kernel_stats.csv 2>/dev/null
 i=0
 for P in "FETCH_SIZE" "WRITE_SIZE" \
@@ -43,7 +43,7 @@ timeout 200 python3 tools/rccl_selftest.py > $OUT/${TAG}_rccl_one_rank.json 2> $
 timeout 200 python3 tools/emd_time.py > $OUT/${TAG}_emd_level_culling.txt 2> $OUT/emd.err || echo "emd timing failed"
 timeout 300 python3 -m pytest tests/test_hostile_inputs_gpu.py -s -q > $OUT/${TAG}_hostile_inputs.txt 2>&1 || echo "hostile inputs run failed"
 # the default bench command, untraced, on the same box as everything above (profiles/<tag>_bench_default_run.json)
-timeout 600 python3 bench.py > $OUT/${TAG}_bench_default_run.json 2> $OUT/default.err || echo "default bench failed"
+timeout 600 python3 bench.py --full > $OUT/${TAG}_bench_default_run.json 2> $OUT/default.err || echo "default bench failed"
 # r06 (late): the training step with its weight gradients on the second stream (default) and on the main stream, the
 # both-trunk step, and the framework launches of a step by source line
 { for V in "" "--wgrad-main-stream" "" "--wgrad-main-stream" "--full-image" "--full-image --batch 32"; do
