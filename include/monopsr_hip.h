@@ -616,6 +616,79 @@ int mpsr_heads_fwd_cams(const float *feat_box3d, int B, int feat_elems, const fl
                         const float *blob, const mpsr_layer *layers, int n_layers, const mpsr_head_outputs *outs,
                         void *workspace, size_t workspace_bytes, mpsr_stream_t stream);
 
+
+/* ---- KITTI object evaluation (scripts/offline_eval/kitti_native_eval/evaluate_object_3d_offline.cpp), fp64 ----
+ * One ragged batch of F frames.  Rows hold MPSR_KITTI_FIELDS doubles in the column order below (a detection's score and
+ * a ground truth's truncation share a column; a detection's occlusion column is unused); class codes are
+ * MPSR_KITTI_CAR ... MPSR_KITTI_OTHER (int32).  Frame f owns detection rows det_off[f] .. det_off[f+1], ground-truth
+ * rows gt_off[f] .. gt_off[f+1] and pairs pair_off[f] .. pair_off[f+1]; pair pair_off[f] + j * n_gt(f) + i is
+ * (detection j, ground truth i) of the frame.  The offsets come twice: in device memory for the kernels and in host
+ * memory, where they are checked (start at 0, never decrease, pair counts = detections x ground truths, end at the row
+ * counts) and read before anything is launched.
+ * A configuration is (metric, class, difficulty), index (metric * 3 + class) * 3 + difficulty: metric 0 image,
+ * 1 bird's-eye view, 2 3D; class 0 car, 1 pedestrian, 2 cyclist; difficulty 0 easy, 1 moderate, 2 hard.
+ * min_overlap (host, 9 doubles): MIN_OVERLAP[metric][class] (:55). */
+#define MPSR_KITTI_FIELDS 14
+#define MPSR_KITTI_X1 0
+#define MPSR_KITTI_Y1 1
+#define MPSR_KITTI_X2 2
+#define MPSR_KITTI_Y2 3
+#define MPSR_KITTI_ALPHA 4
+#define MPSR_KITTI_H 5
+#define MPSR_KITTI_W 6
+#define MPSR_KITTI_L 7
+#define MPSR_KITTI_TX 8
+#define MPSR_KITTI_TY 9
+#define MPSR_KITTI_TZ 10
+#define MPSR_KITTI_RY 11
+#define MPSR_KITTI_SCORE 12
+#define MPSR_KITTI_TRUNCATION 12
+#define MPSR_KITTI_OCCLUSION 13
+enum { MPSR_KITTI_CAR = 0, MPSR_KITTI_PEDESTRIAN = 1, MPSR_KITTI_CYCLIST = 2, MPSR_KITTI_VAN = 3,
+       MPSR_KITTI_PERSON_SITTING = 4, MPSR_KITTI_DONTCARE = 5, MPSR_KITTI_OTHER = 6 };
+#define MPSR_KITTI_CONFIGS 27
+#define MPSR_KITTI_POINTS 41 /* recall sample points; also the most score thresholds of a configuration */
+/* the statistics kernels keep one bit per detection of a frame and lane in 64 KB of LDS */
+#define MPSR_KITTI_MAX_FRAME_DETECTIONS 8192
+
+typedef struct mpsr_kitti_batch {
+    const double *det;            /* (n_det, MPSR_KITTI_FIELDS) */
+    const int *det_cls;           /* (n_det) */
+    const double *gt;             /* (n_gt, MPSR_KITTI_FIELDS) */
+    const int *gt_cls;            /* (n_gt) */
+    const int *det_off;           /* (n_frames + 1), device */
+    const int *gt_off;            /* (n_frames + 1), device */
+    const long long *pair_off;    /* (n_frames + 1), device */
+    const int *det_off_host;      /* the same three, host */
+    const int *gt_off_host;
+    const long long *pair_off_host;
+    int n_det, n_gt, n_frames;
+} mpsr_kitti_batch;
+
+/* imageBoxOverlap / groundBoxOverlap / box3DOverlap (:228-345) of every pair: overlaps (6, n_pairs) = image, BEV, 3D
+ * IoU (criterion -1), then the same over the detection's own area / volume (criterion 0).  BEV: exact clipping of the
+ * two rotated rectangles.  A box with non-positive l or w (BEV), or l, w or h (3D), overlaps nothing (0). */
+int mpsr_kitti_overlaps(const mpsr_kitti_batch *batch, double *overlaps, mpsr_stream_t stream);
+
+/* computeStatistics with compute_fp = false (:457-636), cleanData (:382-455) applied in the kernel, for every
+ * configuration and frame.  tp_scores (27, n_gt): the score of the detection taken as the true positive of each
+ * ground-truth row, NaN where there is none; n_care (27, n_frames): the ground truths that count (ignored_gt == 0).
+ * A frame with more than MPSR_KITTI_MAX_FRAME_DETECTIONS detections: MPSR_ERR_INVALID_ARG. */
+int mpsr_kitti_match(const mpsr_kitti_batch *batch, const double *overlaps, const double *min_overlap,
+                     double *tp_scores, int *n_care, mpsr_stream_t stream);
+
+/* Bytes of mpsr_kitti_stats' workspace: the per-frame results of n_configs configurations (those with thresholds). */
+size_t mpsr_kitti_stats_workspace_bytes(int n_frames, int n_configs);
+
+/* computeStatistics with compute_fp = true for every configuration, frame and score threshold, summed over frames in
+ * frame order (eval_class :686-705).  thresholds (27, MPSR_KITTI_POINTS) device; n_thresholds (27) host, 0..41 (0: the
+ * configuration is skipped); compute_aos: the image metric's orientation similarity (0 when a detection has alpha
+ * -10).  counts (27, 41, 3) int32 = tp, fp, fn; similarity (27, 41, 2) = orientation similarity (image metric) and
+ * heading similarity (BEV, 3D); entries of skipped configurations and thresholds are 0. */
+int mpsr_kitti_stats(const mpsr_kitti_batch *batch, const double *overlaps, const double *min_overlap,
+                     const double *thresholds, const int *n_thresholds, int compute_aos, int *counts,
+                     double *similarity, void *workspace, size_t workspace_bytes, mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MPSR_LIB_PATH: development knob for A/B-ing two builds of the library inside one GPU session
 LIB_PATH = os.environ.get("MPSR_LIB_PATH") or os.path.join(_HERE, "libmonopsr_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _lib = None
 
@@ -65,6 +65,13 @@ class PackJob(ctypes.Structure):
     """struct mpsr_pack_job"""
     _fields_ = [("w", ctypes.c_void_p), ("wd", ctypes.c_void_p), ("N", ctypes.c_int32), ("Nd", ctypes.c_int32),
                 ("T", ctypes.c_int32), ("C", ctypes.c_int32), ("chunk0", ctypes.c_int64)]
+
+
+class KittiBatch(ctypes.Structure):
+    """struct mpsr_kitti_batch"""
+    _fields_ = [(k, ctypes.c_void_p) for k in
+                ("det", "det_cls", "gt", "gt_cls", "det_off", "gt_off", "pair_off", "det_off_host", "gt_off_host",
+                 "pair_off_host")] + [("n_det", ctypes.c_int32), ("n_gt", ctypes.c_int32), ("n_frames", ctypes.c_int32)]
 
 
 # per-call option values (MPSR_CALL_MATH_*, MPSR_CALL_WINOGRAD_*): None / "inherit" = the process-wide default
@@ -171,6 +178,11 @@ SIGNATURES = {
                              ctypes.POINTER(Layer), c_i, ctypes.POINTER(HeadOutputs), c_f, c_sz, c_f]),
     "mpsr_heads_fwd_cams": (c_i, [c_f, c_i, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, ctypes.POINTER(HeadConsts), c_f,
                                   ctypes.POINTER(Layer), c_i, ctypes.POINTER(HeadOutputs), c_f, c_sz, c_f]),
+    "mpsr_kitti_overlaps": (c_i, [ctypes.POINTER(KittiBatch), c_f, c_f]),
+    "mpsr_kitti_match": (c_i, [ctypes.POINTER(KittiBatch), c_f, ctypes.POINTER(ctypes.c_double), c_f, c_f, c_f]),
+    "mpsr_kitti_stats_workspace_bytes": (c_sz, [c_i, c_i]),
+    "mpsr_kitti_stats": (c_i, [ctypes.POINTER(KittiBatch), c_f, ctypes.POINTER(ctypes.c_double), c_f,
+                               ctypes.POINTER(c_i), c_i, c_f, c_f, c_f, c_sz, c_f]),
 }
 
 

@@ -10,7 +10,10 @@ in front of it.  `project_3d_box=True` (2-D box = clipped projection of the 3-D 
 vectorised over the boxes of a frame; it needs the frame's P2 matrix and image size, which the caller supplies
 (`frame_info`) because this package has no dataset reader.
 
-Running the native KITTI evaluator and the metrics CSV (evaluator_utils.py:280-560) are out of scope.
+The native KITTI evaluator the reference compiles and runs (evaluator_utils.py:457-560) is replaced by
+`monopsr_amd.core.kitti_eval`, which computes the same AP on the GPU from these label files (`evaluate_dirs`) or
+straight from format_predictions output (`evaluate_predictions`, through `kitti_label_array`).  The metrics CSV,
+checkpoint sweeps and summaries (evaluator_utils.py:280-456) are out of scope.
 """
 import os
 
@@ -45,10 +48,9 @@ def project_boxes_3d(boxes_3d, cam_p, image_size, max_fraction=0.8):
     return clipped, inside & small
 
 
-def kitti_label_rows(box_3d, box_2d, classes, score_threshold, image_boxes=None, keep=None):
-    """Detections of one frame -> list of KITTI label lines (no line ends).
-    box_3d (n,9), box_2d (n,7) as format_predictions returns them; `image_boxes` (n,4) [x1,y1,x2,y2] replaces the
-    2-D boxes of box_2d (projection mode), `keep` (n,) drops rows on top of the score filter."""
+def kitti_label_array(box_3d, box_2d, score_threshold, image_boxes=None, keep=None):
+    """The numbers of the label lines `kitti_label_rows` writes, before they become text: (class index (m,) int,
+    values (m,12) float64 rounded to 3 decimals: alpha | x1 y1 x2 y2 | h w l | x y z | ry score)."""
     box_3d = np.asarray(box_3d, np.float64).reshape(-1, 9)
     box_2d = np.asarray(box_2d, np.float64).reshape(-1, 7)
     sel = box_3d[:, _SCORE] >= score_threshold
@@ -56,10 +58,17 @@ def kitti_label_rows(box_3d, box_2d, classes, score_threshold, image_boxes=None,
         sel &= np.asarray(keep, bool)
     b3, b2 = box_3d[sel], box_2d[sel]
     xyxy = b2[:, [1, 0, 3, 2]] if image_boxes is None else np.asarray(image_boxes, np.float64)[sel]
-    # alpha | x1 y1 x2 y2 | h w l | x y z | ry score
     numbers = np.round(np.column_stack([b2[:, 4], xyxy, b3[:, [_H, _W, _L]], b3[:, _X:_X + 3],
                                         b3[:, [_RY, _SCORE]]]), 3)
-    names = [classes[int(k)] for k in b3[:, _CLS]]
+    return b3[:, _CLS].astype(np.int64), numbers
+
+
+def kitti_label_rows(box_3d, box_2d, classes, score_threshold, image_boxes=None, keep=None):
+    """Detections of one frame -> list of KITTI label lines (no line ends).
+    box_3d (n,9), box_2d (n,7) as format_predictions returns them; `image_boxes` (n,4) [x1,y1,x2,y2] replaces the
+    2-D boxes of box_2d (projection mode), `keep` (n,) drops rows on top of the score filter."""
+    cls, numbers = kitti_label_array(box_3d, box_2d, score_threshold, image_boxes, keep)
+    names = [classes[int(k)] for k in cls]
     return [' '.join([name, '-1', '-1'] + [repr(float(v)) for v in row]) for name, row in zip(names, numbers)]
 
 
