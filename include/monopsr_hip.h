@@ -689,6 +689,52 @@ int mpsr_kitti_stats(const mpsr_kitti_batch *batch, const double *overlaps, cons
                      const double *thresholds, const int *n_thresholds, int compute_aos, int *counts,
                      double *similarity, void *workspace, size_t workspace_bytes, mpsr_stream_t stream);
 
+/* ---- LiDAR depth maps (ABI 8): demos/depth_completion/save_lidar_depth_maps.py ----
+ * Several frames that share one image size (h, w); all maps are (n_frames, h, w) float32. */
+
+/* Bytes of mpsr_lidar_project_depths' workspace: one int per pixel and frame. */
+size_t mpsr_lidar_project_workspace_bytes(int n_frames, int h, int w);
+
+/* depth_map_utils.project_depths (monopsr/datasets/kitti/depth_map_utils.py:305-348) of the cloud that
+ * get_lidar_point_cloud builds (obj_utils.py:432-450).  points (P, 4) float32 velodyne x y z intensity, frame f owning
+ * rows frame_offsets[f] .. frame_offsets[f+1] (device and host copies of the same n_frames + 1 offsets; the host copy is
+ * checked: starts at 0, never decreases, at most INT_MAX points per frame).  velo_to_cam0 (n_frames, 3, 4) fp64: rows 0..2
+ * of R0_rect . Tr_velo_to_cam composed in 4 x 4 as calib_utils.lidar_to_cam_frame (:311-342) composes it; p2
+ * (n_frames, 3, 4) fp64.  In fp64 without contraction: cam0 = T . [x y z 1], pixel = rint(u / w), rint(v / w) of
+ * P2 . [cam0 1] (round half to even); a point whose pixel is not finite or lies outside the image is dropped; there is
+ * NO z > 0 filter.  Where points share a pixel the LAST one (in cloud order) wins, and the stored value is
+ * max_depth - max(0, max_depth - z) rounded once to float32 (a point beyond max_depth stores max_depth); 0 elsewhere. */
+int mpsr_lidar_project_depths(const float *points, const long long *frame_offsets, const long long *frame_offsets_host,
+                              int n_frames, const double *velo_to_cam0, const double *p2, int h, int w,
+                              double max_depth, float *out, void *workspace, size_t workspace_bytes,
+                              mpsr_stream_t stream);
+
+#define MPSR_DEPTH_MAX_KERNEL 15
+enum { MPSR_DEPTH_BLUR_BILATERAL = 0, MPSR_DEPTH_BLUR_GAUSSIAN = 1 };
+enum { MPSR_DEPTH_KERNEL_FAR = 0, MPSR_DEPTH_KERNEL_MED = 1, MPSR_DEPTH_KERNEL_NEAR = 2 };
+
+typedef struct mpsr_depth_fill_opts {
+    float max_depth;    /* 100.0 in the reference */
+    int extrapolate;    /* 0 / 1 */
+    int blur_type;      /* MPSR_DEPTH_BLUR_* */
+    int kernel_h[3];    /* dilation kernels far (30 < d), med (15 < d <= 30), near (0.1 < d <= 15): 1 .. 15 */
+    int kernel_w[3];
+    unsigned char kernels[3][MPSR_DEPTH_MAX_KERNEL * MPSR_DEPTH_MAX_KERNEL]; /* 0/1, row-major, row stride 15 */
+} mpsr_depth_fill_opts;
+
+/* Bytes of mpsr_depth_fill_multiscale's workspace (it holds the stage planes when the caller passes no `stages`). */
+size_t mpsr_depth_fill_workspace_bytes(int n_frames, int h, int w);
+
+/* IP-Basic's fill_in_multiscale (src/ip_basic/ip_basic.py:40-193) of every frame: depths (n_frames, h, w) -> out.
+ * stages, if not null: (n_frames, 8, h, w), the process images s1 .. s8 of show_process.  h, w >= 5; the dilation
+ * kernels take cv2's default anchor (kw / 2, kh / 2).  The cv2 calls follow OpenCV's semantics: dilate / erode ignore
+ * the image border, medianBlur(5) replicates it, GaussianBlur((5,5), 0) ([1 4 6 4 1] / 16, rows then columns) and
+ * bilateralFilter(5, 0.5, 2.0) (13 taps, the 4098-entry colour table of the frame's max - min, sum / wsum in float32)
+ * reflect it (BORDER_REFLECT_101).  Every selection stage is exact; DESIGN.md section 7.2 says what the blurs assume. */
+int mpsr_depth_fill_multiscale(const float *depths, int n_frames, int h, int w, const mpsr_depth_fill_opts *opts,
+                               float *out, float *stages, void *workspace, size_t workspace_bytes,
+                               mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

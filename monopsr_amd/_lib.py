@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MPSR_LIB_PATH: development knob for A/B-ing two builds of the library inside one GPU session
 LIB_PATH = os.environ.get("MPSR_LIB_PATH") or os.path.join(_HERE, "libmonopsr_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _lib = None
 
@@ -72,6 +72,13 @@ class KittiBatch(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in
                 ("det", "det_cls", "gt", "gt_cls", "det_off", "gt_off", "pair_off", "det_off_host", "gt_off_host",
                  "pair_off_host")] + [("n_det", ctypes.c_int32), ("n_gt", ctypes.c_int32), ("n_frames", ctypes.c_int32)]
+
+
+class DepthFillOpts(ctypes.Structure):
+    """struct mpsr_depth_fill_opts"""
+    _fields_ = [("max_depth", ctypes.c_float), ("extrapolate", ctypes.c_int32), ("blur_type", ctypes.c_int32),
+                ("kernel_h", ctypes.c_int32 * 3), ("kernel_w", ctypes.c_int32 * 3),
+                ("kernels", (ctypes.c_uint8 * (15 * 15)) * 3)]
 
 
 # per-call option values (MPSR_CALL_MATH_*, MPSR_CALL_WINOGRAD_*): None / "inherit" = the process-wide default
@@ -183,6 +190,11 @@ SIGNATURES = {
     "mpsr_kitti_stats_workspace_bytes": (c_sz, [c_i, c_i]),
     "mpsr_kitti_stats": (c_i, [ctypes.POINTER(KittiBatch), c_f, ctypes.POINTER(ctypes.c_double), c_f,
                                ctypes.POINTER(c_i), c_i, c_f, c_f, c_f, c_sz, c_f]),
+    "mpsr_lidar_project_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "mpsr_lidar_project_depths": (c_i, [c_f, c_f, ctypes.c_void_p, c_i, c_f, c_f, c_i, c_i, ctypes.c_double, c_f, c_f,
+                                        c_sz, c_f]),
+    "mpsr_depth_fill_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "mpsr_depth_fill_multiscale": (c_i, [c_f, c_i, c_i, c_i, ctypes.POINTER(DepthFillOpts), c_f, c_f, c_f, c_sz, c_f]),
 }
 
 
