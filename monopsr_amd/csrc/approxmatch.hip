@@ -45,10 +45,7 @@
 namespace {
 
 constexpr int kThreads = 256;
-#ifndef MPSR_EMD_PT
-#define MPSR_EMD_PT 2
-#endif
-constexpr int kPT = MPSR_EMD_PT;  // own points per thread in the passes (even)
+constexpr int kPT = 2;  // own points per thread in the passes (even): one 2-wide packed vector of them
 constexpr int kPV = kPT / 2;       // ... as 2-wide vectors
 constexpr int kTile = 1024;  // opposite-cloud points per LDS tile
 constexpr float kLog2e = 1.4426950408889634f;

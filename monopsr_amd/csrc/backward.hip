@@ -51,22 +51,14 @@ struct WgradParams {
 };
 constexpr int MAX_TAPS = 9;
 
-#ifndef WG_WAVES
-#define WG_WAVES 0  // A/B builds: waves per SIMD the register allocation is held to (0 = hipcc's choice: 136 registers, 3)
-#endif
-#if WG_WAVES
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WG_WAVES, WG_WAVES))) void conv_wgrad_kernel(const WgradParams p)
-#else
+// (hipcc's register choice: 136 registers, three waves per SIMD; held to four it measured equal.  Two LDS tile pairs
+// with one barrier per step measured slower: 64 KB of LDS leave two workgroups per CU instead of three -- b3 conv1 232
+// vs 181 us, the training step 51.2 vs 47.8 ms: residency, not the second barrier, is what this kernel lives on.
+// DESIGN.md 4.6)
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p)
-#endif
 {
-#ifndef WG_DB
-#define WG_DB 0  // 1: two LDS tile pairs, one barrier per step.  A/B build (r06), measured SLOWER: 64 KB of LDS leave two
-                 // workgroups per CU instead of three -- b3 conv1 232 vs 181 us, the training step 51.2 vs 47.8 ms:
-                 // residency, not the second barrier, is what this kernel lives on
-#endif
-    __shared__ __attribute__((aligned(16))) float At[(WG_DB ? 2 : 1) * WG_K * WG_T];  // [pixel][n]
-    __shared__ __attribute__((aligned(16))) float Bt[(WG_DB ? 2 : 1) * WG_K * WG_T];  // [pixel][c]
+    __shared__ __attribute__((aligned(16))) float At[WG_K * WG_T];  // [pixel][n]
+    __shared__ __attribute__((aligned(16))) float Bt[WG_K * WG_T];  // [pixel][c]
     int t = blockIdx.x;
     int tap, si, nsplit;
     if (p.grouped) {
@@ -164,9 +156,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p)
     };
     const unsigned lcol4 = (unsigned)lcol * 4u;
     auto load_tile = [&](int ms) {
-#ifdef WG_NO_LOAD  // (timing experiment only)
-        if (ms > ms_begin + 1) return;
-#endif
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint2 o = offs[ms & 1][lrow + 8 * j];
@@ -178,16 +167,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p)
             rb[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, offb, 0, 0));
         }
     };
-    auto store_tile = [&](int buf = 0) {
-#ifdef WG_NO_LDS_STORE  // (timing experiment only)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(ra[j].x), "v"(ra[j].y), "v"(ra[j].z), "v"(ra[j].w), "v"(rb[j].x), "v"(rb[j].y), "v"(rb[j].z), "v"(rb[j].w));
-        return;
-#endif
+    auto store_tile = [&]() {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            *reinterpret_cast<float4 *>(&At[buf * WG_K * WG_T + (lrow + 8 * j) * WG_T + lcol]) = ra[j];
-            *reinterpret_cast<float4 *>(&Bt[buf * WG_K * WG_T + (lrow + 8 * j) * WG_T + lcol]) = rb[j];
+            *reinterpret_cast<float4 *>(&At[(lrow + 8 * j) * WG_T + lcol]) = ra[j];
+            *reinterpret_cast<float4 *>(&Bt[(lrow + 8 * j) * WG_T + lcol]) = rb[j];
         }
     };
     const float *Aw = At + (lane >> 5) * 4 * WG_T + wm * 64 + (lane & 31);
@@ -196,16 +180,16 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p)
     // every pixel exactly once): thread t < 128 owns column n0 + t
     const bool do_db = p.db != nullptr && tap == (p.KH * p.KW) / 2 && tc == 0 && tid < WG_T;
     float colsum = 0.f;
-    auto compute_tile = [&](int buf = 0) {
+    auto compute_tile = [&]() {
         if (do_db) {
 #pragma unroll
-            for (int k = 0; k < WG_K; ++k) colsum += At[buf * WG_K * WG_T + k * WG_T + tid];
+            for (int k = 0; k < WG_K; ++k) colsum += At[k * WG_T + tid];
         }
 #pragma unroll
         for (int kb = 0; kb < WG_K / 8; ++kb)
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                const int row = buf * WG_K * WG_T + (kb * 8 + s) * WG_T;
+                const int row = (kb * 8 + s) * WG_T;
                 const float a0 = Aw[row], a1 = Aw[row + 32], b0 = Bw[row], b1 = Bw[row + 32];
                 acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
                 acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
@@ -221,18 +205,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p)
     load_tile(ms_begin);
     store_tile();
     __syncthreads();
-#if WG_DB
-    int cur = 0;
-    for (int ms = ms_begin; ms < ms_end - 1; ++ms) {
-        load_tile(ms + 1);
-        decode_rows(ms + 2);  // (entry ms & 1: last read by load_tile(ms), before the previous trip's barrier)
-        compute_tile(cur);
-        store_tile(cur ^ 1);  // the other pair: nobody reads it before the barrier
-        __syncthreads();
-        cur ^= 1;
-    }
-    compute_tile(cur);
-#else
     for (int ms = ms_begin; ms < ms_end - 1; ++ms) {
         load_tile(ms + 1);
         decode_rows(ms + 2);  // into the table entry load_tile(ms) read before the barriers of the previous trip
@@ -242,7 +214,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p)
         __syncthreads();
     }
     compute_tile();
-#endif
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -260,13 +231,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int n = n0 + wm * 64 + i * 32 + rsub + (e & 3) + 8 * (e >> 2);
-#ifdef WG_PLAIN_STORE  // (timing experiments only, tools/README.md: wrong results)
-                if (n < p.N) p.dw[(size_t)n * Ktot + (size_t)tap * p.C + c] = acc[i][j][e];
-#elif defined(WG_NO_STORE)
-                asm volatile("" ::"v"(acc[i][j][e]));
-#else
                 if (n < p.N) unsafeAtomicAdd(&p.dw[(size_t)n * Ktot + (size_t)tap * p.C + c], acc[i][j][e]);
-#endif
             }
     }
 }
@@ -276,13 +241,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p)
 // (i, k) = (lane & 31, lane >> 5) holds column i of reduction row k, i.e. the 32 lanes of a half-wave read ONE 128-byte
 // segment of pixel row k.  So a wave feeds its 64 x 64 share of the tile with four dword buffer loads per four MFMAs
 // straight from L2 / the vector cache into the MFMA's source registers: no LDS staging, no barriers (the four waves
-// of a workgroup never wait for each other), no register -> LDS -> register round trip.  Loads run a ring of WD_DEPTH
+// of a workgroup never wait for each other), no register -> LDS -> register round trip.  Loads run a ring of WD_RING
 // reduction pairs ahead.  Same tiles, slices, XCD grouping, atomics and bias gradient as conv_wgrad_kernel.
 // An A/B alternative, not the default (see g_wgrad_direct below): its dword loads cost more than the LDS kernel's
 // float4 loads + staging save.
-#ifndef WD_DEPTH
-#define WD_DEPTH 8
-#endif
+constexpr int WD_RING = 8;  // reduction pairs in flight per wave (depths 4 / 8 / 16 measured identical: DESIGN.md 4.6)
 __global__ __launch_bounds__(256) void pw_wgrad_direct_kernel(const WgradParams p)
 {
     int t = blockIdx.x;
@@ -316,7 +279,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_direct_kernel(const WgradParams 
     const unsigned NB = (unsigned)p.N * 4u, CB = (unsigned)p.C * 4u;
     const int na = n0 + wm * 64 + col, cb = c0 + wn * 64 + col;
     // byte offsets of this lane's element of the first pair; a column outside the tensor keeps an out-of-range offset
-    // (increment 0).  The host keeps (M + 2 * WD_DEPTH + 32) rows of either tensor below 4 GiB: no wrap-around.
+    // (increment 0).  The host keeps (M + 2 * WD_RING + 32) rows of either tensor below 4 GiB: no wrap-around.
     const unsigned row0 = (unsigned)(kp_begin * 2 + kh);
     unsigned oa0 = na < p.N ? row0 * NB + (unsigned)na * 4u : 0xfffffff0u;
     unsigned oa1 = na + 32 < p.N ? row0 * NB + (unsigned)(na + 32) * 4u : 0xfffffff0u;
@@ -332,7 +295,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_direct_kernel(const WgradParams 
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    float a0[WD_DEPTH], a1[WD_DEPTH], b0[WD_DEPTH], b1[WD_DEPTH];
+    float a0[WD_RING], a1[WD_RING], b0[WD_RING], b1[WD_RING];
     auto issue = [&](int d) {
         a0[d] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rdy, oa0, 0, 0));
         a1[d] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rdy, oa1, 0, 0));
@@ -351,21 +314,17 @@ __global__ __launch_bounds__(256) void pw_wgrad_direct_kernel(const WgradParams 
         acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[d], b1[d], acc[1][1], 0, 0, 0);
     };
 #pragma unroll
-    for (int d = 0; d < WD_DEPTH; ++d) issue(d);
+    for (int d = 0; d < WD_RING; ++d) issue(d);
     int kp = kp_begin;
-    for (; kp + WD_DEPTH <= kp_end; kp += WD_DEPTH) {
+    for (; kp + WD_RING <= kp_end; kp += WD_RING) {
 #pragma unroll
-        for (int d = 0; d < WD_DEPTH; ++d) {
+        for (int d = 0; d < WD_RING; ++d) {
             consume(d);
-#ifdef WG_NO_LOAD  // (timing experiment only)
-            asm volatile("" : "+v"(a0[d]), "+v"(a1[d]), "+v"(b0[d]), "+v"(b1[d]));
-            continue;
-#endif
-            issue(d);  // the pair WD_DEPTH ahead (past the slice: rows of the next slice or zeros, never consumed)
+            issue(d);  // the pair WD_RING ahead (past the slice: rows of the next slice or zeros, never consumed)
         }
     }
 #pragma unroll
-    for (int d = 0; d < WD_DEPTH; ++d)
+    for (int d = 0; d < WD_RING; ++d)
         if (kp + d < kp_end) consume(d);  // (uniform)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -390,13 +349,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_direct_kernel(const WgradParams 
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int n = n0 + wm * 64 + i * 32 + rsub + (e & 3) + 8 * (e >> 2);
-#ifdef WG_PLAIN_STORE  // (timing experiments only, tools/README.md: wrong results)
-                if (n < p.N) p.dw[(size_t)n * p.C + c] = acc[i][j][e];
-#elif defined(WG_NO_STORE)
-                asm volatile("" ::"v"(acc[i][j][e]));
-#else
                 if (n < p.N) unsafeAtomicAdd(&p.dw[(size_t)n * p.C + c], acc[i][j][e]);
-#endif
             }
     }
 }
@@ -791,8 +744,8 @@ extern "C" int mpsr_conv2d_wgrad_f32(const float *x, const float *dy, int B, int
     p.ngroups = (int)groups;
     if (p.grouped) blocks = (groups + 7) / 8 * 8 * tiles;
     // 1x1 layers: operands straight from memory into the MFMA's source registers (no wrap-around of its running
-    // 32-bit offsets: the ring reads up to 2 * WD_DEPTH rows past a slice, a slice ends up to 31 rows past M)
-    const long long slack = 2 * WD_DEPTH + WG_K;
+    // 32-bit offsets: the ring reads up to 2 * WD_RING rows past a slice, a slice ends up to 31 rows past M)
+    const long long slack = 2 * WD_RING + WG_K;
     if (g_wgrad_direct && taps == 1 && (M + slack) * C * 4 < 0xfffffff0LL && (M + slack) * N * 4 < 0xfffffff0LL) {
         hipLaunchKernelGGL(pw_wgrad_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, mpsr::as_stream(stream), p);
         MPSR_CHECK_LAUNCH("pw_wgrad_direct_kernel");

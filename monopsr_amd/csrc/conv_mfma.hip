@@ -100,10 +100,6 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p)
     constexpr int AV = BM / 32, BV = BN / 32;  // float4 loads per thread per tile
     __shared__ __attribute__((aligned(16))) float lds[(BM + BN) * LDS_STRIDE];
     float *As = lds, *Bs = lds + BM * LDS_STRIDE;
-#ifdef MPSR_TRACE
-    unsigned long long tr0 = __builtin_readcyclecounter(), tr1 = 0, tr2 = 0;
-    const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
 
     // Tile order.  Workgroup b is observed to run on XCD b % 8 (speed only, never correctness): XCD x takes M tiles
     // x, x+8, x+16, ... of EVERY pixel class -- so each XCD gets the same mix of long and short K loops -- and walks
@@ -375,9 +371,6 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p)
         load_tile(Set0{}, true);
         store_tile(Set0{});
         __syncthreads();
-#ifdef MPSR_TRACE
-        tr1 = __builtin_readcyclecounter();
-#endif
         if constexpr (DEPTH == 1) {
             for (int ks = ks_begin; ks < ks_end - 1; ++ks) {
                 load_tile(Set0{}, true);
@@ -422,18 +415,6 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p)
 #pragma unroll
         for (int j = 0; j < TN; ++j) asm volatile("s_nop 15\n\ts_nop 7" : "+a"(acc[i][j]));
 
-#ifdef MPSR_TRACE
-    tr2 = __builtin_readcyclecounter();
-    auto trace_end = [&]() {
-        if (threadIdx.x == 0 && p.ws) {
-            unsigned long long *r = reinterpret_cast<unsigned long long *>(p.ws) + (size_t)blockIdx.x * 8;
-            r[0] = tr0; r[1] = tr1; r[2] = tr2; r[3] = __builtin_readcyclecounter();
-            r[4] = __builtin_amdgcn_s_getreg(63492);  // HW_REG_HW_ID
-            r[5] = __builtin_amdgcn_s_getreg(63508);  // HW_REG_XCC_ID
-            r[6] = rt0; r[7] = __builtin_amdgcn_s_memrealtime();
-        }
-    };
-#endif
     // epilogue.  C/D layout of the 32x32 MFMA: column = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5).
     const int col = lane & 31, rsub = (lane >> 5) * 4;
     float *dst = p.splits == 1 ? p.y : p.ws + (size_t)si * p.M * p.N;
@@ -481,9 +462,6 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p)
                 __builtin_amdgcn_wave_barrier();
             }
         }
-#ifdef MPSR_TRACE
-        trace_end();
-#endif
         return;
     }
     // scalar path (N not a multiple of 4: the 3-channel xyz head, the 27- and 2-wide head outputs)

@@ -33,7 +33,7 @@
 //     the range check, no vector-ALU address work.
 // M = batch x 144 pixels on the 12x12 trunk maps: 96-row groups divide it exactly, and at batch 256 the 384 groups x
 // N / 128 column blocks are 1.5 (N = 256), 3 (512) or 6 (1024) tiles for each of the 512 resident workgroups.
-// What is left (tools/pws_trace.py): one vmcnt counts loads AND stores in order, so the first wait after a store or a
+// What is left: one vmcnt counts loads AND stores in order, so the first wait after a store or a
 // residual request also waits for those -- stages 1-2 of a tile take ~3x a plain stage.
 #include <atomic>
 #include <type_traits>
@@ -45,44 +45,20 @@ namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-// PWS_WIDE (A/B builds only, default 0): the MFMA operands swapped (the matrix pipe computes the TRANSPOSED 32 x 32 block,
-// W X^T), so that a lane's four consecutive accumulator registers are four consecutive output CHANNELS of one pixel
-// row: a tile leaves as 12 buffer_store_dwordx4 per lane instead of 48 buffer_store_dword and starts from the residual
-// copy with 12 ds_read_b128 instead of 48 ds_read_b32.  Same products, same K order: bit-identical results (tested).
-// Measured SLOWER (r04, whole step, interleaved on one board: 15.20 -> 15.47 ms; 15.42 with the stores spread thinner,
-// profiles/r04_pointwise_wide_stores.txt): a dword store writes 2 rows x 128 contiguous bytes = two full lines per
-// instruction, the 16-byte form 32 rows x 32 bytes = 32 partial lines -- four times the write requests for the same
-// bytes.  The guide's "widen the epilogue stores" applies to row-per-lane layouts, not to stores that are already
-// full lines.
-#ifndef PWS_WIDE
-#define PWS_WIDE 0
-#endif
+// (The transposed accumulator layout -- 16-byte stores of four channels -- is bit-identical and measured slower: a dword
+// store already writes two full lines, the 16-byte form 32 partial ones; DESIGN.md 4.1 (f),
+// profiles/r04_pointwise_wide_stores.txt.)
 // Cache-policy bits of the residual loads and of the result stores: 2 = non-temporal.  The residual passes through ONCE
 // (151 MB on block3's conv3) next to operands that are re-read for the whole launch -- the 1 MB of filters by every
 // tile, a row group's activations by all its column blocks: marked streaming it stops evicting those from the 4 MB L2.
 // Step, interleaved on one board, three boards: 13.50 -> 13.41 ms (-1.2 %) with the residual loads alone.  The result
 // stores are a smaller and mixed effect: streaming them helps the launches WITHOUT a residual (conv1 / shortcut / tap
-// GEMMs: 13.41 -> 13.39) and costs on conv3 (its result is the next launch's input: 13.43 with every store streaming),
-// hence the default below.  The same hint on the F(4x4,3x3) / sixteen-product kernels' stores (W4_NT, W3Z_STORE_AUX)
-// measured +0.08 / +0.05 ms, on their transformed-filter loads +0.05 / +0.09 (W4_BAUX, W3Z_BAUX), on F(4x4,3x3)'s patch
-// loads +0.13 (W4_AAUX), on the upsampling gather's loads and stores (UPC_NT) equal: everything that is read twice or
-// read back at once wants the default policy; they stay off.
-#ifndef PWS_STORE_AUX
-#define PWS_STORE_AUX (RES ? 0 : 2)
-#endif
-#ifndef PWS_A_AUX
-#define PWS_A_AUX 0  // the activations' loads (A/B builds): streaming them costs +0.2 .. +0.36 ms -- every row group is read
-                     // by all of its column blocks and wants to stay in L2
-#endif
-#ifndef PWS_RES_AUX
-#define PWS_RES_AUX 2
-#endif
-#ifndef PWS_WSTEP
-#define PWS_WSTEP 16  // wide form: MFMA slots between two stores of the previous tile (16: three per stage, four stages)
-#endif
-
+// GEMMs: 13.41 -> 13.39) and costs on conv3 (its result is the next launch's input: 13.43 with every store streaming).
+// The same hint on the activations' loads cost +0.2 .. +0.36 ms (every row group is read by all of its column blocks),
+// and on the Winograd kernels' and the upsampling gather's loads and stores it measured equal or slower: everything
+// that is read twice or read back at once wants the default policy.
 namespace pws {
-constexpr bool WIDE = PWS_WIDE != 0;
+constexpr int RES_AUX = 2;  // the residual loads stream
 constexpr int WT = 3, ROWS = 96, COLS = 128, KS = 32;
 constexpr int TILE_B = 32 * KS * 4;          // 4096
 constexpr int STAGE_B = WT * TILE_B;         // 12288
@@ -100,7 +76,6 @@ struct PwsParams {
     int M, N, K, relu;
     int rgroups, cblocks, ntiles;  // ntiles: padded to 8 x column blocks
     unsigned wbytes;
-    unsigned long long *trace;  // -DPWS_TRACE builds: 16 stamps per wave (the workgroup's third tile)
     // tail job: the F(3x3,3x3) filter transform of the 3x3 layer that follows (wino3_filter.h), shared by all workgroups
     const float *fw;
     float *fu;
@@ -127,14 +102,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nst = p.K / KS;  // even, >= 4
-#ifdef PWS_PRIO  // A/B builds (r06): issue priority between the two co-resident workgroups' waves of a SIMD, by the
-    // hardware wave slot (HW_ID.wave_id, bits 3:0): 1 = the odd slot runs at priority 1 for the whole launch; 2 = the
-    // two alternate tile by tile.  Measured over three interleaved rounds of the step (tools/step_libs.sh): 13.266 ms
-    // without, 13.285 with 1, 13.297 with 2 -- two independent persistent workgroups are not the compute / load pair of
-    // one workgroup that a static priority helps (it did help winograd4.hip: W4_PRIO); not compiled in.
-    const int slot_bit = (int)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4) & 1;
-    if (PWS_PRIO == 1 && slot_bit) __builtin_amdgcn_s_setprio(1);
-#endif
+    constexpr int STORE_AUX = RES ? 0 : 2;  // the result stores stream unless the launch adds a residual (see RES_AUX)
+    // (a static issue priority between the two co-resident workgroups' waves measured slower: DESIGN.md 0)
 
     // this workgroup's tiles: i -> row group; the column block is fixed
     const int G = gridDim.x;
@@ -177,7 +146,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     float4 stg[WT];
     auto load_a = [&](RowRef xr, int stage, int j) __attribute__((always_inline)) {
         stg[j] = __builtin_bit_cast(
-            float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_at(xr, 32 * j, p.K), avoff, stage * (KS * 4), PWS_A_AUX));
+            float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_at(xr, 32 * j, p.K), avoff, stage * (KS * 4), 0));
     };
     auto store_a = [&](int buf, int j) __attribute__((always_inline)) {
         *reinterpret_cast<float4 *>(lds + buf * STAGE_B + j * TILE_B + awoff) = stg[j];
@@ -209,32 +178,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- residual staging: piece P = tid + 256 jj of the 96 x 128 tile (row-major, 32 pieces per row): row
     // (tid >> 5) + 8 jj, columns 4 (tid & 31) .. + 3
     const unsigned rvoff = ((unsigned)(tid >> 5) * (unsigned)p.N + (unsigned)(n0 + 4 * (tid & 31))) * 4u;
-    // (wide form: the 16-byte pieces of a row are XOR-swizzled by row & 15 -- lanes of one ds_read_b128 group then hit
-    // 16 different bank quads although their rows are 512 bytes apart; row & 15 = (tid >> 5) + 8 (jj & 1))
-    const unsigned rwoff = WIDE ? (unsigned)(RES_OFF + (tid >> 5) * 512 + (((tid & 31) ^ (tid >> 5)) << 4))
-                                : (unsigned)(RES_OFF + (tid >> 5) * 512 + (tid & 31) * 16);
+    const unsigned rwoff = (unsigned)(RES_OFF + (tid >> 5) * 512 + (tid & 31) * 16);
     float4 rst[6];
     auto load_r = [&](RowRef rr, int jj) __attribute__((always_inline)) {
-        rst[jj % 6] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_at(rr, 8 * jj, p.N), rvoff, 0, PWS_RES_AUX));
+        rst[jj % 6] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_at(rr, 8 * jj, p.N), rvoff, 0, RES_AUX));
     };
     auto store_r = [&](int jj) __attribute__((always_inline)) {
-        *reinterpret_cast<float4 *>(lds + ((WIDE && (jj & 1)) ? (rwoff ^ 128u) : rwoff) + jj * 4096) = rst[jj % 6];
+        *reinterpret_cast<float4 *>(lds + rwoff + jj * 4096) = rst[jj % 6];
     };
     // element (q, e) of a lane: row 32 q + (e & 3) + 8 (e >> 2) + 4 (lane >> 5) of the tile, column 32 wave + (lane & 31)
-    // wide form: element (q, e) of a lane: row 32 q + (lane & 31), column 32 wave + 8 (e >> 2) + 4 (lane >> 5) + (e & 3);
-    // a register quad g = e >> 2 is piece 8 wave + 2 g + (lane >> 5) of the row (swizzled: ^ (row & 15) = ^ (lane & 15))
-    const unsigned rroff = WIDE ? (unsigned)(RES_OFF + (lane & 31) * 512 + (((8 * wave + (lane >> 5)) ^ (lane & 15)) << 4))
-                                : (unsigned)(RES_OFF + (4 * (lane >> 5)) * 512 + (32 * wave + (lane & 31)) * 4);
-    const unsigned evoff = WIDE ? ((unsigned)(lane & 31) * (unsigned)p.N + (unsigned)(n0 + 32 * wave + 4 * (lane >> 5))) * 4u
-                                : ((unsigned)(4 * (lane >> 5)) * (unsigned)p.N + (unsigned)ncol) * 4u;
+    const unsigned rroff = (unsigned)(RES_OFF + (4 * (lane >> 5)) * 512 + (32 * wave + (lane & 31)) * 4);
+    const unsigned evoff = ((unsigned)(4 * (lane >> 5)) * (unsigned)p.N + (unsigned)ncol) * 4u;
 
     const float bias = (p.bias && wave_live) ? p.bias[ncol] : 0.f;
     const float one = lane < 32 ? 1.f : 0.f;
-    const float bias_k0 = lane < 32 ? bias : 0.f;  // wide form: the bias is the A operand (row index = channel), k = 0 only
     const float relu_lo = p.relu ? 0.f : -__builtin_inff();
     // MASK: the three mask words (32 rows x this lane's column) of the tile that accumulates in set S, requested when the
     // tile starts and used a whole tile later; out_bits() = what a store writes for element (q, e) of a set
-    static_assert(!(MASK && WIDE), "the mask words follow the narrow accumulator layout");
     unsigned mw[2][WT];
     const unsigned mvoff = wave_live ? (unsigned)ncol * 4u : OOB;
     auto load_mask = [&](auto set_c, int r0, bool live) __attribute__((always_inline)) {
@@ -273,16 +233,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[1][q][e] = 0.f;
 
-    // wide form: register quad idx = 4 q + g of accumulator set SET -> ReLU -> 16 bytes of row 32 q + (lane & 31)
-    using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-    auto store_quad = [&](auto set_c, int idx, RowRef yr) __attribute__((always_inline)) {
-        constexpr int SET = decltype(set_c)::value;
-        const int q = idx / 4, g = idx % 4;
-        u32x4 v;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] = __builtin_bit_cast(unsigned, fmaxf(acc[SET][q][4 * g + c], relu_lo));
-        __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_at(yr, 32 * q, p.N), evoff, 32 * g, 0);
-    };
 
     // One stage = 4 units (kb) of 12 MFMAs on the three accumulators, k outermost.  Slot D = 12 kb + m carries: the next
     // unit's fragment reads (m = 0); the A staging of tile j (registers -> LDS at D = 4 + 12 j, the request two stages on
@@ -321,19 +271,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     const int m = 3 * k + j, D = 12 * kb + m;
                     const float av = k == 0 ? fa[set][j].x : k == 1 ? fa[set][j].y : k == 2 ? fa[set][j].z : fa[set][j].w;
                     const float bv = k == 0 ? fb[kb].x : k == 1 ? fb[kb].y : k == 2 ? fb[kb].z : fb[kb].w;
-                    acc[SET][j] = WIDE ? __builtin_amdgcn_mfma_f32_32x32x2f32(bv, av, acc[SET][j], 0, 0, 0)
-                                       : __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[SET][j], 0, 0, 0);
+                    acc[SET][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[SET][j], 0, 0, 0);
                     if (m == 0 && kb < 3) read_a(buf, kb + 1, set ^ 1);
-#ifndef PWS_SKIP_STORE  // (timing experiments only: tools/README.md)
-                    if constexpr (SE0 >= 0 && WIDE) {
-                        if (D % SSTEP == 1 && SE0 + D / SSTEP < 4 * WT) store_quad(IC<SET ^ 1>{}, SE0 + D / SSTEP, yp);
-                    } else if constexpr (SE0 >= 0) if (D % SSTEP == 1 && SE0 + D / SSTEP < 16 * WT) {
+                    if constexpr (SE0 >= 0) if (D % SSTEP == 1 && SE0 + D / SSTEP < 16 * WT) {
                         const int q = (SE0 + D / SSTEP) / 16, e = (SE0 + D / SSTEP) % 16;
                         __builtin_amdgcn_raw_buffer_store_b32(out_bits(IC<SET ^ 1>{}, q, e),
-                                                              rsrc_at(yp, 32 * q + (e & 3) + 8 * (e >> 2), p.N), evoff, 0, PWS_STORE_AUX);
+                                                              rsrc_at(yp, 32 * q + (e & 3) + 8 * (e >> 2), p.N), evoff, 0, STORE_AUX);
                         if constexpr (EMIT) if (e == 15) emit_bits(IC<SET ^ 1>{}, q, r0p, plive);
                     }
-#endif
                     if (D >= 4 && D < 4 + 12 * WT && (D - 4) % 12 == 0) store_a(buf ^ 1, (D - 4) / 12);
                     if (D >= 6 && D < 6 + 12 * WT && (D - 6) % 12 == 0) load_a(xa, a_st, (D - 6) / 12);
                     if (m == 11) load_b(b_live, b_st, kb);
@@ -342,10 +287,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         // 6 + n into it)
                         if ((DUTY == 2 || DUTY == 3) && D >= 7 && D < 7 + 36 && (D - 7) % 6 == 0)
                             store_r((DUTY - 2) * 6 + (D - 7) / 6);
-#ifndef PWS_SKIP_RES
                         if ((DUTY == 1 || DUTY == 2) && D >= 9 && D < 9 + 36 && (D - 9) % 6 == 0)
                             load_r(rn, (DUTY - 1) * 6 + (D - 9) / 6);
-#endif
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -377,84 +320,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         __syncthreads();
     }
 
-#ifdef PWS_TRACE
-    unsigned long long ts[16];
-    int nts = 0;
-    for (int k = 0; k < 16; ++k) ts[k] = 0;
-#define PWS_STAMP(cond) do { if ((cond) && nts < 16) ts[nts++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define PWS_STAMP(cond) do { } while (0)
-#endif
     auto tile_body = [&](auto set_c, int i) __attribute__((always_inline)) {
         constexpr int SET = decltype(set_c)::value;
         const int r0c = r0_of(i), r0n = r0_of(i + 1);
         const bool nlive = i + 1 < n_my;
-#ifdef PWS_PRIO
-        if (PWS_PRIO == 2) {
-            if ((SET ^ slot_bit) & 1) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-        }
-#endif
-        PWS_STAMP(i == 2);  // 0: tile start
         const RowRef xc = row_ref(p.x, p.K, r0c, true), xn = row_ref(p.x, p.K, r0n, nlive);
         const RowRef rn = row_ref(p.residual, p.N, r0n, nlive);
         const RowRef yp = row_ref(p.y, p.N, r0_of(i - 1), i > 0 && wave_live);
         if constexpr (MASK) load_mask(IC<SET>{}, r0c, r0c < p.M);
         // the accumulators start from the residual (its LDS copy) ...
-        if constexpr (WIDE) {
 #pragma unroll
-            for (int q = 0; q < WT; ++q)
+        for (int q = 0; q < WT; ++q)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 r4 = RES ? *reinterpret_cast<const float4 *>(lds + (rroff ^ (unsigned)(32 * g)) + q * 16384)
-                                          : float4{0.f, 0.f, 0.f, 0.f};
-                    acc[SET][q][4 * g] = r4.x;
-                    acc[SET][q][4 * g + 1] = r4.y;
-                    acc[SET][q][4 * g + 2] = r4.z;
-                    acc[SET][q][4 * g + 3] = r4.w;
-                }
-            // ... + bias as one more k: A = bias of the lane's channel row (k = 0 only), B = 1
+            for (int e = 0; e < 16; ++e)
+                acc[SET][q][e] = RES ? *reinterpret_cast<const float *>(lds + rroff + (32 * q + (e & 3) + 8 * (e >> 2)) * 512) : 0.f;
+        // ... + bias as one more k: A = (1, 0) over the lane halves, B = bias of the lane's column
 #pragma unroll
-            for (int q = 0; q < WT; ++q) acc[SET][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(bias_k0, 1.f, acc[SET][q], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int q = 0; q < WT; ++q)
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    acc[SET][q][e] = RES ? *reinterpret_cast<const float *>(lds + rroff + (32 * q + (e & 3) + 8 * (e >> 2)) * 512) : 0.f;
-            // ... + bias as one more k: A = (1, 0) over the lane halves, B = bias of the lane's column
-#pragma unroll
-            for (int q = 0; q < WT; ++q) acc[SET][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(one, bias, acc[SET][q], 0, 0, 0);
-        }
+        for (int q = 0; q < WT; ++q) acc[SET][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(one, bias, acc[SET][q], 0, 0, 0);
         // stage (s, buffer s & 1, residual duty, first stored element, slots per store)
 #define PWS_STAGE(S_, DUTY_, SE0_, SSTEP_)                                                                            \
     stage_body(IC<SET>{}, IC<(S_) & 1>{}, IC<DUTY_>{}, IC<SE0_>{}, IC<SSTEP_>{}, S_, xc, true, xn, nlive, rn, yp,     \
                r0_of(i - 1), i > 0 && r0_of(i - 1) < p.M);                                                            \
     __syncthreads()
-        if constexpr (WIDE) {
-            // 12 quad stores: PWS_WSTEP slots apart (48 / PWS_WSTEP per stage) over the first stages; the residual duties
-            // as before in stages 1-3.  (after stage 0's barrier every wave has read its part of the residual copy:
-            // the next tile's may be written)
-            constexpr int WS = (!LONG && PWS_WSTEP > 16) ? 16 : PWS_WSTEP;  // (short K: four stages carry the 12 stores)
-            constexpr int PS = 48 / WS;                                      // stores per stage
-            static_assert((LONG ? 8 : 4) * PS >= 4 * WT, "not enough store slots for a tile");
-            PWS_STAGE(0, 0, 0, WS);
-            PWS_STAGE(1, 1, PS, WS);
-            PWS_STAGE(2, 2, 2 * PS, WS);
-            PWS_STAGE(3, 3, 3 * PS, WS);
-            if constexpr (LONG) {
-                PWS_STAGE(4, 0, 4 * PS, WS);
-                PWS_STAGE(5, 0, 5 * PS, WS);
-                PWS_STAGE(6, 0, 6 * PS, WS);
-                PWS_STAGE(7, 0, 7 * PS, WS);
-            }
-            for (int s = LONG ? 8 : 4; s < nst; s += 2) {
-                stage_body(IC<SET>{}, IC<0>{}, IC<0>{}, IC<-1>{}, IC<1>{}, s, xc, true, xn, nlive, rn, yp);
-                __syncthreads();
-                stage_body(IC<SET>{}, IC<1>{}, IC<0>{}, IC<-1>{}, IC<1>{}, s + 1, xc, true, xn, nlive, rn, yp);
-                __syncthreads();
-            }
-        } else if constexpr (LONG) {
+        if constexpr (LONG) {
             PWS_STAGE(0, 0, 0, 8);  // (after this barrier every wave has read its part of the residual copy: the
             PWS_STAGE(1, 1, 6, 8);  //  next tile's may be written)
             PWS_STAGE(2, 2, 12, 8);
@@ -482,7 +370,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
         }
 #undef PWS_STAGE
-        PWS_STAMP(i == 2);  // 1: K loop done
     };
     int i = 0;
     for (; i < n_my; i += 2) {
@@ -500,20 +387,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const RowRef yl = row_ref(p.y, p.N, r0s, wave_live);
     auto finish = [&](auto set_c) __attribute__((always_inline)) {
         constexpr int SET = decltype(set_c)::value;
-        if constexpr (WIDE) {
 #pragma unroll
-            for (int idx = 0; idx < 4 * WT; ++idx) store_quad(IC<SET>{}, idx, yl);
-        } else {
+        for (int q = 0; q < WT; ++q)
 #pragma unroll
-            for (int q = 0; q < WT; ++q)
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                {
-                    __builtin_amdgcn_raw_buffer_store_b32(out_bits(IC<SET>{}, q, e),
-                                                          rsrc_at(yl, 32 * q + (e & 3) + 8 * (e >> 2), p.N), evoff, 0, PWS_STORE_AUX);
-                    if constexpr (EMIT) if (e == 15) emit_bits(IC<SET>{}, q, r0s, r0s < p.M);
-                }
-        }
+            for (int e = 0; e < 16; ++e) {
+                __builtin_amdgcn_raw_buffer_store_b32(out_bits(IC<SET>{}, q, e),
+                                                      rsrc_at(yl, 32 * q + (e & 3) + 8 * (e >> 2), p.N), evoff, 0, STORE_AUX);
+                if constexpr (EMIT) if (e == 15) emit_bits(IC<SET>{}, q, r0s, r0s < p.M);
+            }
     };
     if (last & 1) finish(IC<1>{});  // block-uniform
     else finish(IC<0>{});
@@ -523,12 +404,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if (p.fform) mpsr::wino3z_filter_one(p.fw, p.fN, p.fC, p.fu, i);
             else mpsr::wino3_filter_one(p.fw, p.fN, p.fC, p.fu, i);
     }
-#ifdef PWS_TRACE
-    if (p.trace && lane == 0) {
-        unsigned long long *dst = p.trace + ((size_t)blockIdx.x * 4 + wave) * 16;
-        for (int k = 0; k < 16; ++k) dst[k] = ts[k];
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -618,13 +493,11 @@ __global__ __launch_bounds__(256) void fc_rows_kernel(const float *__restrict__ 
 
 std::atomic<int> g_pw_override{-1};  // -1 heuristic, 0 never, 1 wherever it applies
 std::atomic<int> g_pws_per_cu{2};
-unsigned long long *g_pw_trace = nullptr;
 
 }  // namespace
 
 extern "C" void mpsr_debug_set_conv_pointwise(int mode) { g_pw_override = mode; }
 extern "C" void mpsr_debug_set_pointwise_per_cu(int n) { g_pws_per_cu = n > 0 ? n : 2; }
-extern "C" void mpsr_debug_set_pointwise_trace(void *buf) { g_pw_trace = static_cast<unsigned long long *>(buf); }
 
 namespace mpsr {
 
@@ -642,7 +515,7 @@ bool pointwise_applies(long long M, int K, int N)
 // Shapes whose result can leave through a ReLU bit mask (conv1x1_pointwise_masked): the long-K instantiations
 bool pointwise_masked_applies(long long M, int K, int N)
 {
-    return !pws::WIDE && pointwise_applies(M, K, N) && K / pws::KS >= 8;
+    return pointwise_applies(M, K, N) && K / pws::KS >= 8;
 }
 
 static int pointwise_launch(const float *x, long long M, int K, const float *w, const float *bias, const float *residual,
@@ -705,7 +578,6 @@ static int pointwise_launch(const float *x, long long M, int K, const float *w, 
     int grid = g_pws_per_cu.load() * cus / unit * unit;
     if (grid < unit) grid = unit;
     if (grid > p.ntiles) grid = p.ntiles;
-    p.trace = g_pw_trace;
     // a pending filter-transform job rides on this launch
     p.fw = g_filter_tail_job.w; p.fu = g_filter_tail_job.u; p.fN = g_filter_tail_job.N; p.fC = g_filter_tail_job.C;
     p.fform = g_filter_tail_job.form;
@@ -718,7 +590,6 @@ static int pointwise_launch(const float *x, long long M, int K, const float *w, 
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));              \
         hipLaunchKernelGGL((pw_conv_kernel<__VA_ARGS__>), dim3(grid), dim3(256), lds_bytes, s, p);                    \
     } while (0)
-#if !PWS_WIDE
     if (mask || emit) {
         if (mask && residual) MPSR_PW(true, true, true);
         else if (mask) MPSR_PW(false, true, true);
@@ -727,7 +598,6 @@ static int pointwise_launch(const float *x, long long M, int K, const float *w, 
         MPSR_CHECK_LAUNCH("pw_conv_kernel");
         return MPSR_OK;
     }
-#endif
     if (K / KS >= 8) {
         if (residual) MPSR_PW(true, true);
         else MPSR_PW(false, true);

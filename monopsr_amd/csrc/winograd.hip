@@ -49,7 +49,6 @@ struct WinoParams {
     int dil;
     int cblocks, nblocks, mblocks, relu;
     unsigned xbytes, ubytes;
-    unsigned long long *trace;  // -DWINO_TRACE builds: per-workgroup timestamps (tools/wino_trace.py)
     // SPLIT instantiation of the eight-wave kernel (launches too small to fill the chip: one full image): K slices;
     // slice k runs channel steps [k * steps, (k + 1) * steps) and stores PARTIAL outputs into part + k * yfloats
     // (winograd3z.hip: winograd_finish_slices adds them in order, + bias, ReLU)
@@ -141,14 +140,6 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(const WinoParams p)
     const int mb = (l_ / p.nblocks) * 8 + xcd;
     if (mb >= p.mblocks) return;  // block-uniform
     const int n0 = nb * NT, t0 = mb * MT;
-#ifdef WINO_TRACE
-    unsigned long long ts[8];
-    int nts = 0;
-    ts[nts++] = __builtin_readcyclecounter();
-#define WINO_STAMP() do { if (nts < 8) ts[nts++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define WINO_STAMP() do { } while (0)
-#endif
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -287,7 +278,6 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(const WinoParams p)
         }
     }
     __syncthreads();
-    WINO_STAMP();  // 1: prologue done
     // The 256 accumulators fill the accumulator file, so the loop must not give the compiler a reason to copy them (a
     // branch that selects between two multiply blocks does: it then spills accumulators to scratch).  Hence the
     // rotation: first half of step 0 before the loop, one straight-line trip = [second half of step k, first half of
@@ -307,15 +297,8 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(const WinoParams p)
     for (int i = 0; i < 16; ++i) load_a1(1, nsteps > 1, i);
     compute(G0{}, [](int) {});
     __syncthreads();
-    WINO_STAMP();  // 2: first half of step 0 done
-#ifdef WINO_TRACE
-    unsigned long long sum_g1 = 0, sum_g0 = 0;
-#endif
     for (int k = 0; k + 1 < nsteps; ++k) {
         const bool more2 = k + 2 < nsteps;
-#ifdef WINO_TRACE
-        const unsigned long long h0 = __builtin_readcyclecounter();
-#endif
         compute(G1{}, [&](int slot) {
             if (slot < 4) row_transform_col(slot);
             else if (slot >= 8 && slot < 16) load_b1(k + 1, slot - 8, slot - 8);
@@ -324,29 +307,13 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(const WinoParams p)
             else if (slot >= 48 && slot < 56) store_b(slot - 48, slot - 48);
         });
         __syncthreads();
-        if (k == 0) WINO_STAMP();  // 3: second half of step 0 (with fillers) done
-#ifdef WINO_TRACE
-        const unsigned long long h1 = __builtin_readcyclecounter();
-        sum_g1 += h1 - h0;
-#endif
         compute(G0{}, [&](int slot) {
             if (slot < 8) load_b1(k + 1, 8 + slot, slot);
             else if (slot >= 12 && slot < 20) store_a(8 + slot - 12);
             else if (slot >= 40 && slot < 48) store_b(8 + slot - 40, slot - 40);
         });
         __syncthreads();
-        if (k == 0) WINO_STAMP();  // 4: first half of step 1 (with fillers) done
-#ifdef WINO_TRACE
-        sum_g0 += __builtin_readcyclecounter() - h1;
-#endif
     }
-#ifdef WINO_TRACE
-    if (p.trace && threadIdx.x == 0) {
-        p.trace[(size_t)(gridDim.x + blockIdx.x) * 8] = sum_g1;
-        p.trace[(size_t)(gridDim.x + blockIdx.x) * 8 + 1] = sum_g0;
-    }
-#endif
-    WINO_STAMP();  // 5: loop done
     compute(G1{}, [](int) {});
     // (the 16-pass MFMA needs 18 wait states before its result is read; made explicit as in conv_mfma.hip -- one
     // wait, tied to every accumulator so that no read is scheduled above it)
@@ -355,7 +322,6 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(const WinoParams p)
                    "+a"(acc[7]), "+a"(acc[8]), "+a"(acc[9]), "+a"(acc[10]), "+a"(acc[11]), "+a"(acc[12]),
                    "+a"(acc[13]), "+a"(acc[14]), "+v"(acc[15]));
 
-    WINO_STAMP();  // 6: last half done
     // ---- output transform + bias + ReLU + store.  Accumulator element e of a lane: tile row (e&3) + 8(e>>2) + 4(lane>>5)
     // of the wave's 32, output channel n0 + 32 wn + (lane & 31).
     const int n = n0 + wn * 32 + (lane & 31);
@@ -386,11 +352,6 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(const WinoParams p)
             o[(size_t)p.dil * p.W * p.N + (size_t)p.dil * p.N] = y11;
         }
     }
-#ifdef WINO_TRACE
-    WINO_STAMP();  // 7: epilogue issued
-    if (p.trace && tid == 0)
-        for (int i = 0; i < 8; ++i) p.trace[(size_t)blockIdx.x * 8 + i] = i < nts ? ts[i] : 0;
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -654,8 +615,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 }  // namespace
 
-static unsigned long long *g_wino_trace = nullptr;
-extern "C" void mpsr_debug_set_wino_trace(void *buf) { g_wino_trace = static_cast<unsigned long long *>(buf); }
 namespace mpsr { extern std::atomic<int> g_wino_waves; }
 extern "C" void mpsr_debug_set_wino_waves(int waves) { mpsr::g_wino_waves = waves; }
 
@@ -717,7 +676,6 @@ int conv3x3_winograd(const float *x, int B, int H, int W, int C, const float *w,
     p.relu = relu;
     p.xbytes = (unsigned)((long long)B * H * W * C * 4);
     p.ubytes = (unsigned)(winograd_scratch_floats(C, N) * 4);
-    p.trace = g_wino_trace;
     const long long blocks = 8LL * ceil_div(p.mblocks, 8) * p.nblocks;
     if (blocks > 0x7fffffffLL) return fail(MPSR_ERR_UNSUPPORTED, "conv3x3_winograd: grid too large");
     // launches too small to fill the chip (the full-image trunk's atrous layers at ONE image: 96 workgroups) are cut

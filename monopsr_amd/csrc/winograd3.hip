@@ -103,9 +103,6 @@ __device__ __forceinline__ void wino3_body(const Wino3Params &p, const int n0, c
     }
     float pa[25];  // 5x5: the 3x3 data arrives in the middle, the transforms expand it in place (HALO: all 25 arrive)
     auto load_patch1 = [&](int step, int L) __attribute__((always_inline)) {
-#ifdef W3_SKIP_LOAD
-        if (step > 1) return;
-#endif
         const bool live = step < nsteps;
         if constexpr (HALO) {
             const int s_ = L / 5, r_ = L % 5;  // column by column
@@ -124,9 +121,6 @@ __device__ __forceinline__ void wino3_body(const Wino3Params &p, const int n0, c
         }
     };
     auto vertical = [&](int j) __attribute__((always_inline)) {  // data column j (0..2; HALO: patch column j - 1 + 1 = 0..4) -> all five rows of it
-#ifdef W3_SKIP_VALU
-        return;
-#endif
         float t0_, t1_, t2_, t3_, t4_;
         if constexpr (HALO) {  // j = patch column 0..4
             bt5(pa[5 + j], pa[10 + j], pa[15 + j], t0_, t1_, t2_, t3_, t4_);
@@ -145,9 +139,6 @@ __device__ __forceinline__ void wino3_body(const Wino3Params &p, const int n0, c
         pa[20 + j + 1] = t4_;
     };
     auto horizontal = [&](int r) __attribute__((always_inline)) {  // row r (0..4): three values -> five (HALO: five -> five)
-#ifdef W3_SKIP_VALU
-        return;
-#endif
         float t0_, t1_, t2_, t3_, t4_;
         bt5(pa[5 * r + 1], pa[5 * r + 2], pa[5 * r + 3], t0_, t1_, t2_, t3_, t4_);
         if constexpr (HALO) {
@@ -163,11 +154,7 @@ __device__ __forceinline__ void wino3_body(const Wino3Params &p, const int n0, c
     // A[buf][pos][tile][8 channels], 16-byte halves swapped on odd 8-row blocks
     float *awr = lds + lt * 8 + 4 * ((ch >> 2) ^ ((lt >> 3) & 1)) + (ch & 3);
     auto store_a = [&](int buf, int pos) __attribute__((always_inline)) {
-#ifndef W3_SKIP_STORE  // (timing experiments only)
         awr[buf * ABUF + pos * APOS] = pa[pos];
-#else
-        asm volatile("" ::"v"(pa[pos]));
-#endif
     };
 
     // ---- B fragments from the transformed filters, lane = (n = lane & 31, k half = lane >> 5)
@@ -176,9 +163,6 @@ __device__ __forceinline__ void wino3_body(const Wino3Params &p, const int n0, c
     const unsigned bpstride = (unsigned)p.N * KC * 4u;
     float4 fb[NU][3];
     auto load_b1 = [&](int step, int q, int set, int j) __attribute__((always_inline)) {  // position q of the wave
-#ifdef W3_SKIP_BLOAD
-        if (step > 0) return;
-#endif
         const bool live = step < nsteps;
         const __amdgpu_buffer_rsrc_t rr =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.u), 0, live ? (int)p.ubytes : 0, 0x00020000);
@@ -294,24 +278,19 @@ __device__ __forceinline__ void wino3_body(const Wino3Params &p, const int n0, c
     __syncthreads();
 
     // ---- K loop, two steps per trip (roles as in winograd4.hip)
-#ifdef W3_NO_BARRIER  // (timing experiment only: wrong results)
-#define W3_SYNC() do { } while (0)
-#else
-#define W3_SYNC() __syncthreads()
-#endif
     if (DG == 0) {
         for (int s = 0; s < nsteps; s += 2) {
             kstep(s, IC3<0>{}, request(s + 2));
-            W3_SYNC();
+            __syncthreads();
             kstep(s + 1, IC3<1>{}, transform(IC3<0>{}));
-            W3_SYNC();
+            __syncthreads();
         }
     } else {
         for (int s = 0; s < nsteps; s += 2) {
             kstep(s, IC3<0>{}, transform(IC3<1>{}));
-            W3_SYNC();
+            __syncthreads();
             kstep(s + 1, IC3<1>{}, request(s + 3));
-            W3_SYNC();
+            __syncthreads();
         }
     }
     int tid2 = tid;

@@ -311,11 +311,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             gt(t[a][0], t[a][1], t[a][2], t[a][3], o[0], o[1], o[2]);
 #pragma unroll
             for (int b = 0; b < 3; ++b) {
-#ifdef W3G_NO_ATOMICS  // (timing experiment only: wrong results)
-                if (o[b] == 123.456f) dst[0] = o[b];
-#else
                 if (n < p.N && cc < p.C) unsafeAtomicAdd(dst + (size_t)(a * 3 + b) * p.C, o[b]);
-#endif
             }
         }
         __builtin_amdgcn_sched_barrier(0);

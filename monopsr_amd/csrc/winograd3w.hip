@@ -44,16 +44,11 @@ namespace f3w {
 constexpr int KC = 8, NP = 25;
 constexpr unsigned OOB = 0x80000000u;
 constexpr int cA(int p) { return p < 21 ? p % 3 : p - 21; }  // ring colour of position p's A fragment (4 quads)
-#ifndef W3W_BPRE
-#define W3W_BPRE 7
-#endif
-constexpr int BPRE = W3W_BPRE;  // B fragments requested this many positions ahead: 4 (ring of 5), 7 (ring of 9), 11 (ring of 13)
-constexpr int BRING = BPRE == 4 ? 5 : BPRE == 7 ? 9 : 13;
-static_assert(BPRE == 4 || BPRE == 7 || BPRE == 11, "ring colourings: 25 = 5 x 5, 8 + 8 + 9, 12 + 13");
-constexpr int cB(int p)  // ... of its B fragment
-{
-    return BPRE == 4 ? p % 5 : BPRE == 7 ? (p < 16 ? p % 8 : p - 16) : (p < 12 ? p : p - 12);
-}
+// B fragments requested this many positions ahead (28 MFMAs), ring of nine: 25 = 8 + 8 + 9.  Four ahead is late inside
+// a step, eleven measured equal
+constexpr int BPRE = 7;
+constexpr int BRING = 9;
+constexpr int cB(int p) { return p < 16 ? p % 8 : p - 16; }  // ... of its B fragment
 }  // namespace f3w
 
 struct Wino3WParams {
@@ -64,17 +59,6 @@ struct Wino3WParams {
     unsigned xbytes, ubytes, ybytes;
     FastDiv div_tpi, div_d;  // tiles per image = dil^2, dil
 };
-
-#ifdef W3W_TRACE  // (timing builds only: tools/wino3w_trace.py) cycle stamps of the first eight workgroups' waves
-__device__ unsigned long long g_w3w_trace[8 * 4 * 40];
-#define W3W_STAMP(i)                                                                                        \
-    do {                                                                                                    \
-        if (blockIdx.x < 8 && (threadIdx.x & 63) == 0)                                                      \
-            g_w3w_trace[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 40 + (i)] = __builtin_readcyclecounter();  \
-    } while (0)
-#else
-#define W3W_STAMP(i) do { } while (0)
-#endif
 
 template <int V>
 using ICW = std::integral_constant<int, V>;
@@ -99,15 +83,10 @@ __device__ __forceinline__ void static_for(F &&f)
 // which hipcc does not pad for inline asm -- the operands here are written by LDS / buffer loads only, and
 // tests/test_build_audit.py checks the compiled kernel for a vector-ALU write of an operand in the two instructions in
 // front of each MFMA; a blanket s_nop 1 measured 1 % of the K loop)
-#ifdef W3W_PAD_NOP
-#define W3W_PAD "s_nop 1\n\t"
-#else
-#define W3W_PAD ""
-#endif
 #define W3W_MFMA_A(q, a, b)                                                                                   \
-    asm volatile(W3W_PAD "v_mfma_f32_32x32x2_f32 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(a), "v"(b), "i"(16 * (q)), \
+    asm volatile("v_mfma_f32_32x32x2_f32 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(a), "v"(b), "i"(16 * (q)), \
                  "i"(16 * (q) + 15))
-#define W3W_MFMA_V(acc, a, b) asm volatile(W3W_PAD "v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b))
+#define W3W_MFMA_V(acc, a, b) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b))
 #define W3W_ZERO16(b)                                                                                                     \
     asm volatile("v_accvgpr_write_b32 a%c0, 0\n\tv_accvgpr_write_b32 a%c1, 0\n\tv_accvgpr_write_b32 a%c2, 0\n\t"          \
                  "v_accvgpr_write_b32 a%c3, 0\n\tv_accvgpr_write_b32 a%c4, 0\n\tv_accvgpr_write_b32 a%c5, 0\n\t"          \
@@ -153,7 +132,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int mb = (l_ / p.nblocks) * 8 + xcd;
     if (mb >= p.mblocks) return;  // block-uniform
     const int n0 = nb * NT, t0 = mb * MT;
-    W3W_STAMP(0);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int mi = wave % WM, ni = wave / WM;
@@ -206,9 +184,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // slot with its five stores behind it), the next-but-one step's nine requests per patch from slot 30 on
     auto duty = [&](int s, auto bufc, auto mc) __attribute__((always_inline)) {
         constexpr int m = decltype(mc)::value, nbuf = decltype(bufc)::value ^ 1;
-#ifdef W3W_SKIP_PROD  // (timing experiments only: wrong results)
-        return;
-#endif
         static_for<WM>([&](auto rc) __attribute__((always_inline)) {
             constexpr int r = decltype(rc)::value, o = m - 14 * r;
             if constexpr (o >= 0 && o < 3) vertical(rc, ICW<o>{});
@@ -237,9 +212,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.u), 0, (int)p.ubytes, 0x00020000);
     auto load_b = [&](int step, auto qc) __attribute__((always_inline)) {
         constexpr int q = decltype(qc)::value;
-#ifdef W3W_SKIP_BLOAD
-        if (step > 0) return;
-#endif
         const unsigned so = ((unsigned)step * (unsigned)NP + (unsigned)q) * bpstride;
         fb[cB(q)] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ru, bvoff, so, 0));
     };
@@ -248,9 +220,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     float4 fa[4];
     auto load_a = [&](int buf, auto qc) __attribute__((always_inline)) {
         constexpr int q = decltype(qc)::value;
-#ifdef W3W_SKIP_ALOAD
-        if (buf >= 0 && q > 1) return;
-#endif
         fa[cA(q)] = *reinterpret_cast<const float4 *>(ard + buf * ABUF + q * APOS);
     };
 
@@ -286,7 +255,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     __syncthreads();
     load_a(0, ICW<0>{});
     load_a(0, ICW<1>{});
-    W3W_STAMP(1);
 
     // ---- K loop: slot m = MFMA k = m % 4 of position q = m / 4, followed by the slot's loads and producer work
     auto kstep = [&](int s, auto bufc) __attribute__((always_inline)) {
@@ -297,9 +265,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const float bv = k == 0 ? fb[cB(q)].x : k == 1 ? fb[cB(q)].y : k == 2 ? fb[cB(q)].z : fb[cB(q)].w;
             mfma(ICW<q>{}, av, bv);
             if constexpr (k == 0) {
-#ifndef W3W_NO_BARRIER
                 if constexpr (m == 92) __syncthreads();
-#endif
                 if constexpr (q + 2 < NP) load_a(buf, ICW<(q + 2) % NP>{});
                 else load_a(buf ^ 1, ICW<(q + 2) % NP>{});
             }
@@ -313,12 +279,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     };
     for (int s = 0; s < nsteps; s += 2) {
         kstep(s, ICW<0>{});
-        if (s < 32) W3W_STAMP(2 + s);
         kstep(s + 1, ICW<1>{});
-        if (s < 32) W3W_STAMP(3 + s);
     }
     // the last MFMAs' results: 18 wait states before anything reads them (hipcc pads nothing behind inline asm)
-    W3W_STAMP(34);
     int lane2 = lane;
     asm volatile("s_nop 15\n\ts_nop 7"
                  : "+v"(accV[0]), "+v"(accV[1]), "+v"(accV[2]), "+v"(accV[3]), "+v"(accV[4]), "+v"(accV[5]), "+v"(accV[6]),
@@ -374,7 +337,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
         __builtin_amdgcn_sched_barrier(0);  // (one register column at a time: hipcc otherwise hoists all 400 reads)
     });
-    W3W_STAMP(35);
 }
 
 }  // namespace
@@ -430,10 +392,3 @@ int launch_winograd3w(const float *x, int B, int H, int W, int C, const float *u
 
 }  // namespace mpsr
 
-#ifdef W3W_TRACE
-extern "C" int mpsr_debug_wino3w_trace(unsigned long long *host_out, int count)
-{
-    if (count > 8 * 4 * 40) count = 8 * 4 * 40;
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_w3w_trace), sizeof(unsigned long long) * count) == hipSuccess ? 0 : 1;
-}
-#endif

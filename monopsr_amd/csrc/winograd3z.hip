@@ -62,17 +62,6 @@ struct Wino3ZParams {
     int nslices, steps;
 };
 
-#ifdef W3Z_TRACE  // (timing builds only: tools/wino3w_trace.py) cycle stamps of the first eight workgroups' waves
-__device__ unsigned long long g_w3z_trace[8 * 4 * 40];
-#define W3Z_STAMP(i)                                                                                        \
-    do {                                                                                                    \
-        if (blockIdx.x < 8 && (threadIdx.x & 63) == 0)                                                      \
-            g_w3z_trace[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 40 + (i)] = __builtin_readcyclecounter();  \
-    } while (0)
-#else
-#define W3Z_STAMP(i) do { } while (0)
-#endif
-
 template <int V>
 using ICZ = std::integral_constant<int, V>;
 template <int... Is, class F>
@@ -93,19 +82,9 @@ __device__ __forceinline__ void static_for(F &&f)
 // which hipcc does not pad for inline asm -- the operands here are written by LDS / buffer loads only, and
 // tests/test_build_audit.py checks the compiled kernel for a vector-ALU write of an operand in the two instructions in
 // front of each MFMA; a blanket s_nop 1 measured 1 % of the K loop)
-#ifndef W3Z_BAUX
-#define W3Z_BAUX 0  // cache policy of the transformed-filter loads: 2 = non-temporal (A/B builds)
-#endif
-#ifndef W3Z_STORE_AUX
-#define W3Z_STORE_AUX 0  // cache policy of the result stores: 2 = non-temporal (A/B builds)
-#endif
-#ifdef W3Z_PAD_NOP
-#define W3Z_PAD "s_nop 1\n\t"
-#else
-#define W3Z_PAD ""
-#endif
+// (the non-temporal cache policy on the transformed-filter loads or the result stores measured slower: DESIGN.md 4.1 (f))
 #define W3Z_MFMA_A(q, a, b)                                                                                   \
-    asm volatile(W3Z_PAD "v_mfma_f32_32x32x2_f32 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(a), "v"(b), "i"(16 * (q)), \
+    asm volatile("v_mfma_f32_32x32x2_f32 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(a), "v"(b), "i"(16 * (q)), \
                  "i"(16 * (q) + 15))
 #define W3Z_ZERO16(b)                                                                                                     \
     asm volatile("v_accvgpr_write_b32 a%c0, 0\n\tv_accvgpr_write_b32 a%c1, 0\n\tv_accvgpr_write_b32 a%c2, 0\n\t"          \
@@ -158,7 +137,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int mb = l2_ * 8 + xcd;
     if (mb >= p.mblocks) return;  // block-uniform
     const int n0 = nb * NT, t0 = mb * MT;
-    W3Z_STAMP(0);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int mi = wave % WM, ni = wave / WM;
@@ -210,9 +188,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // four stores behind it), the next-but-one step's nine requests from slot 16 on
     auto duty = [&](int s, auto bufc, auto mc) __attribute__((always_inline)) {
         constexpr int m = decltype(mc)::value, nbuf = decltype(bufc)::value ^ 1;
-#ifdef W3Z_SKIP_PROD  // (timing experiments only: wrong results)
-        return;
-#endif
         static_for<WM>([&](auto rc) __attribute__((always_inline)) {
             constexpr int o = m;
             if constexpr (o >= 0 && o < 3) vertical(rc, ICZ<o>{});
@@ -240,20 +215,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.u), 0, (int)p.ubytes, 0x00020000);
     auto load_b = [&](int step, auto qc) __attribute__((always_inline)) {
         constexpr int q = decltype(qc)::value;
-#ifdef W3Z_SKIP_BLOAD
-        if (step > 0) return;
-#endif
         const unsigned so = ((unsigned)step * (unsigned)NP + (unsigned)q) * bpstride;
-        fb[cB(q)] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ru, bvoff, so, W3Z_BAUX));
+        fb[cB(q)] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ru, bvoff, so, 0));
     };
     // ---- A fragments: lane = (tile = lane & 31 of the wave's 32, k half = lane >> 5)
     const float *ard = lds + (32 * mi + (lane & 31)) * 8 + 4 * ((lane >> 5) ^ (((lane & 31) >> 3) & 1));
     float4 fa[4];
     auto load_a = [&](int buf, auto qc) __attribute__((always_inline)) {
         constexpr int q = decltype(qc)::value;
-#ifdef W3Z_SKIP_ALOAD
-        if (buf >= 0 && q > 1) return;
-#endif
         fa[cA(q)] = *reinterpret_cast<const float4 *>(ard + buf * ABUF + q * APOS);
     };
 
@@ -279,7 +248,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     __syncthreads();
     load_a(0, ICZ<0>{});
     load_a(0, ICZ<1>{});
-    W3Z_STAMP(1);
 
     // ---- K loop: slot m = MFMA k = m % 4 of position q = m / 4, followed by the slot's loads and producer work
     auto kstep = [&](int s, auto bufc) __attribute__((always_inline)) {
@@ -290,9 +258,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const float bv = k == 0 ? fb[cB(q)].x : k == 1 ? fb[cB(q)].y : k == 2 ? fb[cB(q)].z : fb[cB(q)].w;
             mfma(ICZ<q>{}, av, bv);
             if constexpr (k == 0) {
-#ifndef W3Z_NO_BARRIER
                 if constexpr (m == 4 * (NP - 2)) __syncthreads();
-#endif
                 if constexpr (q + 2 < NP) load_a(buf, ICZ<(q + 2) % NP>{});
                 else load_a(buf ^ 1, ICZ<(q + 2) % NP>{});
             }
@@ -306,12 +272,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     };
     for (int s = s0; s < send; s += 2) {
         kstep(s, ICZ<0>{});
-        if (s - s0 < 32) W3Z_STAMP(2 + s - s0);
         kstep(s + 1, ICZ<1>{});
-        if (s - s0 < 32) W3Z_STAMP(3 + s - s0);
     }
     // the last MFMAs' results: 18 wait states before anything reads them (hipcc pads nothing behind inline asm)
-    W3Z_STAMP(34);
     int lane2 = lane;
     asm volatile("s_nop 15\n\ts_nop 7" : "+v"(lane2));
 
@@ -358,12 +321,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int i = 0; i < 3; ++i) {
                 float v = fmaxf(yv[i] + bias_v, floor_v);
                 if constexpr (MASK) v = mk[3 * j + i] > 0.f ? v : 0.f;
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), ry, voff, so[3 * j + i], W3Z_STORE_AUX);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), ry, voff, so[3 * j + i], 0);
             }
         }
         __builtin_amdgcn_sched_barrier(0);  // (one register column at a time: hipcc otherwise hoists all 256 reads)
     });
-    W3Z_STAMP(35);
 }
 
 }  // namespace
@@ -483,10 +445,3 @@ int launch_winograd3z_filter(const float *w, int N, int C, float *u, hipStream_t
 
 extern "C" void mpsr_debug_set_wino3z_split(int slices) { mpsr::g_w3z_split = slices; }
 
-#ifdef W3Z_TRACE
-extern "C" int mpsr_debug_wino3z_trace(unsigned long long *host_out, int count)
-{
-    if (count > 8 * 4 * 40) count = 8 * 4 * 40;
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_w3z_trace), sizeof(unsigned long long) * count) == hipSuccess ? 0 : 1;
-}
-#endif

@@ -64,7 +64,6 @@ struct Wino4Params {
     float *part;  // split kernel: partial outputs of the first-arriving half, laid out like y
     int *sync;    // split kernel: a ticket and a flag per pair of workgroups, zeroed before the launch
     unsigned pbytes;
-    unsigned long long *trace;  // -DW4_TRACE builds: per-wave cycle stamps of two K steps (tools/wino4_trace.py)
 };
 
 // U[cb][pos][n][8] = (G g G^T)[pos] for filter g = w[n][(ky*3+kx)*C + c], c = cb*8 + j.  One thread per (n, c).
@@ -131,27 +130,8 @@ __device__ __forceinline__ void at4(float m0, float m1, float m2, float m3, floa
 template <int V>
 using IC = std::integral_constant<int, V>;
 
-#ifndef W4_BAUX
-#define W4_BAUX 0  // cache policy of the transformed-filter loads / the patch loads: 2 = non-temporal (A/B builds)
-#endif
-#ifndef W4_AAUX
-#define W4_AAUX 0
-#endif
-#ifndef W4_NT
-#define W4_NT 0  // 1: the result leaves through non-temporal stores (A/B builds)
-#endif
-#ifndef W4_SPREAD
-#define W4_SPREAD 0
-#endif
-#ifndef W4_PRIO
-#define W4_PRIO 1  // static issue priority inside the K loop: 0 none, 1 waves 4-7 (shipped), 2 waves 0-3
-#endif
-#ifndef W4_BPRE
-#define W4_BPRE 1  // B fragments requested this many units (of 12 MFMAs) ahead: 1 (two register sets) or 2 (three)
-#endif
-#ifndef W4_APRE
-#define W4_APRE 0  // 1: read the next unit's A fragments during the current unit (12 more registers)
-#endif
+// (The non-temporal cache policy on the transformed-filter loads, the patch loads or the result stores measured slower:
+// DESIGN.md 4.1 (f), "cache policy of the once-through streams".)
 
 // IN_C8 / OUT_C8: the tensor is channel-blocked, [B][C/8][H][W][8] ("C8"), instead of NHWC.  A K step then reads
 // whole 128-byte lines (4 pixels x 8 channels) instead of 32 bytes out of every pixel's line: the decoder's internal
@@ -170,14 +150,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (mb >= p.mblocks) return;  // block-uniform
     const int n0 = nb * NT, t0 = mb * MT;
 
-#ifdef W4_TRACE
-    unsigned long long ts[16];
-    int nts = 0;
-#define W4_STAMP(cond) do { if ((cond) && nts < 16) ts[nts++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define W4_STAMP(cond) do { } while (0)
-#endif
-    W4_STAMP(true);  // 0: start
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = wave >> 1, nh = wave & 1;  // consumer role: position block, channel half
@@ -217,9 +189,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // request number L of a patch, column by column (the column transforms start with column 0)
     auto load_patch1 = [&](int step, int L) __attribute__((always_inline)) {
         const int s = L / 6, r = L % 6;
-#ifdef W4_SKIP_LOAD
-        if (step > 1) return;
-#endif
         const bool live = step < nsteps;
         // (a request past the last channel block goes through a zero-length descriptor: a scalar select)
         const __amdgpu_buffer_rsrc_t rr =
@@ -228,16 +197,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                   : (unsigned)((r * p.W + s) * p.C + (live ? step : 0) * KC) * 4u;
         pa[6 * r + s] = __builtin_bit_cast(
             float, __builtin_amdgcn_raw_buffer_load_b32(rr, voffc[r == 0 ? 0 : r == 5 ? 2 : 1][s == 0 ? 0 : s == 5 ? 2 : 1],
-                                                        so, W4_AAUX));
+                                                        so, 0));
     };
     // B^T applied to six values in place, in three parts of four operations (parts 0 and 1 read the original values,
     // part 2 finishes from part 0's temporaries)
     float ta, tb, tc, te;
     auto bt_part = [&](int part, float &d0, float &d1, float &d2, float &d3, float &d4, float &d5)
                        __attribute__((always_inline)) {
-#ifdef W4_SKIP_VALU
-        return;
-#endif
         if (part == 0) {
             ta = fmaf(-4.f, d2, d4);
             tb = fmaf(-4.f, d1, d3);
@@ -262,11 +228,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // A[buf][pos][tile][8 channels], 16-byte halves swapped on odd 8-row blocks
     float *awr = lds + lt * 8 + 4 * ((ch >> 2) ^ ((lt >> 3) & 1)) + (ch & 3);
     auto store_a = [&](int buf, int pos) __attribute__((always_inline)) {
-#ifndef W4_SKIP_STORE  // (timing experiments only: tools/README.md)
         awr[buf * ABUF + pos * APOS] = pa[pos];
-#else
-        asm volatile("" ::"v"(pa[pos]));
-#endif
     };
 
     // ---- B fragments straight from the transformed filters (L2) into registers: wave (g, nh) is the only consumer
@@ -275,25 +237,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const unsigned bvoff =
         n0 + 32 * nh + (lane & 31) < p.N ? (unsigned)((n0 + 32 * nh + (lane & 31)) * KC + 4 * (lane >> 5)) * 4u : OOB;
     const unsigned bpstride = (unsigned)p.N * KC * 4u;  // bytes between positions of one channel block
-    float4 fb[1 + W4_BPRE][3];
+    float4 fb[2][3];  // two register sets: a unit's B fragments, the next unit's in flight
     auto load_b1 = [&](int step, int u, int j, int set) __attribute__((always_inline)) {
-#ifdef W4_SKIP_BLOAD
-        if (step > 0) return;
-#endif
         const bool live = step < nsteps;
         const __amdgpu_buffer_rsrc_t rr =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.u), 0, live ? (int)p.ubytes : 0, 0x00020000);
         const unsigned so = ((unsigned)(live ? step : 0) * 36u + (unsigned)(gpos + 6 * u + j)) * bpstride;
-        fb[set][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rr, bvoff, so, W4_BAUX));
+        fb[set][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rr, bvoff, so, 0));
     };
 
     // ---- A fragment address: row = lane & 31 (tile), k half = lane >> 5
     const float *ard = lds + gpos * APOS + (lane & 31) * 8 + 4 * ((lane >> 5) ^ (((lane & 31) >> 3) & 1));
-    float4 fa[1 + W4_APRE][3];
-    auto read_a = [&](int buf, int u, int set) __attribute__((always_inline)) {
+    float4 fa[3];
+    auto read_a = [&](int buf, int u) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-            fa[set][j] = *reinterpret_cast<const float4 *>(ard + buf * ABUF + (6 * u + j) * APOS);
+            fa[j] = *reinterpret_cast<const float4 *>(ard + buf * ABUF + (6 * u + j) * APOS);
     };
 
     f32x16 acc[9];
@@ -310,37 +269,28 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // (parity bpar of the register sets alternates unit by unit: 3 units per step, two steps per loop trip).
     auto kstep = [&](int s, auto buf_c, auto &&duty) __attribute__((always_inline)) {
         constexpr int buf = decltype(buf_c)::value;
-        W4_STAMP((s >> 1) == 4);  // steps 8 and 9: step start, after each unit, after the barrier
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
-            // register set of this unit's B fragments: distance 1 -> the two sets alternate unit by unit (3 units per
-            // step, two steps per loop trip); distance 2 -> unit u always uses set u
-            const int bpar = W4_BPRE == 2 ? u : (3 * buf + u) & 1;
-            const int aset = W4_APRE ? ((3 * buf + u) & 1) : 0;
-            if (!W4_APRE || u == 0) read_a(buf, u, aset);
+            // register set of this unit's B fragments: the two sets alternate unit by unit (3 units per step, two steps
+            // per loop trip)
+            const int bpar = (3 * buf + u) & 1;
+            read_a(buf, u);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     const int m = 12 * u + 3 * k + j;
-                    const float av = k == 0 ? fa[aset][j].x : k == 1 ? fa[aset][j].y : k == 2 ? fa[aset][j].z : fa[aset][j].w;
+                    const float av = k == 0 ? fa[j].x : k == 1 ? fa[j].y : k == 2 ? fa[j].z : fa[j].w;
                     const float bv = k == 0 ? fb[bpar][j].x : k == 1 ? fb[bpar][j].y : k == 2 ? fb[bpar][j].z : fb[bpar][j].w;
                     acc[3 * u + j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[3 * u + j], 0, 0, 0);
                     if (k == 0) {
-                        if (W4_BPRE == 2) {  // unit u + 2 (of this step or the next) into the set unit u - 1 just left
-                            if (u == 0) load_b1(s, 2, j, 2);
-                            else load_b1(s + 1, u - 1, j, u - 1);
-                        } else {
-                            if (u < 2) load_b1(s, u + 1, j, bpar ^ 1);
-                            else load_b1(s + 1, 0, j, bpar ^ 1);
-                        }
+                        if (u < 2) load_b1(s, u + 1, j, bpar ^ 1);
+                        else load_b1(s + 1, 0, j, bpar ^ 1);
                     }
-                    if (W4_APRE && k == 2 && j == 0 && u < 2) read_a(buf, u + 1, aset ^ 1);
                     duty(m);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-            W4_STAMP((s >> 1) == 4);
         }
     };
     // Producer duties.  request: 18 loads in slots 3-11 and 18 in slots 15-23, two per slot -- behind each unit's B
@@ -349,9 +299,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // of a finished row follow two per slot from slot 21; the last row's six after the step's last MFMA.
     auto request = [&](int step) __attribute__((always_inline)) {
         return [&, step](int slot) __attribute__((always_inline)) {
-#if W4_SPREAD
-            load_patch1(step, slot);  // one request per slot
-#else
             if (slot >= 3 && slot < 12) {
                 load_patch1(step, 2 * (slot - 3));
                 load_patch1(step, 2 * (slot - 3) + 1);
@@ -359,21 +306,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 load_patch1(step, 18 + 2 * (slot - 15));
                 load_patch1(step, 18 + 2 * (slot - 15) + 1);
             }
-#endif
         };
     };
     auto transform = [&](auto buf_c) __attribute__((always_inline)) {
         return [&](int slot) __attribute__((always_inline)) {
             constexpr int buf = decltype(buf_c)::value;
-#ifdef W4_HALF_DUTY  // timing experiment: the producer work of a workgroup that owns 18 of the 36 positions
-            if (slot < 18) { if (slot % 3 != 2) vertical(slot / 3, slot % 3); }
-            else if (slot < 27) horizontal((slot - 18) / 3, (slot - 18) % 3);
-            if (slot >= 21 && slot < 30) {
-                store_a(buf, 2 * (slot - 21));
-                store_a(buf, 2 * (slot - 21) + 1);
-            }
-            if (true) return;
-#endif
             if (slot < 18) vertical(slot / 3, slot % 3);
             else horizontal((slot - 18) / 3, (slot - 18) % 3);
             if (slot >= 21) {
@@ -389,9 +326,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- prologue: B of (step 0, unit 0); A of step 0 by waves 0-3; the patch of step 1 requested by waves 4-7
 #pragma unroll
     for (int j = 0; j < 3; ++j) load_b1(0, 0, j, 0);
-    if (W4_BPRE == 2)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) load_b1(0, 1, j, 1);
 #pragma unroll
     for (int i = 0; i < 36; ++i) load_patch1(dgrp, i);
     if (dgrp == 0) {
@@ -403,7 +337,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int i = 0; i < 36; ++i) store_a(0, i);
     }
     __syncthreads();
-    W4_STAMP(true);  // 1: prologue done
 
     // ---- K loop, two steps per trip.  Waves 0-3: even step = request the patch of step s + 2, odd step = transform
     // it into buffer 0.  Waves 4-7: even step = transform the patch of step s + 1 into buffer 1, odd step = request
@@ -411,37 +344,26 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // Static priority for the second-dispatched half of the workgroup (MI355X_MICROARCH.md, "two waves per SIMD", item 4:
     // the younger wave of a SIMD loses the issue arbitration at every segment start; one s_setprio for the whole K loop,
     // no per-segment flips).  r06, same-session step A/B over three rounds each (tools/step_libs.sh): 13.339 ms without,
-    // 13.323 with waves 0-3 raised, 13.313 with waves 4-7 raised (-2.5 % of this kernel's two launches); 0 = off.
-#if W4_PRIO
-    if (dgrp == (W4_PRIO == 1 ? 1 : 0)) __builtin_amdgcn_s_setprio(1);
-#endif
+    // 13.323 with waves 0-3 raised, 13.313 with waves 4-7 raised (-2.5 % of this kernel's two launches).
+    if (dgrp == 1) __builtin_amdgcn_s_setprio(1);
     if (dgrp == 0) {
         for (int s = 0; s < nsteps; s += 2) {
             kstep(s, IC<0>{}, request(s + 2));
             __syncthreads();
-            W4_STAMP(s == 8);
             kstep(s + 1, IC<1>{}, transform(IC<0>{}));
             __syncthreads();
-            W4_STAMP(s == 8);
         }
     } else {
         for (int s = 0; s < nsteps; s += 2) {
             kstep(s, IC<0>{}, transform(IC<1>{}));
             __syncthreads();
-            W4_STAMP(s == 8);
             kstep(s + 1, IC<1>{}, request(s + 3));
             __syncthreads();
-            W4_STAMP(s == 8);
         }
     }
     // (the 16-pass MFMA needs 18 wait states before its result is read; made explicit as in conv_mfma.hip.  Plain
     // vector registers: with an "a" constraint hipcc splits the 256-register budget 128 + 128 and spills)
-#ifdef W4_TRACE
-    W4_STAMP(true);  // 12: K loop done
-#endif
-#if W4_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     int tid2 = tid;
     asm volatile("s_nop 15\n\ts_nop 7"
                  : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]), "+v"(acc[6]),
@@ -474,7 +396,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 mwr[(6 * (q / 3) + q % 3) * (16 * 64) + trow * 64] = acc[q][e];
             }
         __syncthreads();
-        W4_STAMP(round == 0);  // 13: round 0 exchanged
         const int tt = t0 + 16 * round + (tid2 >> 5);
         const int img = tt / tpi, rem = tt - img * tpi;
         const int ty = rem / p.tw, tx = rem - ty * p.tw;
@@ -503,22 +424,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int yy = 0; yy < 4; ++yy) {
                     float v = yv[yy] + bias2[h];
                     if (p.relu) v = fmaxf(v, 0.f);
-#if W4_NT
-                    if (ok) __builtin_nontemporal_store(v, &o[((size_t)yy * p.W + xx) * pstride]);
-#else
                     if (ok) o[((size_t)yy * p.W + xx) * pstride] = v;
-#endif
                 }
             }
         }
-        W4_STAMP(true);  // 14, 15: round finished (stores issued)
     }
-#ifdef W4_TRACE
-    if (p.trace && lane2 == 0) {
-        unsigned long long *dst = p.trace + ((size_t)blockIdx.x * 8 + wave) * 16;
-        for (int i = 0; i < 16; ++i) dst[i] = i < nts ? ts[i] : 0;
-    }
-#endif
 }
 
 
@@ -584,7 +494,7 @@ __device__ __forceinline__ void wino4s_body(const Wino4Params &p, const int mb, 
                                   : (unsigned)((r * p.W + s) * p.C + (live ? step : 0) * KC) * 4u;
         pa[6 * r + s] = __builtin_bit_cast(
             float, __builtin_amdgcn_raw_buffer_load_b32(rr, voffc[r == 0 ? 0 : r == 5 ? 2 : 1][s == 0 ? 0 : s == 5 ? 2 : 1],
-                                                        so, W4_AAUX));
+                                                        so, 0));
     };
     float ta, tb, tc, te;
     // column s of the patch -> rows 3 half .. 3 half + 2 of B^T d, left in rows 0..2; two parts of three operations
@@ -644,7 +554,7 @@ __device__ __forceinline__ void wino4s_body(const Wino4Params &p, const int mb, 
         const __amdgpu_buffer_rsrc_t rr =
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.u), 0, live ? (int)p.ubytes : 0, 0x00020000);
         const unsigned so = ((unsigned)(live ? step : 0) * 36u + (unsigned)(gpos + 6 * u + j)) * bpstride;
-        fb[set][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rr, bvoff, so, W4_BAUX));
+        fb[set][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rr, bvoff, so, 0));
     };
     const float *ard = lds + 3 * jb * APOS + (lane & 31) * 8 + 4 * ((lane >> 5) ^ (((lane & 31) >> 3) & 1));
     float4 fa[3];
@@ -820,13 +730,8 @@ __device__ __forceinline__ void wino4s_body(const Wino4Params &p, const int mb, 
     // flag, done.  Ticket 1: the partner holds ticket 0 and is publishing -- wait for its flag (one lane polls), read,
     // finish.  (Measured against "both publish, the last one finishes, nobody waits": that form writes every partial.)
     __syncthreads();
-#ifdef W4S_NOSYNC  // (timing experiment: no publication, no ticket -- wrong results)
-    if (tid2 == 0) *ticket_slot = 1;
-#else
     if (tid2 == 0) *ticket_slot = __hip_atomic_fetch_add(p.sync + 2 * pair, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     __syncthreads();
-#ifndef W4S_NOSYNC
     if (*ticket_slot == 0) {
 #pragma unroll
         for (int round = 0; round < 2; ++round)
@@ -845,7 +750,6 @@ __device__ __forceinline__ void wino4s_body(const Wino4Params &p, const int mb, 
         while (__hip_atomic_load(p.sync + 2 * pair + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
             __builtin_amdgcn_s_sleep(2);
     __syncthreads();
-#endif
     {  // the partner's partials are complete: finish the outputs
         f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
         if (p.bias) bias4 = *reinterpret_cast<const f32x4 *>(p.bias + n);
@@ -855,13 +759,9 @@ __device__ __forceinline__ void wino4s_body(const Wino4Params &p, const int mb, 
             f32x4 other[16];
 #pragma unroll
             for (int px = 0; px < 16; ++px)
-#ifdef W4S_NOSYNC
-                other[px] = f32x4{0.f, 0.f, 0.f, 0.f};
-#else
                 other[px] = __builtin_bit_cast(
                     f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                rpart, obase[round] + (unsigned)(((px >> 2) * p.W + (px & 3)) * pstride * 4), 0, 17));
-#endif
 #pragma unroll
             for (int px = 0; px < 16; ++px) {
                 f32x4 v = mine[round][px] + other[px] + bias4;
@@ -927,8 +827,6 @@ extern "C" int mpsr_debug_fetch_calibration(const float *p, size_t floats, int m
     return MPSR_OK;
 }
 
-static unsigned long long *g_wino4_trace = nullptr;
-extern "C" void mpsr_debug_set_wino4_trace(void *buf) { g_wino4_trace = static_cast<unsigned long long *>(buf); }
 
 namespace mpsr { extern std::atomic<int> g_wino4_split; }
 extern "C" void mpsr_debug_set_wino4_split(int on) { mpsr::g_wino4_split = on; }
@@ -1008,7 +906,6 @@ int conv3x3_winograd4(const float *x, int B, int H, int W, int C, const float *w
     p.xbytes = (unsigned)xbytes;
     p.ubytes = (unsigned)(winograd4_scratch_floats(C, N) * 4);
     p.part = nullptr; p.sync = nullptr; p.pbytes = 0;
-    p.trace = g_wino4_trace;
     long long blocks = 8LL * ceil_div(p.mblocks, 8) * p.nblocks;
     if (split) blocks *= 2;
     if (blocks > 0x7fffffffLL) return fail(MPSR_ERR_UNSUPPORTED, "conv3x3_winograd4: grid too large");

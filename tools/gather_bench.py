@@ -1,9 +1,7 @@
 """The decoder's two upsampled convolutions (conv2_1: 12x12x512 -> 24x24x256; conv3_1: 24x24x256 -> 48x48x128, B = 256;
 reference net_builder.py:72-77, :81-85) through mpsr_conv3x3_upsampled_f32, per kernel: the tap GEMMs (pw_conv_kernel)
 and upconv_gather_kernel, durations from torch.profiler (roctracer records), whole call from HIP events.
-Knock-out builds (tools/build_variant.sh <name> upconv.hip -DUPC_SKIP_SUM / -DUPC_SKIP_LOAD / -DUPC_SKIP_STORE, then
-MPSR_LIB_PATH=abl/<name>.so) say which of the gather's three streams (LDS reads + arithmetic, z loads, result stores)
-its time follows.  usage: python tools/gather_bench.py [--batch 256] [--reps 10]"""
+usage: python tools/gather_bench.py [--batch 256] [--reps 10]"""
 import argparse
 import json
 import os

@@ -74,8 +74,8 @@ def main(tag, commit, paths):
         # (every long kernel of every collection gives GUI_ACTIVE / 8 / duration = 2.41-2.46 GHz), while
         # SQ_VALU_MFMA_BUSY_CYCLES counts shader cycles: mfma_busy is therefore a fraction of TIME at the nominal clock
         # -- it already contains the clock the power limit takes away -- and compares directly with bench.py's
-        # roofline.frac.  The fraction of a wave's own CYCLES spent issuing MFMAs comes from the kernels' cycle stamps
-        # (tools/wino3w_trace.py: 0.86 for the wave-owned F(3x3,3x3) kernel at 0.73 here).
+        # roofline.frac.  The fraction of a wave's own CYCLES spent issuing MFMAs came from the kernels' cycle stamps
+        # (0.86 for the wave-owned F(3x3,3x3) kernel at 0.73 here).
         out["gui_active_GHz"] = round(tot["active_cycles"] / tot["active_us"] / 1e3, 3)
     print(json.dumps(out, indent=1))
 
