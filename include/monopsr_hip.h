@@ -735,6 +735,42 @@ int mpsr_depth_fill_multiscale(const float *depths, int n_frames, int h, int w, 
                                float *out, float *stages, void *workspace, size_t workspace_bytes,
                                mpsr_stream_t stream);
 
+/* ---- Training ground truth from depth maps (ABI 9): instance images and per-box crops ----
+ * Several frames that share one image size (h, w); depth maps (n_frames, h, w) float32 as read_depth_map returns them. */
+
+#define MPSR_INSTANCE_MAX_BOXES 255  /* per frame: value 255 of an instance image is the background */
+#define MPSR_INSTANCE_BOX_STRIDE 20  /* doubles per box of mpsr_instance_images' table */
+enum { MPSR_CENTROID_BOTTOM = 0, MPSR_CENTROID_MIDDLE = 1 };
+
+/* demos/instances/gen_instance_masks.py:86-153 (depth-map clouds) of every frame -> out (n_frames, h, w) uint8: 255 is
+ * background, k the k-th box of the frame.  boxes (n_boxes_total, 20) fp64, frame f owning rows box_offsets[f] ..
+ * box_offsets[f+1] (device and host copies; at most 255 per frame): the inflated box's u, up0, up1, v, vp0, vp3, w,
+ * wp0, wp4 of obj_utils.points_in_box_3d (:867-910), then the float32 2-D box y1, x1, y2, x2 and one unused double.
+ * p2 (n_frames, 3, 4) fp64.  Per pixel (u, v) of depth d: the point of depth_map_utils.get_depth_point_cloud with
+ * ratio = d / (float)P[0][0] in float32, x = (u - cu) * ratio + x_offset, y = (v - cv) * ratio in fp64, z = d, rounded
+ * to float32 (zero depths included); it belongs to a box when the three slab tests (x a0 + y a1) + z a2 in fp64 hold
+ * inclusively and its projection ((p0 x + p1 y) + p2 z) + p3, u' = r0 / r2, v' = r1 / r2 lies in [x1, x2] x [y1, y2].
+ * The LAST such box of the frame wins. */
+int mpsr_instance_images(const float *depth, int n_frames, int h, int w, const double *p2, const double *boxes,
+                         const long long *box_offsets, const long long *box_offsets_host, unsigned char *out,
+                         mpsr_stream_t stream);
+
+/* instance_utils.tf_instance_xyz_crop_from_depth_map (instance_utils.py:395-481) of n_boxes boxes across frames, with
+ * view_norm=True (xyz_local) and view_norm=False (xyz_global) in one pass.  inst (n_frames, h, w) uint8 instance images;
+ * p2 (n_frames, 3, 4) float32; per box: frame_index, instance_id (0..254), boxes_2d [y1, x1, y2, x2] float32, boxes_3d
+ * (7) float32, view_angs (the estimated viewing angle).  Device arrays, plus host copies of frame_index, instance_id and
+ * boxes_2d for the checks.  The box rounds half to even; rows r0:r2 and columns c0:c2 must be a non-empty part of the
+ * image.  The depth masked by inst == id is resized to roi x roi by TF 1.8's resize_nearest_neighbor(align_corners),
+ * back-projected at pixel centres of the unrounded box in float32; valid = |d| >= 0.1; both maps are multiplied by valid.
+ * The ROI must be square (roi_h == roi_w).  xyz_local / xyz_global (n_boxes, roi, roi, 3), valid (n_boxes, roi, roi, 1);
+ * every element is written.  DESIGN.md section 7.3. */
+int mpsr_instance_xyz_crops(const float *depth, const unsigned char *inst, const float *p2, int n_frames, int h, int w,
+                            const int *frame_index, const int *instance_id, const float *boxes_2d,
+                            const float *boxes_3d, const float *view_angs, const int *frame_index_host,
+                            const int *instance_id_host, const float *boxes_2d_host, int n_boxes, int roi_h,
+                            int roi_w, int centroid_type, int rotate_view, float *xyz_local, float *xyz_global,
+                            float *valid, mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

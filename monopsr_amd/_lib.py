@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MPSR_LIB_PATH: development knob for A/B-ing two builds of the library inside one GPU session
 LIB_PATH = os.environ.get("MPSR_LIB_PATH") or os.path.join(_HERE, "libmonopsr_hip.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _lib = None
 
@@ -195,6 +195,9 @@ SIGNATURES = {
                                         c_sz, c_f]),
     "mpsr_depth_fill_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "mpsr_depth_fill_multiscale": (c_i, [c_f, c_i, c_i, c_i, ctypes.POINTER(DepthFillOpts), c_f, c_f, c_f, c_sz, c_f]),
+    "mpsr_instance_images": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f, c_f, ctypes.c_void_p, c_f, c_f]),
+    "mpsr_instance_xyz_crops": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
 }
 
 

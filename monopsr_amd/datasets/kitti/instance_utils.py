@@ -1,7 +1,27 @@
 """Instance-map geometry, mirroring the TF functions of the reference's datasets/kitti/instance_utils.py that sit on
 the model's output path (same names and argument meaning).  Tensors are torch CUDA tensors; the compute is
 libmonopsr_hip.so (geometry.hip), wrapped in autograd Functions so the training loss can differentiate through it.
+
+The training ground truth comes from the same module (instance_maps.hip):
+
+    images = gen_instance_images(depth_maps, calibs, labels_per_frame)      # (F, H, W) uint8 CUDA tensor
+    save_instance_image(path, images[0].cpu().numpy())
+    local, glob, valid = instance_xyz_crops(depth_maps, images, p2s, frame_index, instance_id, boxes_2d, boxes_3d,
+                                            view_angs, roi=(48, 48))
+
+Command line (what demos/instances/gen_instance_masks.py does for a split directory with label_2/, calib/, image_2/
+and a directory of depth maps):
+
+    python -m monopsr_amd.datasets.kitti.instance_utils SPLIT_DIR DEPTH_DIR OUT_DIR [--frames 000001 ...] [--batch 8]
+
+writes OUT_DIR/<name>.png, 255 on the background and k on the k-th kept label.
 """
+import argparse
+import ctypes
+import os
+import sys
+
+import numpy as np
 import torch
 
 from monopsr_amd import _lib
@@ -162,3 +182,240 @@ def format_boxes(lwh, view_angs, alpha_bins, alpha_regs, centroids, boxes_2d, sc
                                             int(bool(post_process_cen_x)), float(max_depth), _lib.ptr(b3),
                                             _lib.ptr(b2), _lib.stream()))
     return b3, b2
+
+
+# ---------------------------------------------------------------------------------------------- training ground truth
+
+# gen_instance_masks.py: the classes that get an instance id, and each class's inflation of (x, y, z, l, w, h, ry)
+REQUIRED_CLASSES = ('Car', 'Pedestrian', 'Cyclist', 'Van', 'Truck', 'Person_sitting', 'Tram', 'Misc')
+INFLATIONS = {
+    'Car': np.array([1.0, 1.0, 1.0, 1.25, 1.25, 1.1, 1.0]),
+    'Van': np.array([1.0, 1.0, 1.0, 1.1, 1.1, 1.05, 1.0]),
+    'Truck': np.array([1.0, 1.0, 1.0, 1.1, 1.1, 1.05, 1.0]),
+    'Pedestrian': np.array([1.0, 1.0, 1.0, 1.0, 1.0, 1.05, 1.0]),
+    'Person_sitting': np.array([1.0, 1.0, 1.0, 1.0, 1.0, 1.05, 1.0]),
+    'Cyclist': np.array([1.0, 1.0, 1.0, 1.1, 1.1, 1.05, 1.0]),
+    'Tram': np.array([1.0, 1.0, 1.0, 1.0, 1.1, 1.05, 1.0]),
+    'Misc': np.array([1.0, 1.0, 1.0, 1.05, 1.05, 1.05, 1.0]),
+}
+_INFLATION_OFFSET = np.array([0.0, -0.05, 0.0, 0.0, 0.0, 0.0, 0.0])
+BOX_STRIDE = 20  # MPSR_INSTANCE_BOX_STRIDE
+MAX_BOXES = 255  # MPSR_INSTANCE_MAX_BOXES
+
+
+def get_prop_cen_z_offset(class_str):
+    """The proposal z centroid offset of a class."""
+    offsets = {'Car': 2.17799973487854, 'Pedestrian': 0.351921409368515, 'Cyclist': 0.8944902420043945}
+    if class_str not in offsets:
+        raise ValueError('Invalid class_str', class_str)
+    return offsets[class_str]
+
+
+def instance_box_table(obj_labels):
+    """The per-box constants of one frame for mpsr_instance_images, (n, 20) fp64: the labels of REQUIRED_CLASSES in
+    file order (instance id = row of this table), each box_3d (float32) * INFLATIONS[type] + [0, -0.05, 0, ...] in
+    fp64, then the u / v / w axes and bounds of points_in_box_3d, computed as the reference orders them, and the
+    label's float32 2-D box [y1, x1, y2, x2]."""
+    from monopsr_amd.datasets.kitti import obj_utils
+    kept = [o for o in obj_labels if o.type in REQUIRED_CLASSES]
+    table = np.zeros((len(kept), BOX_STRIDE), np.float64)
+    for k, o in enumerate(kept):
+        box_3d = obj_utils.object_label_to_box_3d(o) * INFLATIONS[o.type] + _INFLATION_OFFSET
+        u, up0, up1, v, vp0, vp3, w, wp0, wp4 = obj_utils.box_3d_slab_bounds(box_3d)
+        table[k, 0:15] = np.concatenate([u, [up0, up1], v, [vp0, vp3], w, [wp0, wp4]])
+        table[k, 15:19] = obj_utils.object_label_to_box_2d(o)
+    return table
+
+
+def _device(device):
+    return torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def _p2_of(calib):
+    return np.asarray(getattr(calib, 'p2', calib), np.float64).reshape(3, 4)
+
+
+def gen_instance_images(depth_maps, calibs, labels_per_frame, device=None):
+    """Instance images of F frames of one size: depth_maps (F, H, W) float32 (numpy or CUDA tensor, as read_depth_map
+    returns them), calibs F FrameCalibs or (3, 4) P2 matrices, labels_per_frame F lists of ObjectLabels ->
+    (F, H, W) uint8 CUDA tensor.  At most 255 labels of REQUIRED_CLASSES per frame."""
+    nf = len(labels_per_frame)
+    if len(calibs) != nf or len(depth_maps) != nf:
+        raise _lib.InvalidArgumentError('gen_instance_images: %d depth maps, %d calibrations, %d label lists'
+                                        % (len(depth_maps), len(calibs), nf))
+    tables = [instance_box_table(lbl) for lbl in labels_per_frame]
+    for f, t in enumerate(tables):
+        if len(t) > MAX_BOXES:
+            raise _lib.InvalidArgumentError('gen_instance_images: frame %d has %d boxes, at most %d (255 is the '
+                                            'background)' % (f, len(t), MAX_BOXES))
+    return instance_images_from_tables(depth_maps, [_p2_of(c) for c in calibs], tables, device)
+
+
+def instance_images_from_tables(depth_maps, p2s, tables, device=None):
+    """gen_instance_images on precomputed instance_box_table()s."""
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        depth = torch.as_tensor(depth_maps, device=dev)
+        if depth.dim() != 3 or depth.dtype != torch.float32:
+            raise _lib.InvalidArgumentError('depth_maps must be (F, H, W) float32, got %s %s'
+                                            % (tuple(depth.shape), depth.dtype))
+        nf, h, w = depth.shape
+        if len(p2s) != nf or len(tables) != nf:
+            raise _lib.InvalidArgumentError('instance_images: %d frames, %d P2, %d box tables'
+                                            % (nf, len(p2s), len(tables)))
+        depth = depth.contiguous()
+        offs = np.zeros(nf + 1, np.int64)
+        offs[1:] = np.cumsum([len(t) for t in tables])
+        tab = np.ascontiguousarray(np.concatenate(list(tables) + [np.zeros((0, BOX_STRIDE))]).astype(np.float64))
+        p2 = np.ascontiguousarray(np.stack([np.asarray(p, np.float64).reshape(3, 4) for p in p2s] or
+                                           [np.zeros((3, 4))]))
+        tab_d = torch.from_numpy(tab).to(dev) if len(tab) else None
+        offs_d, p2_d = torch.from_numpy(offs).to(dev), torch.from_numpy(p2).to(dev)
+        out = torch.empty((nf, h, w), dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().mpsr_instance_images(_lib.ptr(depth), nf, h, w, _lib.ptr(p2_d), _lib.ptr(tab_d),
+                                                   _lib.ptr(offs_d), offs.ctypes.data_as(ctypes.c_void_p),
+                                                   _lib.ptr(out), _lib.stream()))
+    return out
+
+
+def read_instance_image(instance_image_path):
+    """uint8 PNG -> (H, W) uint8 array."""
+    from PIL import Image
+    return np.asarray(Image.open(instance_image_path), np.uint8)
+
+
+def save_instance_image(save_path, instance_image):
+    from PIL import Image
+    img = np.asarray(instance_image)
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise ValueError('an instance image is (H, W) uint8, got %s %s' % (img.dtype, img.shape))
+    Image.fromarray(img).save(save_path, format='PNG')
+
+
+def get_instance_mask_list(instance_img, num_instances=None):
+    """(k, H, W) boolean masks, mask i = (instance_img == i) (the reference's get_instance_mask_list)."""
+    if num_instances is None:
+        valid_pixels = instance_img[instance_img != 255]
+        if len(valid_pixels) == 0:
+            return []
+        num_instances = np.max(valid_pixels) + 1
+    return np.asarray([(instance_img == i) for i in range(num_instances)])
+
+
+_CENTROID_TYPES = {'bottom': 0, 'middle': 1}
+
+
+def _crop_args(boxes_2d, frame_index, instance_id, n):
+    b2 = np.ascontiguousarray(np.asarray(boxes_2d, np.float32).reshape(-1, 4))
+    fi = np.ascontiguousarray(np.asarray(frame_index, np.int32).reshape(-1))
+    ii = np.ascontiguousarray(np.asarray(instance_id, np.int32).reshape(-1))
+    if not (len(b2) == len(fi) == len(ii) == n):
+        raise _lib.InvalidArgumentError('instance_xyz_crops: %d boxes_2d, %d frame indices, %d instance ids, %d boxes_3d'
+                                        % (len(b2), len(fi), len(ii), n))
+    return b2, fi, ii
+
+
+def instance_xyz_crops(depth_maps, instance_images, cam_ps, frame_index, instance_id, boxes_2d, boxes_3d, view_angs,
+                       roi_size=(48, 48), centroid_type='middle', rotate_view=True, device=None, out=None):
+    """The ground truth tf_instance_xyz_crop_from_depth_map builds for every box (monopsr_model.py:158-203) in one
+    launch: depth_maps (F, H, W) float32, instance_images (F, H, W) uint8, cam_ps (F, 3, 4); per box frame_index,
+    instance_id, boxes_2d [y1, x1, y2, x2] (B, 4), boxes_3d (B, 7), view_angs (B) the estimated (2-D) viewing angles
+    -> (xyz_local (B, r, r, 3), xyz_global (B, r, r, 3), valid (B, r, r, 1)) float32 CUDA tensors.  `out`, if given,
+    is such a triple to write into.  A box that rounds to an empty crop or one outside the image, a frame or id out of
+    range and a non-square roi_size raise InvalidArgumentError."""
+    dev = _device(device)
+    roi_h, roi_w = (int(roi_size), int(roi_size)) if np.ndim(roi_size) == 0 else (int(roi_size[0]), int(roi_size[1]))
+    if centroid_type not in _CENTROID_TYPES:
+        raise _lib.InvalidArgumentError('centroid_type must be bottom or middle, got %r' % (centroid_type,))
+    with torch.cuda.device(dev):
+        f32 = lambda a: torch.as_tensor(np.asarray(a, np.float32) if not torch.is_tensor(a) else a, device=dev) \
+            .float().contiguous()
+        depth = f32(depth_maps)
+        if not torch.is_tensor(instance_images):
+            instance_images = np.require(instance_images, requirements=['C', 'W'])  # (PNG arrays are read-only)
+        inst = torch.as_tensor(instance_images, device=dev).contiguous()
+        if depth.dim() != 3 or tuple(inst.shape) != tuple(depth.shape) or inst.dtype != torch.uint8:
+            raise _lib.InvalidArgumentError('depth_maps (F, H, W) float32 and instance_images (F, H, W) uint8, got %s '
+                                            'and %s %s' % (tuple(depth.shape), tuple(inst.shape), inst.dtype))
+        nf, h, w = depth.shape
+        p2 = f32(cam_ps).reshape(-1)
+        if p2.numel() != 12 * nf:
+            raise _lib.InvalidArgumentError('cam_ps must be (F, 3, 4)')
+        b3 = f32(boxes_3d).reshape(-1, 7)
+        n = b3.shape[0]
+        host = lambda a: a.cpu().numpy() if torch.is_tensor(a) else a
+        b2_h, fi_h, ii_h = _crop_args(host(boxes_2d), host(frame_index), host(instance_id), n)
+        va = f32(view_angs).reshape(-1)
+        if va.numel() != n:
+            raise _lib.InvalidArgumentError('view_angs must hold one angle per box')
+        b2, fi, ii = (torch.from_numpy(a).to(dev) for a in (b2_h, fi_h, ii_h))
+        if out is None:
+            out = (torch.empty((n, roi_h, roi_w, 3), dtype=torch.float32, device=dev),
+                   torch.empty((n, roi_h, roi_w, 3), dtype=torch.float32, device=dev),
+                   torch.empty((n, roi_h, roi_w, 1), dtype=torch.float32, device=dev))
+        loc, glob, valid = out
+        for t, c in ((loc, 3), (glob, 3), (valid, 1)):
+            if tuple(t.shape) != (n, roi_h, roi_w, c) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise _lib.InvalidArgumentError('out tensors must be contiguous float32 (B, r, r, 3/3/1)')
+        _lib.check(_lib.lib().mpsr_instance_xyz_crops(
+            _lib.ptr(depth), _lib.ptr(inst), _lib.ptr(p2), nf, h, w, _lib.ptr(fi), _lib.ptr(ii), _lib.ptr(b2),
+            _lib.ptr(b3), _lib.ptr(va), fi_h.ctypes.data_as(ctypes.c_void_p), ii_h.ctypes.data_as(ctypes.c_void_p),
+            b2_h.ctypes.data_as(ctypes.c_void_p), n, roi_h, roi_w, _CENTROID_TYPES[centroid_type], int(bool(rotate_view)),
+            _lib.ptr(loc), _lib.ptr(glob), _lib.ptr(valid), _lib.stream()))
+    return loc, glob, valid
+
+
+def save_instance_images(split_dir, depth_dir, out_dir, frames=None, batch=8, log=None):
+    """gen_instance_masks.py for split_dir (label_2/, calib/, optionally image_2/) and depth_dir/<name>.png into
+    out_dir/<name>.png.  Returns the names written, in the order written."""
+    from monopsr_amd.datasets.kitti import depth_map_utils, obj_utils
+    if batch < 1:
+        raise ValueError('batch must be >= 1, got %d' % batch)
+    if frames is None:
+        if not os.path.isdir(depth_dir):
+            raise FileNotFoundError('no such depth directory: %s' % depth_dir)
+        frames = sorted(f[:-4] for f in os.listdir(depth_dir) if f.endswith('.png'))
+    shapes = {}
+    for n in frames:
+        shapes[n] = depth_map_utils.image_shape(os.path.join(depth_dir, n + '.png'))
+        img = os.path.join(split_dir, 'image_2', n + '.png')
+        if os.path.exists(img) and depth_map_utils.image_shape(img) != shapes[n]:
+            raise ValueError('frame %s: image_2 is %s but its depth map is %s'
+                             % (n, depth_map_utils.image_shape(img), shapes[n]))
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for _, names in depth_map_utils._groups(frames, shapes, batch):
+        depths = np.stack([depth_map_utils.read_depth_map(os.path.join(depth_dir, n + '.png')) for n in names])
+        calibs = [depth_map_utils.read_calibration(os.path.join(split_dir, 'calib', n + '.txt')) for n in names]
+        labels = [obj_utils.read_labels(os.path.join(split_dir, 'label_2'), n) for n in names]
+        images = gen_instance_images(depths, calibs, labels).cpu().numpy()
+        for n, im in zip(names, images):
+            save_instance_image(os.path.join(out_dir, n + '.png'), im)
+            written.append(n)
+        if log:
+            log('%d / %d frames' % (len(written), len(frames)))
+    return written
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(prog='python -m monopsr_amd.datasets.kitti.instance_utils',
+                                description='KITTI instance images (255 = background, k = k-th label) on the GPU.')
+    p.add_argument('split_dir', help='KITTI split directory with label_2/ and calib/ (image_2/ is checked if present)')
+    p.add_argument('depth_dir', help='directory of <name>.png depth maps (depth_map_utils writes them)')
+    p.add_argument('out_dir', help='directory for <name>.png')
+    p.add_argument('--frames', nargs='+', help='frame names (default: every depth map in depth_dir)')
+    p.add_argument('--batch', type=int, default=8, help='frames per launch (default 8)')
+    a = p.parse_args(argv)
+    if a.batch < 1:
+        p.error('--batch must be >= 1')
+    for d in (a.split_dir, a.depth_dir):
+        if not os.path.isdir(d):
+            p.error('no such directory: %s' % d)
+    names = save_instance_images(a.split_dir, a.depth_dir, a.out_dir, a.frames, a.batch,
+                                 log=lambda m: print(m, file=sys.stderr))
+    print('wrote %d instance images to %s' % (len(names), a.out_dir))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
