@@ -771,6 +771,61 @@ int mpsr_instance_xyz_crops(const float *depth, const unsigned char *inst, const
                             int roi_w, int centroid_type, int rotate_view, float *xyz_local, float *xyz_global,
                             float *valid, mpsr_stream_t stream);
 
+/* ---- Training samples assembled on the device (ABI 10): oversampling draw, 2-D box jitter, crops without host copies ----
+ * Random numbers are counter-based, Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9,
+ * 0xBB67AE85): key = (seed & 0xffffffff, seed >> 32), counter = (draw j, slot s, the frame's index in the split file,
+ * (epoch << 4) | stream), stream 0 for the oversampling draw and 1 for the jitter; 0 <= epoch < 2^28.  A uniform is
+ * ((w0 >> 5) * 2^26 + (w1 >> 6)) / 2^53 of two words; a pair of normals is Box-Muller in fp64 of (1 - u0, u1), u0 from
+ * words 0, 1 and u1 from words 2, 3: r = sqrt(-2 ln(1 - u0)), z0 = r cos(2 pi u1), z1 = r sin(2 pi u1).
+ * DESIGN.md section 7.4. */
+
+enum { MPSR_JITTER_NONE = 0, MPSR_JITTER_OVERSAMPLE = 1, MPSR_JITTER_ALL = 2 };
+
+/* The slots of a batch.  Per slot: slot_frame (a row of the per-frame tables, 0 .. n_frames-1) and slot_s (its slot in
+ * the frame's sample).  Per-frame tables: num_objs (>= 1), label_offset (the frame's first row of label_boxes),
+ * split_index (the RNG coordinate), frame_local (passed through: the frame's index among the frames of its image size),
+ * image_hw (n_frames, 2), p00_p02 (n_frames, 2) = P2[0][0], P2[0][2].  label_boxes (n_labels, 4) fp64 x1 y1 x2 y2.
+ * kitti_dataset.py:301-308: slot s < num_objs is label s; a later slot is label floor(u * num_objs), u the uniform of
+ * draw 0 of stream 0.  jitter_flag: 0 (MPSR_JITTER_NONE), s >= num_objs (MPSR_JITTER_OVERSAMPLE) or 1 (MPSR_JITTER_ALL).
+ * Outputs per slot: label_row = label_offset + index, oversample_index, jitter_flag, boxes_xyxy (n, 4) the label's box,
+ * slot_hw (n, 2), slot_p (n, 2), slot_split_index, slot_frame_local.
+ * THE CALLER MUST GUARANTEE 0 <= slot_frame < n_frames and slot_s >= 0: both arrays are on the device, so this entry
+ * point cannot check them and has no status word.  A value out of range is not reported; it is read as frame 0 /
+ * slot 0 (so that no lane reads outside the tables) and the slot's outputs are those of that frame, i.e. wrong. */
+int mpsr_sample_slots(const int *slot_frame, const int *slot_s, int n, const int *num_objs,
+                      const long long *label_offset, const int *split_index, const int *frame_local,
+                      const int *image_hw, const double *p00_p02, const double *label_boxes, int n_frames,
+                      unsigned long long seed, int epoch, int jitter_mode, long long *label_row, int *oversample_index,
+                      int *jitter_flag, double *boxes_xyxy, int *slot_hw, double *slot_p, int *slot_split_index,
+                      int *slot_frame_local, mpsr_stream_t stream);
+
+/* kitti_aug.jitter_obj_boxes_2d (kitti_aug.py:173-254) of n slots, one lane per slot, in fp64 and in the reference's
+ * order: a slot whose flag is 0 or whose box is under 10 px wide or high keeps its box (0 trials); trial t draws
+ * new_centroid_x ~ N(cx, half_w / 3), new_centroid_y ~ N(cy, half_h / 3) (draw 2t of stream 1: z0, z1) and new_half_w ~
+ * N(half_w, half_w / 6), new_half_h ~ N(half_h, half_h / 6) (draw 2t + 1), clips to [0, width - 1] x [0, height - 1],
+ * and the first trial with evaluation.two_d_iou(new, original) >= iou_threshold_min (in (0, 1]) wins.  The reference
+ * loops until then; here a slot that used max_trials trials keeps its box and reports max_trials + 1.
+ * Inputs per slot: boxes_xyxy (n, 4) fp64, jitter_flag, image_hw (n, 2), p00_p02 (n, 2), frame_index, slot.
+ * Outputs: out_xyxy (n, 4) fp64; out_boxes_2d (n, 4) float32 [y1, x1, y2, x2]; out_boxes_2d_norm = (double)box /
+ * (double)dim rounded to float32 (kitti_dataset.py:450); out_view_angs = get_viewing_angle_box_2d of the float32 box;
+ * out_trials.  With write_unjittered == 0 the three float32 outputs of a slot that kept its box are left as the caller
+ * filled them (the dataset's rows computed on the host). */
+int mpsr_jitter_boxes_2d(const double *boxes_xyxy, const int *jitter_flag, const int *image_hw, const double *p00_p02,
+                         const int *frame_index, const int *slot, int n, unsigned long long seed, int epoch,
+                         double iou_threshold_min, int max_trials, int write_unjittered, double *out_xyxy,
+                         float *out_boxes_2d, float *out_boxes_2d_norm, float *out_view_angs, int *out_trials,
+                         mpsr_stream_t stream);
+
+/* mpsr_instance_xyz_crops (same kernel, same results) without host copies: the per-box checks are made on the device.
+ * A box that fails them is written as zeros and reported in status (2 int32 on the device, which the caller zeroes and
+ * reads when it wants to know): status[0] |= MPSR_CROP_BAD_*, status[1] += 1 per such box. */
+enum { MPSR_CROP_BAD_FRAME = 1, MPSR_CROP_BAD_ID = 2, MPSR_CROP_BAD_NOT_FINITE = 4, MPSR_CROP_BAD_BOX = 8 };
+int mpsr_instance_xyz_crops_status(const float *depth, const unsigned char *inst, const float *p2, int n_frames, int h,
+                                   int w, const int *frame_index, const int *instance_id, const float *boxes_2d,
+                                   const float *boxes_3d, const float *view_angs, int n_boxes, int roi_h, int roi_w,
+                                   int centroid_type, int rotate_view, float *xyz_local, float *xyz_global,
+                                   float *valid, int *status, mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

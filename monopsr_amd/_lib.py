@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MPSR_LIB_PATH: development knob for A/B-ing two builds of the library inside one GPU session
 LIB_PATH = os.environ.get("MPSR_LIB_PATH") or os.path.join(_HERE, "libmonopsr_hip.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _lib = None
 
@@ -198,6 +198,12 @@ SIGNATURES = {
     "mpsr_instance_images": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f, c_f, ctypes.c_void_p, c_f, c_f]),
     "mpsr_instance_xyz_crops": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_f]),
+    "mpsr_sample_slots": (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_uint64, c_i, c_i, c_f,
+                                c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "mpsr_jitter_boxes_2d": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_uint64, c_i, ctypes.c_double, c_i, c_i,
+                                   c_f, c_f, c_f, c_f, c_f, c_f]),
+    "mpsr_instance_xyz_crops_status": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i,
+                                             c_i, c_f, c_f, c_f, c_f, c_f]),
 }
 
 

@@ -78,12 +78,16 @@ __device__ __forceinline__ float linspace_at(float start, float stop, int num, i
     return start + step * (float)i;
 }
 
+// kDeviceChecks: the argument checks mpsr_instance_xyz_crops makes on host copies are made here, per box, on the device
+// arrays; a box that fails them is written as zeros, reads no image, and is reported in status[0] (the OR of the
+// MPSR_CROP_BAD_* bits) and status[1] (the number of such boxes).
+template <bool kDeviceChecks>
 __global__ void __launch_bounds__(kThreads) instance_crop_kernel(
     const float *__restrict__ depth, const unsigned char *__restrict__ inst, const float *__restrict__ p2, int h,
     int w, const int *__restrict__ frame_index, const int *__restrict__ instance_id,
     const float *__restrict__ boxes_2d, const float *__restrict__ boxes_3d, const float *__restrict__ view_angs,
     int n_boxes, int roi, int middle, int rotate_view, float *__restrict__ xyz_local, float *__restrict__ xyz_global,
-    float *__restrict__ valid)
+    float *__restrict__ valid, int n_frames, int *__restrict__ status)
 {
     const long long per_box = (long long)roi * roi;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -93,6 +97,27 @@ __global__ void __launch_bounds__(kThreads) instance_crop_kernel(
     const int i = rem / roi, j = rem - i * roi;
     const int f = frame_index[b];
     const float y1 = boxes_2d[4 * b], x1 = boxes_2d[4 * b + 1], y2 = boxes_2d[4 * b + 2], x2 = boxes_2d[4 * b + 3];
+    if (kDeviceChecks) {
+        int bad = 0;
+        if (f < 0 || f >= n_frames) bad |= MPSR_CROP_BAD_FRAME;
+        if (instance_id[b] < 0 || instance_id[b] > 254) bad |= MPSR_CROP_BAD_ID;
+        if (!(isfinite(y1) && isfinite(x1) && isfinite(y2) && isfinite(x2))) {
+            bad |= MPSR_CROP_BAD_NOT_FINITE;
+        } else {
+            const float fr0 = rintf(y1), fc0 = rintf(x1), fr2 = rintf(y2), fc2 = rintf(x2);
+            if (!(fr0 >= 0.0f && fc0 >= 0.0f && fr2 <= (float)h && fc2 <= (float)w && fr0 < fr2 && fc0 < fc2))
+                bad |= MPSR_CROP_BAD_BOX;
+        }
+        if (bad) {
+            if (rem == 0) {
+                atomicOr(status, bad);
+                atomicAdd(status + 1, 1);
+            }
+            for (int k = 0; k < 3; ++k) xyz_local[3 * idx + k] = xyz_global[3 * idx + k] = 0.0f;
+            valid[idx] = 0.0f;
+            return;
+        }
+    }
     const int r0 = (int)rintf(y1), c0 = (int)rintf(x1), r2 = (int)rintf(y2), c2 = (int)rintf(x2);
     const int sy = r0 + nn_source(i, r2 - r0, roi), sx = c0 + nn_source(j, c2 - c0, roi);
     const long long src = (long long)f * h * w + (long long)sy * w + sx;
@@ -196,9 +221,37 @@ extern "C" int mpsr_instance_xyz_crops(const float *depth, const unsigned char *
     }
     hipStream_t s = mpsr::as_stream(stream);
     const long long total = (long long)n_boxes * roi_h * roi_h;
-    instance_crop_kernel<<<(unsigned)((total + kThreads - 1) / kThreads), kThreads, 0, s>>>(
+    instance_crop_kernel<false><<<(unsigned)((total + kThreads - 1) / kThreads), kThreads, 0, s>>>(
         depth, inst, p2, h, w, frame_index, instance_id, boxes_2d, boxes_3d, view_angs, n_boxes, roi_h,
-        centroid_type == MPSR_CENTROID_MIDDLE, rotate_view != 0, xyz_local, xyz_global, valid);
+        centroid_type == MPSR_CENTROID_MIDDLE, rotate_view != 0, xyz_local, xyz_global, valid, n_frames, nullptr);
+    MPSR_CHECK_LAUNCH("instance_crop_kernel");
+    return MPSR_OK;
+}
+
+extern "C" int mpsr_instance_xyz_crops_status(const float *depth, const unsigned char *inst, const float *p2,
+                                              int n_frames, int h, int w, const int *frame_index,
+                                              const int *instance_id, const float *boxes_2d, const float *boxes_3d,
+                                              const float *view_angs, int n_boxes, int roi_h, int roi_w,
+                                              int centroid_type, int rotate_view, float *xyz_local, float *xyz_global,
+                                              float *valid, int *status, mpsr_stream_t stream)
+{
+    MPSR_REQUIRE(roi_h == roi_w, "instance_crops: the ROI must be square (the reference's graph only builds for "
+                                 "square ROIs), got %d x %d", roi_h, roi_w);
+    MPSR_REQUIRE(roi_h >= 1 && roi_h <= 1024, "instance_crops: roi %d (1..1024)", roi_h);
+    MPSR_REQUIRE(n_boxes >= 0 && n_frames >= 0, "instance_crops: n_boxes %d, n_frames %d", n_boxes, n_frames);
+    MPSR_REQUIRE(h > 0 && w > 0 && (long long)h * w <= (1LL << 30), "instance_crops: bad image size %d x %d", h, w);
+    MPSR_REQUIRE(centroid_type == MPSR_CENTROID_BOTTOM || centroid_type == MPSR_CENTROID_MIDDLE,
+                 "instance_crops: unknown centroid_type %d", centroid_type);
+    if (n_boxes == 0) return MPSR_OK;
+    MPSR_REQUIRE((long long)n_boxes * roi_h * roi_h <= INT_MAX, "instance_crops: %d boxes of %d x %d is too many",
+                 n_boxes, roi_h, roi_h);
+    MPSR_REQUIRE(depth && inst && p2 && frame_index && instance_id && boxes_2d && boxes_3d && view_angs && xyz_local &&
+                     xyz_global && valid && status,
+                 "instance_crops: a pointer is null");
+    const long long total = (long long)n_boxes * roi_h * roi_h;
+    instance_crop_kernel<true><<<(unsigned)((total + kThreads - 1) / kThreads), kThreads, 0, mpsr::as_stream(stream)>>>(
+        depth, inst, p2, h, w, frame_index, instance_id, boxes_2d, boxes_3d, view_angs, n_boxes, roi_h,
+        centroid_type == MPSR_CENTROID_MIDDLE, rotate_view != 0, xyz_local, xyz_global, valid, n_frames, status);
     MPSR_CHECK_LAUNCH("instance_crop_kernel");
     return MPSR_OK;
 }
