@@ -9,12 +9,6 @@
 
 #include "common.h"
 
-namespace mpsr {
-// thin_conv.hip
-bool thin_wgrad_applies(int B, int H, int W, int C, int N, int KH, int KW, int dilation);
-int thin_wgrad(const float *x, const float *dy, int B, int H, int W, int C, float *dw, float *db, hipStream_t s);
-}  // namespace mpsr
-
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
@@ -865,14 +859,6 @@ extern "C" int mpsr_act_bias_grad(const float *dy, const float *y, float *dx, fl
     }
     return MPSR_OK;
 }
-
-namespace mpsr {
-bool pointwise_masked_applies(long long M, int K, int N);
-int conv1x1_pointwise_masked(const float *x, long long M, int K, const float *w, const float *bias, const float *residual,
-                             const unsigned *mask, float *y, int N, hipStream_t s);
-int conv1x1_pointwise_emit(const float *x, long long M, int K, const float *w, const float *bias, const float *residual,
-                           int relu, float *y, unsigned *bits, int N, hipStream_t s);
-}  // namespace mpsr
 
 extern "C" long long mpsr_relu_bitmask_words(long long M, int N) { return M > 0 && N > 0 ? (M + 31) / 32 * N : 0; }
 

@@ -1072,49 +1072,6 @@ int launch_sk(ConvParams &p, int B, bool use_classes, int mode, bool counters_cl
 
 namespace mpsr {
 
-int conv3x3_narrow(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu, float *y,
-                   int N, hipStream_t s, int in_c8);  // image_ops.hip
-// winograd.hip
-size_t winograd_scratch_floats(int C, int N);
-bool winograd_applies(int H, int W, int C, int N);
-bool winograd_applies_dilated(int H, int W, int C, int N, int dilation);
-int conv3x3_winograd(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu, float *y,
-                     int N, float *ws, size_t ws_floats, hipStream_t s, int dilation);
-// winograd4.hip
-size_t winograd4_scratch_floats(int C, int N);
-bool winograd4_applies(int H, int W, int C, int N);
-int conv3x3_winograd4(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu,
-                      float *y, int N, float *ws, size_t ws_floats, hipStream_t s, int in_c8, int out_c8, float *part,
-                      size_t part_floats);
-size_t winograd4_split_floats(int B, int H, int W, int N);
-extern std::atomic<int> g_wino4_split;
-// winograd3.hip
-size_t winograd3_scratch_floats(int C, int N);
-bool winograd3_applies(int H, int W, int C, int dilation);
-double winograd3_executed_flops(int B, int H, int C, int N, int dilation);
-int winograd3_form(int B, int H, int W, int C, int N, int dilation);
-int conv3x3_winograd3(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu,
-                      float *y, int N, int dilation, float *ws, size_t ws_floats, hipStream_t s,
-                      const float *mask = nullptr);
-
-// pointwise.hip
-bool pointwise_applies(long long M, int K, int N);
-int pointwise_override();
-int conv1x1_pointwise(const float *x, long long M, int K, const float *w, const float *bias, const float *residual,
-                      int relu, float *y, int N, hipStream_t s);
-
-// thin_conv.hip
-bool thin_input_conv_applies(int B, int H, int W, int C, int N, int KH, int KW, int dilation);
-int thin_input_conv(const float *x, int B, int H, int W, const float *w, const float *bias, int relu, float *y, int N,
-                    hipStream_t s);
-
-bool fc_rows_applies(long long M, int K, int N);
-bool fc_rows_split_applies(long long M, int K, int N, const float *bias, const float *y, const float *ws, size_t ws_floats);
-int fc_rows_split(const float *x, long long M, int K, const float *w, const float *bias, int relu, float *y, int N,
-                  float *ws, hipStream_t s);
-int fc_rows(const float *x, long long M, int K, const float *w, const float *bias, const float *residual, int relu,
-            float *y, int N, hipStream_t s);
-
 // True when conv2d() sends a fully-connected layer (H = W = 1: a row is an instance) with few rows to fc_rows_kernel
 // (pointwise.hip): the heads' layers, whose 64 x 64 tiles would cover a quarter of the CUs.  The rule looks at nothing
 // but "FC with at most 2048 rows": that kernel sums K in another order than the implicit GEMM, and an instance's

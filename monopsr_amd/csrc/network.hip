@@ -6,40 +6,7 @@
 #include <vector>
 
 #include "common.h"
-#include "wino3_filter.h"
 
-namespace mpsr {
-int conv2d(const float *x, int B, int H, int W, int C, const float *w, const float *bias, const float *residual,
-           float *y, int N, int KH, int KW, int dilation, int relu, int split_k, float *ws, size_t ws_floats,
-           hipStream_t stream);
-size_t conv_scratch_floats(long long M, int N);
-bool conv2d_takes_winograd4(int B, int H, int W, int C, int N, const float *ws, size_t ws_floats);
-int conv3x3_winograd4(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu,
-                      float *y, int N, float *ws, size_t ws_floats, hipStream_t s, int in_c8, int out_c8, float *part,
-                      size_t part_floats);
-size_t winograd4_split_floats(int B, int H, int W, int N);
-extern std::atomic<int> g_wino4_split;
-int winograd3_filter_form(int B, int H, int W, int C, int N, int dilation);  // winograd3.hip
-bool conv2d_takes_winograd3(int B, int H, int W, int C, int N, int KH, int KW, int dilation, int split_k, const float *ws,
-                            size_t ws_floats);
-bool conv2d_takes_pointwise(long long M, int C, int N, int KH, int KW, int split_k);
-int conv3x3_narrow(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu, float *y,
-                   int N, hipStream_t s, int in_c8);
-bool conv3x3_narrow_takes_mfma(const float *x, int B, int H, int W, int C, int N, const float *w);
-int conv2d_winograd_choice(int B, int H, int W, int C, int N, int KH, int KW, int dilation, bool residual, int split_k,
-                           const float *ws, size_t ws_floats);
-int resize_bilinear_c8(const float *in, int B, int H, int W, int C, int OH, int OW, int align_corners, float *out,
-                       hipStream_t s);
-// upconv.hip: 3x3 convolution of a bilinearly upsampled map as a low-resolution tap GEMM + gather
-bool upconv_applies(int B, int h, int w, int C, int OH, int OW, int N, int align_corners);
-size_t upconv_z_floats(long long Msrc, int N);
-size_t upconv_weight_floats(int C, int N);
-int conv3x3_upsampled(const float *x, int B, int h, int w, int C, int OH, int OW, int align_corners, const float *g,
-                      const float *bias, int relu, float *y, int N, int out_c8, float *z, size_t z_floats, float *ws,
-                      size_t ws_floats, hipStream_t s);
-}
-
-#include <atomic>
 // 1 (default): the map decoder's internal tensors are channel-blocked whenever all four of its 3x3 layers go to the
 // F(4x4,3x3) kernel; 0: NHWC throughout (tests compare the two bit for bit)
 static std::atomic<int> g_decoder_c8{1};

@@ -630,10 +630,6 @@ int fc_rows(const float *x, long long M, int K, const float *w, const float *bia
     return MPSR_OK;
 }
 
-// winograd3z.hip
-int winograd_finish_slices(const float *part, const float *bias, float *y, size_t y_floats, int nslices, int N, int relu,
-                           hipStream_t s);
-
 std::atomic<int> g_fc_split_rows{96};  // mpsr_debug_set_fc_split_rows: the K-split few-row kernel up to this many rows (0: never)
 
 // K slabs of the split form for a long-K layer with few rows: enough workgroups to stream the weights from every CU

@@ -24,13 +24,6 @@
 #include <atomic>
 
 #include "common.h"
-#include "wino3_filter.h"
-
-namespace mpsr {
-bool pointwise_applies(long long M, int K, int N);
-int conv1x1_pointwise(const float *x, long long M, int K, const float *w, const float *bias, const float *residual,
-                      int relu, float *y, int N, hipStream_t s);
-}  // namespace mpsr
 
 namespace {
 
@@ -680,13 +673,6 @@ size_t upconv_bwd_scratch_floats(int B, int h, int w, int C, int N)
     const size_t M = (size_t)B * h * w;
     return align_up(M * 9 * N, 64) + 2 * align_up((size_t)9 * N * C, 64);
 }
-
-}  // namespace mpsr
-
-extern "C" int mpsr_conv2d_wgrad_f32(const float *x, const float *dy, int B, int H, int W, int C, int N, int KH, int KW,
-                                     int dilation, float *dw, float *db, mpsr_stream_t stream);
-
-namespace mpsr {
 
 // Backward of conv3x3_upsampled (bias-free part): dy (B,OH,OW,N) NHWC -> dw (N, 9 C) += weight gradient, dx (B,h,w,C) =
 // data gradient (or nullptr).  dz = gather^T(dy) at the SOURCE resolution; dW' = dz^T x (a 1x1 weight gradient with 9 N

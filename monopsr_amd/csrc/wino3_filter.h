@@ -81,36 +81,4 @@ __device__ __forceinline__ void wino3z_filter_one(const float *__restrict__ w, i
         for (int s = 0; s < 4; ++s) dst[(size_t)(r * 4 + s) * N * f3z::KC] = (float)o[s];
     }
 }
-
-// A filter-transform job handed from a network-level entry point (network.hip) to the next pointwise launch on this
-// thread, and the note that it was done, for conv3x3_winograd3 to find.
-struct FilterTailJob {
-    const float *w = nullptr;
-    float *u = nullptr;
-    int N = 0, C = 0;
-    int form = 0;  // 0: F(3x3,3x3), 25 positions (wino3_filter_one); 1: the sixteen-product form (wino3z_filter_one)
-};
-extern thread_local FilterTailJob g_filter_tail_job;    // pending: consumed by conv1x1_pointwise
-extern thread_local FilterTailJob g_filter_tail_done;   // done by the last pointwise launch: consumed by conv3x3_winograd3
-
-// Where the transformed filters of the layer about to run live when the caller keeps them across calls
-// (mpsr_net_opts.filter_cache): set by the network entry points (network.hip) right before the layer, consumed by
-// conv3x3_winograd3 / conv3x3_winograd4, which then use `u` instead of their scratch and skip the transform if `ready`.
-struct FilterCacheSlot {
-    const float *w = nullptr;
-    float *u = nullptr;
-    size_t floats = 0;
-    bool ready = false;
-    int *tag = nullptr;  // caller's note of what the slice holds (mpsr_net_opts.filter_cache_tags), or nullptr
-    // true when the slice already holds form `kind` of this layer's filters; notes `kind` for the next call either way
-    // (the consumer is about to write it if not)
-    bool holds(int kind)
-    {
-        const bool ok = ready && (!tag || *tag == kind);
-        if (tag) *tag = kind;
-        return ok;
-    }
-};
-enum { FILTER_FORM_WINO4 = 1, FILTER_FORM_WINO3 = 2, FILTER_FORM_UPCONV = 3, FILTER_FORM_WINO3Z = 4, FILTER_FORM_WINO2 = 5 };
-extern thread_local FilterCacheSlot g_filter_cache_slot;
 }  // namespace mpsr

@@ -26,7 +26,6 @@
 #include <type_traits>
 
 #include "common.h"
-#include "wino3_filter.h"
 
 namespace {
 
@@ -615,7 +614,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 }  // namespace
 
-namespace mpsr { extern std::atomic<int> g_wino_waves; }
 extern "C" void mpsr_debug_set_wino_waves(int waves) { mpsr::g_wino_waves = waves; }
 
 namespace mpsr {
@@ -631,11 +629,6 @@ bool winograd_applies_dilated(int H, int W, int C, int N, int dilation)
 }
 
 std::atomic<int> g_wino_waves{8};  // 4: the one-wave-per-SIMD kernel, 8: the two-waves-per-SIMD variant
-
-// winograd3z.hip: K slices of a small launch and the launch that adds them
-int winograd_slices(long long blocks, int want_blocks, int cblocks, int min_steps, size_t part_floats, size_t y_floats);
-int winograd_finish_slices(const float *part, const float *bias, float *y, size_t y_floats, int nslices, int N, int relu,
-                           hipStream_t s);
 
 int conv3x3_winograd(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu, float *y,
                      int N, float *ws, size_t ws_floats, hipStream_t s, int dilation)

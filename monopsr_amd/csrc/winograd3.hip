@@ -405,16 +405,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 namespace mpsr {
 
-// winograd3w.hip: the same layer with one wave owning all 25 positions of its tile block
-bool winograd3w_applies(int B, int H, int W, int C, int N, int dilation);
-long long winograd3w_workgroups(int B, int N, int dilation);
-int launch_winograd3w(const float *x, int B, int H, int W, int C, const float *u, const float *bias, int relu, float *y,
-                      int N, int dilation, hipStream_t s, const float *mask);
-// winograd3z.hip: the same layer in SIXTEEN products per tile (a one-tile sub-grid reads nothing outside itself: rank 4 per
-// dimension instead of F(3,3)'s 5), one wave owning all 16 positions of its tile block
-int launch_winograd3z(const float *x, int B, int H, int W, int C, const float *u, const float *bias, int relu, float *y,
-                      int N, int dilation, hipStream_t s, const float *mask, float *part, size_t part_floats);
-int launch_winograd3z_filter(const float *w, int N, int C, float *u, hipStream_t s);
 // mpsr_debug_set_wino3_form: -1 = by size, 0 = F(3x3,3x3) with positions shared by eight waves (this file), 1 = F(3x3,3x3)
 // with one wave per tile block (winograd3w.hip), 2 = the sixteen-product form (winograd3z.hip)
 std::atomic<int> g_wino3_form{-1};

@@ -18,11 +18,9 @@
 // k half h) reads the 8 bytes at 8 h = its k of both MFMAs of the step; double buffered, one barrier per step.  The patches
 // of the step after next are requested in the first slots of a step into the OTHER of two register sets: a full step of
 // lead (the vector half of the register file is nearly empty here).
-#include <type_traits>
-#include <utility>
-
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
+#include "acc_named.h"
 #include "common.h"
 #include "wino3_transforms.h"
 
@@ -32,6 +30,8 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 using mpsr::FastDiv;
 using mpsr::fdiv;
+using mpsr::IC;
+using mpsr::static_for;
 using mpsr::w3t::a4z;
 using mpsr::w3t::bt4z;
 
@@ -55,53 +55,7 @@ struct W3gParams {
     unsigned xbytes, dybytes;
 };
 
-template <int V>
-using ICG = std::integral_constant<int, V>;
-template <int... Is, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F &&f)
-{
-    (f(ICG<Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
-
-// (literal accumulator-register names, no wait states inside the statements: see winograd3w.hip; the same audit in
-// tests/test_build_audit.py covers this kernel)
-#define W3G_MFMA_A(q, a, b)                                                                                 \
-    asm volatile("v_mfma_f32_32x32x2_f32 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(a), "v"(b), "i"(16 * (q)), \
-                 "i"(16 * (q) + 15))
-#define W3G_ZERO16(b)                                                                                                     \
-    asm volatile("v_accvgpr_write_b32 a%c0, 0\n\tv_accvgpr_write_b32 a%c1, 0\n\tv_accvgpr_write_b32 a%c2, 0\n\t"          \
-                 "v_accvgpr_write_b32 a%c3, 0\n\tv_accvgpr_write_b32 a%c4, 0\n\tv_accvgpr_write_b32 a%c5, 0\n\t"          \
-                 "v_accvgpr_write_b32 a%c6, 0\n\tv_accvgpr_write_b32 a%c7, 0\n\tv_accvgpr_write_b32 a%c8, 0\n\t"          \
-                 "v_accvgpr_write_b32 a%c9, 0\n\tv_accvgpr_write_b32 a%c10, 0\n\tv_accvgpr_write_b32 a%c11, 0\n\t"        \
-                 "v_accvgpr_write_b32 a%c12, 0\n\tv_accvgpr_write_b32 a%c13, 0\n\tv_accvgpr_write_b32 a%c14, 0\n\t"       \
-                 "v_accvgpr_write_b32 a%c15, 0" ::"i"((b)), "i"((b) + 1), "i"((b) + 2), "i"((b) + 3), "i"((b) + 4),       \
-                 "i"((b) + 5), "i"((b) + 6), "i"((b) + 7), "i"((b) + 8), "i"((b) + 9), "i"((b) + 10), "i"((b) + 11),      \
-                 "i"((b) + 12), "i"((b) + 13), "i"((b) + 14), "i"((b) + 15))
-#define W3G_READ_ACC(dst, idx) asm volatile("v_accvgpr_read_b32 %0, a%c1" : "=v"(dst) : "i"(idx))
-#define W3G_CLAIM_ACC()                                                                                                   \
-    asm volatile("" :: : \
-    "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15", \
-    "a16", "a17", "a18", "a19", "a20", "a21", "a22", "a23", "a24", "a25", "a26", "a27", "a28", "a29", "a30", "a31", \
-    "a32", "a33", "a34", "a35", "a36", "a37", "a38", "a39", "a40", "a41", "a42", "a43", "a44", "a45", "a46", "a47", \
-    "a48", "a49", "a50", "a51", "a52", "a53", "a54", "a55", "a56", "a57", "a58", "a59", "a60", "a61", "a62", "a63", \
-    "a64", "a65", "a66", "a67", "a68", "a69", "a70", "a71", "a72", "a73", "a74", "a75", "a76", "a77", "a78", "a79", \
-    "a80", "a81", "a82", "a83", "a84", "a85", "a86", "a87", "a88", "a89", "a90", "a91", "a92", "a93", "a94", "a95", \
-    "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108", "a109", "a110", "a111", \
-    "a112", "a113", "a114", "a115", "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127", \
-    "a128", "a129", "a130", "a131", "a132", "a133", "a134", "a135", "a136", "a137", "a138", "a139", "a140", "a141", "a142", "a143", \
-    "a144", "a145", "a146", "a147", "a148", "a149", "a150", "a151", "a152", "a153", "a154", "a155", "a156", "a157", "a158", "a159", \
-    "a160", "a161", "a162", "a163", "a164", "a165", "a166", "a167", "a168", "a169", "a170", "a171", "a172", "a173", "a174", "a175", \
-    "a176", "a177", "a178", "a179", "a180", "a181", "a182", "a183", "a184", "a185", "a186", "a187", "a188", "a189", "a190", "a191", \
-    "a192", "a193", "a194", "a195", "a196", "a197", "a198", "a199", "a200", "a201", "a202", "a203", "a204", "a205", "a206", "a207", \
-    "a208", "a209", "a210", "a211", "a212", "a213", "a214", "a215", "a216", "a217", "a218", "a219", "a220", "a221", "a222", "a223", \
-    "a224", "a225", "a226", "a227", "a228", "a229", "a230", "a231", "a232", "a233", "a234", "a235", "a236", "a237", "a238", "a239", \
-    "a240", "a241", "a242", "a243", "a244", "a245", "a246", "a247", "a248", "a249", "a250", "a251", "a252", "a253", "a254", "a255")
-
+// (the accumulators carry literal register names: acc_named.h)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void wino3_wgrad_kernel(const W3gParams p)
 {
     using namespace w3g;
@@ -193,8 +147,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
         });
         if constexpr (m == 0) locate(s + 2);
-        if constexpr (m < 9) request(stc, ICG<m>{}, ICG<0>{});
-        if constexpr (m >= 9 && m < 18) request(stc, ICG<m - 9>{}, ICG<1>{});
+        if constexpr (m < 9) request(stc, IC<m>{}, IC<0>{});
+        if constexpr (m >= 9 && m < 18) request(stc, IC<m - 9>{}, IC<1>{});
     };
 
     // ---- fragments: lane (row = lane & 31 of the wave's block, k half h = lane >> 5) reads tiles (h, 2 + h) as 8 bytes
@@ -209,18 +163,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
     auto mfma = [&](auto qc, float av, float bv) __attribute__((always_inline)) {
         constexpr int q = decltype(qc)::value;
-        W3G_MFMA_A(q, av, bv);
+        ACC_MFMA_A(q, av, bv);
     };
 
     // ---- prologue: patches of steps 0 and 1 requested, accumulators cleared, step 0 transformed into stage 0
     locate(0);
-    static_for<9>([&](auto Lc) __attribute__((always_inline)) { request(ICG<0>{}, Lc, ICG<0>{}); });
-    static_for<9>([&](auto Lc) __attribute__((always_inline)) { request(ICG<0>{}, Lc, ICG<1>{}); });
+    static_for<9>([&](auto Lc) __attribute__((always_inline)) { request(IC<0>{}, Lc, IC<0>{}); });
+    static_for<9>([&](auto Lc) __attribute__((always_inline)) { request(IC<0>{}, Lc, IC<1>{}); });
     locate(1);
-    static_for<9>([&](auto Lc) __attribute__((always_inline)) { request(ICG<1>{}, Lc, ICG<0>{}); });
-    static_for<9>([&](auto Lc) __attribute__((always_inline)) { request(ICG<1>{}, Lc, ICG<1>{}); });
-    W3G_CLAIM_ACC();
-    static_for<16>([&](auto qc) __attribute__((always_inline)) { W3G_ZERO16(16 * decltype(qc)::value); });
+    static_for<9>([&](auto Lc) __attribute__((always_inline)) { request(IC<1>{}, Lc, IC<0>{}); });
+    static_for<9>([&](auto Lc) __attribute__((always_inline)) { request(IC<1>{}, Lc, IC<1>{}); });
+    ACC_CLAIM_ACC();
+    static_for<16>([&](auto qc) __attribute__((always_inline)) { ACC_ZERO16(16 * decltype(qc)::value); });
     {   // (the transform half of the duties of a step "-1" with stage 1: register set 0 into stage 0)
         static_for<2>([&](auto opc) __attribute__((always_inline)) {
             constexpr int op = decltype(opc)::value;
@@ -246,8 +200,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         });
     }
     __syncthreads();
-    load_f(0, ICG<0>{});
-    load_f(0, ICG<1>{});
+    load_f(0, IC<0>{});
+    load_f(0, IC<1>{});
 
     // ---- K loop: slot m = MFMA j = m % 2 of position q = m / 2
     auto kstep = [&](int s, auto stc) __attribute__((always_inline)) {
@@ -256,19 +210,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             constexpr int m = decltype(mc)::value, q = m / 2, j = m % 2;
             const float av = j == 0 ? fa[cF(q)].x : fa[cF(q)].y;
             const float bv = j == 0 ? fb[cF(q)].x : fb[cF(q)].y;
-            mfma(ICG<q>{}, av, bv);
+            mfma(IC<q>{}, av, bv);
             if constexpr (j == 0) {
                 if constexpr (m == 2 * (NP - 2)) __syncthreads();
-                if constexpr (q + 2 < NP) load_f(st, ICG<(q + 2) % NP>{});
-                else load_f(st ^ 1, ICG<(q + 2) % NP>{});
+                if constexpr (q + 2 < NP) load_f(st, IC<(q + 2) % NP>{});
+                else load_f(st ^ 1, IC<(q + 2) % NP>{});
             }
             duty(s, stc, mc);
             __builtin_amdgcn_sched_barrier(0);
         });
     };
     for (int s = 0; s < p.steps; s += 2) {
-        kstep(s, ICG<0>{});
-        kstep(s + 1, ICG<1>{});
+        kstep(s, IC<0>{});
+        kstep(s + 1, IC<1>{});
     }
     int lane2 = lane;
     asm volatile("s_nop 15\n\ts_nop 7" : "+v"(lane2));
@@ -300,7 +254,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int j = 0; j < 4; ++j) {  // over the rows u of column j: positions 4 u + j
             float col[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) W3G_READ_ACC(col[r], 16 * (4 * r + j) + e);
+            for (int r = 0; r < 4; ++r) ACC_READ_ACC(col[r], 16 * (4 * r + j) + e);
             gt(col[0], col[1], col[2], col[3], t[0][j], t[1][j], t[2][j]);
         }
         const int n = n0 + 32 * mi + (e & 3) + 8 * (e >> 2) + 4 * (lane2 >> 5);

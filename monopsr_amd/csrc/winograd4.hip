@@ -35,7 +35,6 @@
 #include <type_traits>
 
 #include "common.h"
-#include "wino3_filter.h"
 
 namespace {
 
@@ -828,7 +827,6 @@ extern "C" int mpsr_debug_fetch_calibration(const float *p, size_t floats, int m
 }
 
 
-namespace mpsr { extern std::atomic<int> g_wino4_split; }
 extern "C" void mpsr_debug_set_wino4_split(int on) { mpsr::g_wino4_split = on; }
 
 namespace mpsr {

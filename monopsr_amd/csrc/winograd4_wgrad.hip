@@ -321,12 +321,6 @@ int conv3x3_wgrad_winograd4(const float *x, const float *dy, int B, int H, int W
 
 }  // namespace mpsr
 
-namespace mpsr {  // winograd3_wgrad.hip: the atrous layers whose pixel sub-grids are single 3x3 tiles (block3's conv2)
-bool winograd3_wgrad_applies(int B, int H, int W, int C, int N, int KH, int KW, int dilation);
-int conv3x3_wgrad_winograd3(const float *x, const float *dy, int B, int H, int W, int C, int N, int dilation, float *dw,
-                            float *db, hipStream_t s);
-}  // namespace mpsr
-
 static int g_wgrad_winograd = 1;  // mpsr_debug_set_wgrad_winograd
 extern "C" void mpsr_debug_set_wgrad_winograd(int on) { g_wgrad_winograd = on; }
 

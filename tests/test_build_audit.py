@@ -1,8 +1,8 @@
-"""Audit of the compiled gfx950 code of csrc/winograd3w.hip, csrc/winograd3z.hip and csrc/winograd3_wgrad.hip (no GPU
-needed: hipcc cross-compiles).
+"""Audit of the compiled gfx950 code of csrc/winograd3w.hip, csrc/winograd3z.hip (two forms of the one kernel body in
+csrc/wino3_onewave.h) and csrc/winograd3_wgrad.hip (no GPU needed: hipcc cross-compiles).
 
-Those kernels keep 256 of their 400 accumulator registers under literal names (a0..a255) inside inline-asm statements, and
-issue their MFMAs from inline asm.  hipcc neither knows that those registers are live between the statements nor pads
+Those kernels keep up to 256 accumulator registers under literal names (a0..a255) inside inline-asm statements (the macros
+of csrc/acc_named.h), and issue their MFMAs from inline asm.  hipcc neither knows that those registers are live between the statements nor pads
 hazards around them, so three properties of the generated code are part of the kernel's correctness and are checked
 here on every build of the test suite:
   1. the compiler never touches the accumulator half of the register file itself (it would only do so to spill vector

@@ -1,7 +1,7 @@
 """The kernels of the atrous 3x3 layers whose pixel sub-grids are single tiles, side by side (mpsr_debug_set_wino3_form):
 0 = F(3x3,3x3), a tile's 25 positions shared by eight waves (csrc/winograd3.hip), 1 = F(3x3,3x3), one wave owns all 25
-(csrc/winograd3w.hip: identical bits to 0), 2 = the SIXTEEN-product form of a zero-padded tile, one wave owns all 16
-(csrc/winograd3z.hip).
+(csrc/winograd3w.hip, kernel body in csrc/wino3_onewave.h: identical bits to 0), 2 = the SIXTEEN-product form of a zero-padded tile, one wave owns all 16
+(csrc/winograd3z.hip, the same body).
 
     python tools/wino3_forms.py [--batches 32,64,128,256] [--rounds 5] [--reps 20] [--relu-input]
 
