@@ -826,6 +826,45 @@ int mpsr_instance_xyz_crops_status(const float *depth, const unsigned char *inst
                                    int centroid_type, int rotate_view, float *xyz_local, float *xyz_global,
                                    float *valid, int *status, mpsr_stream_t stream);
 
+/* ---- Evaluation on 2-D detections (ABI 11): MSCNN merging and the evaluator's detection rows ----
+ * DESIGN.md section 7.5. */
+
+enum { MPSR_MERGE_SCORE_DISTANCE = 0, MPSR_MERGE_SCORE_MAX = 1, MPSR_MERGE_SCORE_MIN = 2 };
+
+/* obj_utils.merge_kitti_and_mscnn_obj_labels (obj_utils.py:1037-1089) of n_frames frames in one launch, one wave per
+ * frame.  Ragged inputs: frame f owns the labels label_off[f] .. label_off[f+1]-1 of label_boxes (n_labels, 4) float32
+ * [y1, x1, y2, x2] and label_z (n_labels) float32 (the labels' t[2]), and the detections det_off[f] .. det_off[f+1]-1
+ * of det_boxes (n_dets, 4) float32 [y1, x1, y2, x2] and det_scores (n_dets) fp64, in file order.  Both offset tables
+ * hold n_frames + 1 entries on the device.
+ * Per detection, in order: two_d_iou (datasets/kitti/evaluation.py:6-44) against the frame's ORIGINAL label boxes --
+ * products, union and quotient in float32, the quotient widened to fp64 and rounded to 3 decimals, rint(x * 1000) /
+ * 1000 --, the arg-max with the lowest index on ties, and, when iou >= min_iou, the label's box, score and match index
+ * are overwritten.  Then every label whose score is exactly 0 gets, in float32,
+ * min(max(1 - z / 45, 0.1), 1) (MPSR_MERGE_SCORE_DISTANCE), 1 (_MAX), or stays 0 (_MIN).
+ * Outputs per label: out_boxes (n_labels, 4) float32, out_scores (n_labels) fp64, out_match (n_labels) int32: the
+ * detection's index within its frame, or -1.  A frame without labels merges nothing (the reference's np.argmax raises).
+ * THE CALLER MUST GUARANTEE that both offset tables are non-decreasing and end at n_labels / n_dets; a frame whose
+ * offsets leave the tables is not reported: its labels are left unwritten (label offsets) or it is merged with no
+ * detection (detection offsets). */
+int mpsr_merge_detections(const float *label_boxes, const float *label_z, const long long *label_off,
+                          long long n_labels, const float *det_boxes, const double *det_scores,
+                          const long long *det_off, long long n_dets, int n_frames, double min_iou, int score_type,
+                          float *out_boxes, double *out_scores, int *out_match, mpsr_stream_t stream);
+
+/* evaluator_utils.kitti_label_array of n prediction rows in one launch, one lane per row.  box_3d (n, 9) float32
+ * [x y z l w h ry score class] and box_2d (n, 7) float32 [y1 x1 y2 x2 alpha score class] as mpsr_format_boxes leaves
+ * them.  Every value is widened to fp64 and rounded as np.round(v, 3) rounds it: rint(v * 1000) / 1000.
+ * rows (n, MPSR_KITTI_FIELDS) fp64 in the evaluator's column order (x1 y1 x2 y2 alpha h w l x y z ry score 0);
+ * cls (n) = (int)class; keep (n) = score >= score_threshold, in fp64 on the unrounded score.
+ * project != 0: the 2-D box is evaluator_utils.project_boxes_3d of the 3-D box with the frame's p2 (n_frames, 12) fp64
+ * and image_wh (n_frames, 2) int32 [width, height], frame (n) picking the frame: the clipped extent of the eight
+ * projected corners, and keep also needs the box at least partly inside the image and, before clipping, no wider or
+ * taller than 0.8 of it.  A row whose frame is outside [0, n_frames) is not kept.  frame, p2 and image_wh may be null
+ * when project == 0. */
+int mpsr_kitti_detection_rows(const float *box_3d, const float *box_2d, const int *frame, const double *p2,
+                              const int *image_wh, int n, int n_frames, double score_threshold, int project,
+                              double *rows, int *cls, int *keep, mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MPSR_LIB_PATH: development knob for A/B-ing two builds of the library inside one GPU session
 LIB_PATH = os.environ.get("MPSR_LIB_PATH") or os.path.join(_HERE, "libmonopsr_hip.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lib = None
 
@@ -204,6 +204,9 @@ SIGNATURES = {
                                    c_f, c_f, c_f, c_f, c_f, c_f]),
     "mpsr_instance_xyz_crops_status": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i,
                                              c_i, c_f, c_f, c_f, c_f, c_f]),
+    "mpsr_merge_detections": (c_i, [c_f, c_f, c_f, ctypes.c_longlong, c_f, c_f, c_f, ctypes.c_longlong, c_i,
+                                    ctypes.c_double, c_i, c_f, c_f, c_f, c_f]),
+    "mpsr_kitti_detection_rows": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_double, c_i, c_f, c_f, c_f, c_f]),
 }
 
 

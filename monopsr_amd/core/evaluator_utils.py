@@ -63,6 +63,38 @@ def kitti_label_array(box_3d, box_2d, score_threshold, image_boxes=None, keep=No
     return b3[:, _CLS].astype(np.int64), numbers
 
 
+def detection_rows(box_3d, box_2d, score_threshold, frame=None, p2=None, image_wh=None, project_3d_box=False):
+    """kitti_label_array (and project_boxes_3d when project_3d_box) of device-resident predictions in one
+    mpsr_kitti_detection_rows launch, without a copy to the host.  box_3d (n,9), box_2d (n,7) float32 CUDA tensors as
+    format_boxes leaves them; frame (n,) int32, p2 (F,12) float64 and image_wh (F,2) int32 [width, height] are needed
+    for the projection only.  -> (rows (n,14) float64 in kitti_eval's column order, rounded to 3 decimals; class index
+    (n,) int32; keep (n,) int32) on the device, for ALL n rows: the caller compacts with keep."""
+    import torch
+    from monopsr_amd import _lib
+    n, dev = int(box_3d.shape[0]), box_3d.device
+    if tuple(box_3d.shape) != (n, 9) or tuple(box_2d.shape) != (n, 7) or box_3d.dtype != torch.float32 \
+            or box_2d.dtype != torch.float32:
+        raise ValueError('detection_rows: box_3d (n,9) and box_2d (n,7) float32, got %s %s and %s %s' % (
+            tuple(box_3d.shape), box_3d.dtype, tuple(box_2d.shape), box_2d.dtype))
+    n_frames = 0
+    if project_3d_box:
+        if frame is None or p2 is None or image_wh is None:
+            raise ValueError('project_3d_box=True needs frame, p2 and image_wh')
+        n_frames = int(p2.shape[0])
+        if frame.dtype != torch.int32 or p2.dtype != torch.float64 or image_wh.dtype != torch.int32 \
+                or frame.numel() != n or p2.numel() != 12 * n_frames or image_wh.numel() != 2 * n_frames:
+            raise ValueError('detection_rows: frame (n,) int32, p2 (F,12) float64, image_wh (F,2) int32')
+    with torch.cuda.device(dev):
+        rows = torch.empty((n, 14), dtype=torch.float64, device=dev)
+        ints = torch.empty((2, n), dtype=torch.int32, device=dev)
+        p = _lib.ptr
+        _lib.check(_lib.lib().mpsr_kitti_detection_rows(
+            p(box_3d), p(box_2d), p(frame) if project_3d_box else None, p(p2) if project_3d_box else None,
+            p(image_wh) if project_3d_box else None, n, n_frames, float(score_threshold), int(bool(project_3d_box)),
+            p(rows), p(ints[0]), p(ints[1]), _lib.stream()))
+    return rows, ints[0], ints[1]
+
+
 def kitti_label_rows(box_3d, box_2d, classes, score_threshold, image_boxes=None, keep=None):
     """Detections of one frame -> list of KITTI label lines (no line ends).
     box_3d (n,9), box_2d (n,7) as format_predictions returns them; `image_boxes` (n,4) [x1,y1,x2,y2] replaces the

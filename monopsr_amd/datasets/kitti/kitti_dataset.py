@@ -21,7 +21,7 @@ import torch
 
 from monopsr_amd import _lib
 from monopsr_amd.core import orientation_encoder
-from monopsr_amd.datasets.kitti import depth_map_utils, instance_utils, kitti_aug, obj_utils
+from monopsr_amd.datasets.kitti import depth_map_utils, instance_utils, kitti_aug, mscnn_utils, obj_utils
 
 # model 000's obj_filter_config (configs/monopsr_model_000.yaml of the reference)
 DEFAULT_OBJ_FILTER = dict(difficulty_str='hard', box_2d_height=None, truncation=0.3, occlusion=None,
@@ -116,6 +116,8 @@ BOX_JITTER_TYPES = {None: 0, 'oversample': 1, 'all': 2}  # MPSR_JITTER_*
 # the keys of a sample that are rows of the per-label tables, gathered by label row
 _ROW_KEYS = ('boxes_2d', 'boxes_2d_norm', 'est_view_angs', 'class_indices', 'mean_lwh', 'prop_cen_z_offset', 'boxes_3d',
              'gt_alpha_bins', 'gt_alpha_regs', 'gt_alpha_valid_bins', 'gt_view_angs')
+# the rows of a 'test' sample (kitti_dataset.py:396-471 of the reference): no label, so nothing 3-D
+_TEST_ROW_KEYS = ('boxes_2d', 'boxes_2d_norm', 'est_view_angs', 'class_indices', 'mean_lwh', 'prop_cen_z_offset')
 
 
 def _cfg(config, key, default=None):
@@ -178,7 +180,7 @@ class _Group:
 
 
 class KittiDataset:
-    """The reference's KittiDataset for 'train' and 'val' with the split resident on the GPU.
+    """The reference's KittiDataset with the split resident on the GPU.
 
     dataset_config holds the reference's keys (configs/monopsr_model_000.yaml): dataset_dir, data_split,
     data_split_dir, num_boxes, classes, oversample, num_alpha_bins, alpha_bin_overlap, obj_filter_config,
@@ -188,10 +190,17 @@ class KittiDataset:
 
     Frames that keep no label are left out of sample_list and counted in num_skipped (the reference returns None for
     them and its model draws again).  A frame's sample depends on (seed, epoch, the frame's index in the split file)
-    only.  Unsupported recipes raise ValueError naming the option; see DESIGN.md section 7.4 for what is kept."""
+    only.  Unsupported recipes raise ValueError naming the option; see DESIGN.md section 7.4 for what is kept.
+
+    The two evaluation recipes need mscnn_label_dir (the argument, or the config key of that name): the directory of
+    MSCNN detections in KITTI label format, one file per frame of the split.  'val' with use_mscnn_detections merges
+    them into the labels at load (one mpsr_merge_detections launch); 'test' builds its samples
+    from the detection files alone, always oversampled, and reads no label, depth map or instance image.  Samples of
+    both carry label_scores."""
 
     def __init__(self, dataset_config, train_val_test, device=None, seed=0, max_resident_bytes=None, depth_dir=None,
-                 instance_dir=None, map_roi_size=(48, 48), centroid_type=None, rotate_view=True, log=None):
+                 instance_dir=None, map_roi_size=(48, 48), centroid_type=None, rotate_view=True, log=None,
+                 mscnn_label_dir=None):
         self.dataset_config = dataset_config
         self.train_val_test = train_val_test
         self.seed = int(seed)
@@ -213,7 +222,17 @@ class KittiDataset:
         self.depth_version = _cfg(dataset_config, 'depth_version', 'multiscale')
         self.instance_version = _cfg(dataset_config, 'instance_version', 'depth_2_multiscale')
         self.iou_threshold_min = 0.7  # kitti_dataset.py:327-349
+        self.mscnn_label_dir = mscnn_label_dir or _cfg(dataset_config, 'mscnn_label_dir')
+        self.has_kitti_labels = bool(_cfg(dataset_config, 'has_kitti_labels', train_val_test != 'test'))
         self._check_options()
+        self.is_test = self.train_val_test == 'test'
+        self.merges_mscnn = self.train_val_test == 'val' and self.use_mscnn_detections
+        self.mscnn_merge_min_iou = mscnn_utils.MIN_IOU.get(self.classes[0], 0.5)
+        if self.is_test:
+            self.oversample = True  # kitti_dataset.py:412-416
+        self._row_keys = _TEST_ROW_KEYS if self.is_test else _ROW_KEYS
+        if self.is_test or self.merges_mscnn:
+            self._row_keys = self._row_keys + ('label_scores',)
 
         flt = _cfg(dataset_config, 'obj_filter_config')
         self.obj_filter = {k: _cfg(flt, k, v) for k, v in DEFAULT_OBJ_FILTER.items()}
@@ -249,15 +268,15 @@ class KittiDataset:
     # ---- options
 
     def _check_options(self):
-        if self.train_val_test == 'test':
-            raise ValueError("train_val_test = 'test' (MSCNN detections without labels) is not built")
-        if self.train_val_test not in ('train', 'val'):
+        if self.train_val_test == 'test' and not self.mscnn_label_dir:
+            raise ValueError("train_val_test = 'test' builds its samples from MSCNN detections: give mscnn_label_dir")
+        if self.train_val_test not in ('train', 'val', 'test'):
             raise ValueError('Invalid run mode', self.train_val_test)
         if self.num_classes > 1:
             raise NotImplementedError('Number of classes must be 1')
-        if self.train_val_test == 'val' and self.use_mscnn_detections:
-            raise ValueError("use_mscnn_detections = True in 'val' mode (merging MSCNN boxes into the labels) is not "
-                             "built; set it to False to validate on KITTI's boxes")
+        if self.train_val_test == 'val' and self.use_mscnn_detections and not self.mscnn_label_dir:
+            raise ValueError("use_mscnn_detections = True in 'val' mode merges MSCNN boxes into the labels: give "
+                             "mscnn_label_dir, or set it to False to validate on KITTI's boxes")
         self.jitter_mode = 0
         if self.train_val_test == 'train':
             if self.use_image_aug:
@@ -287,6 +306,20 @@ class KittiDataset:
     def _label_rows(self, obj_labels, cam_p, image_shape):
         """The per-label rows of one frame, with the functions and in the order of build_training_sample."""
         boxes_2d = obj_utils.boxes_2d_from_obj_labels(obj_labels)
+        label_boxes = np.asarray([[float(o.x1), float(o.y1), float(o.x2), float(o.y2)] for o in obj_labels],
+                                 np.float64)
+        label_scores = np.asarray([o.score for o in obj_labels], np.float32)
+        if self.is_test:
+            class_strs = [o.type for o in obj_labels]
+            return dict(
+                boxes_2d=boxes_2d, boxes_2d_norm=boxes_2d / np.tile(image_shape, 2),
+                est_view_angs=np.asarray([obj_utils.get_viewing_angle_box_2d(b, cam_p) for b in boxes_2d], np.float32),
+                class_indices=np.asarray([obj_utils.class_str_to_index(c, self.classes) for c in class_strs],
+                                         np.int32)[:, None],
+                mean_lwh=np.asarray([obj_utils.get_mean_lwh_and_std_dev(c)[0] for c in class_strs], np.float32),
+                prop_cen_z_offset=np.asarray([instance_utils.get_prop_cen_z_offset(c) for c in class_strs],
+                                             np.float32),
+                label_boxes=label_boxes, label_scores=label_scores)
         boxes_3d = obj_utils.boxes_3d_from_obj_labels(obj_labels)
         alpha_bins, alpha_regs, valid_bins = zip(*[orientation_encoder.np_orientation_to_angle_bin(
             o.alpha, self.num_alpha_bins, self.alpha_bin_overlap) for o in obj_labels])
@@ -301,21 +334,52 @@ class KittiDataset:
             boxes_3d=boxes_3d, gt_alpha_bins=np.asarray(alpha_bins), gt_alpha_regs=np.stack(alpha_regs),
             gt_alpha_valid_bins=np.stack(valid_bins),
             gt_view_angs=np.asarray([obj_utils.get_viewing_angle_box_3d(b, cam_p) for b in boxes_3d], np.float32),
-            label_boxes=np.asarray([[float(o.x1), float(o.y1), float(o.x2), float(o.y2)] for o in obj_labels],
-                                   np.float64))
+            label_boxes=label_boxes, label_scores=label_scores)
+
+    def _split_labels(self):
+        """Per frame of the split: (the labels its samples are built from, their rows in the label file)."""
+        names = self.split_sample_names
+        if self.is_test:
+            # just the classes (kitti_dataset.py:56-65, 404-410)
+            flt = obj_utils.ObjectFilter(self.classes, 'all')
+            out = []
+            for name in names:
+                labels = obj_utils.read_labels(self.mscnn_label_dir, name)
+                kept, mask = obj_utils.apply_obj_filter(labels, flt)
+                out.append((kept, np.arange(len(labels))[mask]))
+            return out
+        if not self.merges_mscnn:
+            return [training_labels(self.data_split_dir, name, self.classes, self.obj_filter) for name in names]
+        flt = obj_utils.ObjectFilter(self.classes, **self.obj_filter)
+        kitti = [obj_utils.read_labels(self.kitti_label_dir, name) for name in names]
+        mscnn = [obj_utils.read_labels(self.mscnn_label_dir, name) for name in names]
+        ka, ma = [mscnn_utils.label_arrays(k) for k in kitti], [mscnn_utils.label_arrays(m) for m in mscnn]
+        boxes, scores, _ = mscnn_utils.merge_frames([a[0] for a in ka], [a[1] for a in ka], [a[0] for a in ma],
+                                                    [a[2] for a in ma], self.mscnn_merge_min_iou, 'distance',
+                                                    device=self.device)
+        out = []
+        for f in range(len(names)):
+            merged = mscnn_utils.merged_obj_labels(kitti[f], boxes[f], scores[f])
+            kept, mask = obj_utils.apply_obj_filter(merged, flt)
+            # the reference's second check: the original labels must keep something under the same filter
+            if len(kept) and not len(obj_utils.apply_obj_filter(kitti[f], flt)[0]):
+                kept, mask = kept[:0], np.zeros(len(merged), bool)
+            out.append((kept, np.arange(len(merged))[mask]))
+        return out
 
     def _load(self, log):
         # pass 1, host only: labels, calibration and image sizes of every frame; what the split needs on the card
         frames, rows, groups = [], [], {}
+        split_labels = self._split_labels()
         for split_index, name in enumerate(self.split_sample_names):
-            obj_labels, instance_ids = training_labels(self.data_split_dir, name, self.classes, self.obj_filter)
+            obj_labels, instance_ids = split_labels[split_index]
             if len(obj_labels) < 1:
                 self.num_skipped += 1
                 continue
             if self.oversample and len(obj_labels) > self.num_boxes:
                 raise ValueError('%s keeps %d labels, more than num_boxes = %d' % (name, len(obj_labels),
                                                                                     self.num_boxes))
-            if instance_ids.max() > 254:
+            if not self.is_test and instance_ids.max() > 254:
                 raise ValueError('%s: label row %d has no instance id (0..254)' % (name, instance_ids.max()))
             shape = depth_map_utils.image_shape(os.path.join(self.rgb_image_dir, name + '.png'))
             cam_p = depth_map_utils.read_calibration(os.path.join(self.calib_dir, name + '.txt')).p2
@@ -328,7 +392,8 @@ class KittiDataset:
             rows.append(row)
         if not frames:
             raise ValueError('no frame of split %r keeps a label' % self.data_split)
-        need = sum(len(g.frames) * g.shape[0] * g.shape[1] * (3 + 4 + 1) for g in groups.values())
+        pixel_bytes = 3 if self.is_test else 3 + 4 + 1
+        need = sum(len(g.frames) * g.shape[0] * g.shape[1] * pixel_bytes for g in groups.values())
         if self.max_resident_bytes is not None and need > self.max_resident_bytes:
             raise MemoryError('KittiDataset: the images of split %r need %d bytes on the device, max_resident_bytes is '
                               '%d' % (self.data_split, need, self.max_resident_bytes))
@@ -342,15 +407,21 @@ class KittiDataset:
                 g.index = gi
                 h, w = g.shape
                 nf = len(g.frames)
-                self._reserve(nf * h * w * 8 + nf * 48)
+                self._reserve(nf * h * w * pixel_bytes + nf * 48)
                 g.rgb = torch.empty((nf, h, w, 3), dtype=torch.uint8, device=self.device)
-                g.depth = torch.empty((nf, h, w), dtype=torch.float32, device=self.device)
-                g.inst = torch.empty((nf, h, w), dtype=torch.uint8, device=self.device)
+                if not self.is_test:
+                    g.depth = torch.empty((nf, h, w), dtype=torch.float32, device=self.device)
+                    g.inst = torch.empty((nf, h, w), dtype=torch.uint8, device=self.device)
                 g.p2 = torch.as_tensor(np.stack([frames[r]['cam_p'] for r in g.frames]).astype(np.float32)) \
                     .to(self.device)
                 for k, r in enumerate(g.frames):
                     name = frames[r]['name']
                     rgb = _read_rgb(os.path.join(self.rgb_image_dir, name + '.png'))
+                    if self.is_test:
+                        if rgb.shape[0:2] != g.shape:
+                            raise ValueError('%s: image %s, expected %s' % (name, rgb.shape[0:2], g.shape))
+                        g.rgb[k].copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
+                        continue
                     depth = depth_map_utils.read_depth_map(os.path.join(self.depth_dir, name + '.png'))
                     inst = instance_utils.read_instance_image(os.path.join(self.instance_dir, name + '.png'))
                     if rgb.shape[0:2] != g.shape or depth.shape != g.shape or inst.shape != g.shape:
@@ -366,7 +437,7 @@ class KittiDataset:
             cat = lambda k: np.concatenate([row[k] for row in rows])
             f32, i32 = torch.float32, torch.int32
             self._rows = {k: self._upload(cat(k), torch.int64 if k == 'gt_alpha_bins' else
-                                          i32 if k == 'class_indices' else f32) for k in _ROW_KEYS}
+                                          i32 if k == 'class_indices' else f32) for k in self._row_keys}
             self._instance_id = self._upload(cat('instance_id'), i32)
             self._label_boxes = self._upload(cat('label_boxes'), torch.float64)
             self._num_objs_host = np.asarray([f['num_objs'] for f in frames], np.int32)
@@ -401,6 +472,18 @@ class KittiDataset:
     def sample_names(self):
         """The names of the frames that keep a label, in split-file order; sample_list indexes it."""
         return [f['name'] for f in self._frames]
+
+    def frame_info(self, sample_name):
+        """(cam_p (3,4), (image_w, image_h)) of a kept frame, as evaluator_utils.export_kitti_labels asks for them."""
+        for f in self._frames:
+            if f['name'] == sample_name:
+                return f['cam_p'], (f['shape'][1], f['shape'][0])
+        raise KeyError(sample_name)
+
+    def frame_calibrations(self):
+        """(P2 (F,12) float64, image sizes (F,2) int32 [width, height]) of the kept frames, in sample_names' order."""
+        return (np.ascontiguousarray(np.stack([f['cam_p'] for f in self._frames]).astype(np.float64).reshape(-1, 12)),
+                np.asarray([[f['shape'][1], f['shape'][0]] for f in self._frames], np.int32))
 
     def get_sample_names(self):
         return [self._frames[r]['name'] for r in self.sample_list]
@@ -489,9 +572,10 @@ class KittiDataset:
                     _lib.ptr(rows['boxes_2d_norm']), _lib.ptr(rows['est_view_angs']), _lib.ptr(trials), stream))
             else:
                 trials = torch.zeros(n, dtype=i32, device=dev)
-            local = torch.empty((n, roi_h, roi_w, 3), dtype=f32, device=dev)
-            glob = torch.empty((n, roi_h, roi_w, 3), dtype=f32, device=dev)
-            valid = torch.empty((n, roi_h, roi_w, 1), dtype=f32, device=dev)
+            if not self.is_test:
+                local = torch.empty((n, roi_h, roi_w, 3), dtype=f32, device=dev)
+                glob = torch.empty((n, roi_h, roi_w, 3), dtype=f32, device=dev)
+                valid = torch.empty((n, roi_h, roi_w, 1), dtype=f32, device=dev)
             rgb = [None] * nb
             cam_p = self._cam_p.index_select(0, batch_frames)
             groups = self._group_host[sorted_frames]
@@ -502,12 +586,14 @@ class KittiDataset:
                     k1 += 1
                 g = self._groups[groups[k0]]
                 a, b = int(starts[k0]), int(starts[k1])
-                _lib.check(L.mpsr_instance_xyz_crops_status(
-                    _lib.ptr(g.depth), _lib.ptr(g.inst), _lib.ptr(g.p2), len(g.frames), g.shape[0], g.shape[1],
-                    _lib.ptr(slot_local[a:b]), _lib.ptr(instance_id[a:b]), _lib.ptr(rows['boxes_2d'][a:b]),
-                    _lib.ptr(rows['boxes_3d'][a:b]), _lib.ptr(rows['est_view_angs'][a:b]), b - a, roi_h, roi_w,
-                    instance_utils._CENTROID_TYPES[self.centroid_type], int(self.rotate_view), _lib.ptr(local[a:b]),
-                    _lib.ptr(glob[a:b]), _lib.ptr(valid[a:b]), _lib.ptr(self._status), stream))
+                if not self.is_test:
+                    _lib.check(L.mpsr_instance_xyz_crops_status(
+                        _lib.ptr(g.depth), _lib.ptr(g.inst), _lib.ptr(g.p2), len(g.frames), g.shape[0], g.shape[1],
+                        _lib.ptr(slot_local[a:b]), _lib.ptr(instance_id[a:b]), _lib.ptr(rows['boxes_2d'][a:b]),
+                        _lib.ptr(rows['boxes_3d'][a:b]), _lib.ptr(rows['est_view_angs'][a:b]), b - a, roi_h, roi_w,
+                        instance_utils._CENTROID_TYPES[self.centroid_type], int(self.rotate_view),
+                        _lib.ptr(local[a:b]), _lib.ptr(glob[a:b]), _lib.ptr(valid[a:b]), _lib.ptr(self._status),
+                        stream))
                 images = g.rgb.index_select(0, batch_local[k0:k1]).float()
                 for k in range(k0, k1):
                     rgb[k] = images[k - k0]
@@ -517,9 +603,12 @@ class KittiDataset:
             a, b = int(starts[k]), int(starts[k + 1])
             frame = self._frames[sorted_frames[k]]
             sample = {key: t[a:b] for key, t in rows.items()}
-            sample.update(rgb_image=rgb[k], cam_p=cam_p[k], gt_inst_xyz_maps_local=local[a:b],
-                          gt_inst_xyz_maps_global=glob[a:b], gt_valid_mask_maps=valid[a:b],
-                          sample_name=frame['name'], num_objs=frame['num_objs'], oversample_indices=over_idx[a:b],
-                          jitter_trials=trials[a:b])
+            if self.is_test:
+                sample.update(rgb_image=rgb[k], cam_p=cam_p[k], sample_name=frame['name'], num_objs=frame['num_objs'])
+            else:
+                sample.update(rgb_image=rgb[k], cam_p=cam_p[k], gt_inst_xyz_maps_local=local[a:b],
+                              gt_inst_xyz_maps_global=glob[a:b], gt_valid_mask_maps=valid[a:b],
+                              sample_name=frame['name'], num_objs=frame['num_objs'],
+                              oversample_indices=over_idx[a:b], jitter_trials=trials[a:b])
             samples[order[k]] = sample
         return samples

@@ -96,18 +96,19 @@ def filter_labels(obj_labels, classes=None, difficulty=None, box_2d_height=None,
     the level's thresholds); box height > box_2d_height; occlusion < occlusion; truncation < truncation;
     depth_range[0] < z < depth_range[1] -- strict or inclusive exactly as obj_utils.py:215-345 writes them."""
     obj_mask = np.full(len(obj_labels), True)
+    mask = lambda flags: np.asarray(flags, bool).reshape(-1)  # (an empty label file gives an empty list: float64)
     if classes is not None:
-        obj_mask &= [(obj.type in classes) for obj in obj_labels]
+        obj_mask &= mask([(obj.type in classes) for obj in obj_labels])
     if difficulty is not None:
-        obj_mask &= [_check_difficulty(obj, difficulty) for obj in obj_labels]
+        obj_mask &= mask([_check_difficulty(obj, difficulty) for obj in obj_labels])
     if box_2d_height is not None:
-        obj_mask &= [(obj.y2 - obj.y1) > box_2d_height for obj in obj_labels]
+        obj_mask &= mask([(obj.y2 - obj.y1) > box_2d_height for obj in obj_labels])
     if occlusion is not None:
-        obj_mask &= [obj.occlusion < occlusion for obj in obj_labels]
+        obj_mask &= mask([obj.occlusion < occlusion for obj in obj_labels])
     if truncation is not None:
-        obj_mask &= [obj.truncation < truncation for obj in obj_labels]
+        obj_mask &= mask([obj.truncation < truncation for obj in obj_labels])
     if depth_range is not None:
-        obj_mask &= [depth_range[0] < obj.t[2] < depth_range[1] for obj in obj_labels]
+        obj_mask &= mask([depth_range[0] < obj.t[2] < depth_range[1] for obj in obj_labels])
     return obj_labels[obj_mask], obj_mask
 
 
