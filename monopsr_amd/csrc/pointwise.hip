@@ -29,8 +29,10 @@
 //   * tile sequence of workgroup b: b, b + G, ...; G is a multiple of 8 x column blocks, so b keeps its XCD and its
 //     column block (the same 32 rows of w per wave for its whole life); consecutive workgroups of an XCD share the
 //     row group (A from L2).  Tiles past the last row group are all-zero work behind zero-length descriptors;
-//   * every descriptor is built in the scalar ALU (base = the row, length = bytes up to row M): rows past M vanish in
-//     the range check, no vector-ALU address work.
+//   * every descriptor is built in the scalar ALU (base = a row, length = bytes up to row M: rows past M vanish in
+//     the range check), ONE per tile (A, mask / emit words) or per 32-row block of it (residual, result); the rows
+//     inside it are per-lane constants of the launch and wait in vector registers as ready byte offsets: an access
+//     costs its own instruction and no address arithmetic.
 // M = batch x 144 pixels on the 12x12 trunk maps: 96-row groups divide it exactly, and at batch 256 the 384 groups x
 // N / 128 column blocks are 1.5 (N = 256), 3 (512) or 6 (1024) tiles for each of the 512 resident workgroups.
 // What is left: one vmcnt counts loads AND stores in order, so the first wait after a store or a
@@ -127,9 +129,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         r.left = in ? (unsigned)(p.M - row) * (unsigned)width * 4u : 0u;
         return r;
     };
+    auto rsrc_of = [&](RowRef r) __attribute__((always_inline)) {
+        const unsigned long long a = ((unsigned long long)r.hi << 32) | r.lo;
+        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(a), 0, (int)r.left, 0x00020000);
+    };
     // descriptor `rows` rows further on.  max(left - off, 0) in the scalar ALU (hipcc picks the vector ALU's saturating
-    // subtract and a waterfall loop otherwise); the asm also keeps hipcc from building a stage's descriptors ahead of
-    // its first slot and spilling them.
+    // subtract and a waterfall loop otherwise); the asm also keeps the descriptor of a 32-row block in the slot that
+    // first uses it (hipcc otherwise builds a tile's descriptors ahead of its first stage and spills them).
     auto rsrc_at = [&](RowRef r, int rows, int width) __attribute__((always_inline)) {
         const unsigned off = (unsigned)rows * (unsigned)width * 4u;
         unsigned left;
@@ -141,12 +147,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     // ---- A producer: thread = (row prow of each 32-row tile, 16-byte piece pslot of the row's 128 bytes)
     const int prow = tid >> 3, pslot = tid & 7;
-    const unsigned avoff = (unsigned)prow * (unsigned)p.K * 4u + (unsigned)pslot * 16u;
+    unsigned avoff[WT];  // row prow of 32-row tile j of the row group, as a byte offset behind the group's first row
+#pragma unroll
+    for (int j = 0; j < WT; ++j) {
+        avoff[j] = (unsigned)(32 * j + prow) * (unsigned)p.K * 4u + (unsigned)pslot * 16u;
+        asm volatile("" : "+v"(avoff[j]));  // (held, not rebuilt per request)
+    }
     const unsigned awoff = (unsigned)prow * 128u + (unsigned)((pslot ^ ((prow >> 1) & 7)) << 4);
     float4 stg[WT];
-    auto load_a = [&](RowRef xr, int stage, int j) __attribute__((always_inline)) {
-        stg[j] = __builtin_bit_cast(
-            float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_at(xr, 32 * j, p.K), avoff, stage * (KS * 4), 0));
+    auto load_a = [&](__amdgpu_buffer_rsrc_t xd, int stage, int j) __attribute__((always_inline)) {
+        stg[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xd, avoff[j], stage * (KS * 4), 0));
     };
     auto store_a = [&](int buf, int j) __attribute__((always_inline)) {
         *reinterpret_cast<float4 *>(lds + buf * STAGE_B + j * TILE_B + awoff) = stg[j];
@@ -177,18 +187,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
     // ---- residual staging: piece P = tid + 256 jj of the 96 x 128 tile (row-major, 32 pieces per row): row
     // (tid >> 5) + 8 jj, columns 4 (tid & 31) .. + 3
-    const unsigned rvoff = ((unsigned)(tid >> 5) * (unsigned)p.N + (unsigned)(n0 + 4 * (tid & 31))) * 4u;
+    // rvoff[u]: row (tid >> 5) + 8 u as a byte offset behind the first row of a 32-row block; piece jj is u = jj & 3 of
+    // block jj >> 2, whose descriptor `rd` is built in front of the block's first request
+    unsigned rvoff[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        rvoff[u] = ((unsigned)((tid >> 5) + 8 * u) * (unsigned)p.N + (unsigned)(n0 + 4 * (tid & 31))) * 4u;
+        if constexpr (RES) asm volatile("" : "+v"(rvoff[u]));
+    }
+    __amdgpu_buffer_rsrc_t rd;
     const unsigned rwoff = (unsigned)(RES_OFF + (tid >> 5) * 512 + (tid & 31) * 16);
     float4 rst[6];
     auto load_r = [&](RowRef rr, int jj) __attribute__((always_inline)) {
-        rst[jj % 6] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_at(rr, 8 * jj, p.N), rvoff, 0, RES_AUX));
+        if (jj % 4 == 0) rd = rsrc_at(rr, 8 * jj, p.N);
+        rst[jj % 6] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, rvoff[jj & 3], 0, RES_AUX));
     };
     auto store_r = [&](int jj) __attribute__((always_inline)) {
         *reinterpret_cast<float4 *>(lds + rwoff + jj * 4096) = rst[jj % 6];
     };
     // element (q, e) of a lane: row 32 q + (e & 3) + 8 (e >> 2) + 4 (lane >> 5) of the tile, column 32 wave + (lane & 31)
     const unsigned rroff = (unsigned)(RES_OFF + (4 * (lane >> 5)) * 512 + (32 * wave + (lane & 31)) * 4);
-    const unsigned evoff = ((unsigned)(4 * (lane >> 5)) * (unsigned)p.N + (unsigned)ncol) * 4u;
+    // ... as a byte offset behind the first row of 32-row block q, whose descriptor `yd` is built in front of the
+    // block's first store
+    unsigned evoff[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        evoff[e] = ((unsigned)((e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)) * (unsigned)p.N + (unsigned)ncol) * 4u;
+        asm volatile("" : "+v"(evoff[e]));
+    }
+    __amdgpu_buffer_rsrc_t yd;
 
     const float bias = (p.bias && wave_live) ? p.bias[ncol] : 0.f;
     const float one = lane < 32 ? 1.f : 0.f;
@@ -197,13 +224,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // tile starts and used a whole tile later; out_bits() = what a store writes for element (q, e) of a set
     unsigned mw[2][WT];
     const unsigned mvoff = wave_live ? (unsigned)ncol * 4u : OOB;
+    // the words of the 32-row blocks from row r0 (< M when live) on: block q of the tile is q rows of N words further,
+    // in the vector offset -- a block past the last one vanishes in the range check
+    auto words_rsrc = [&](const unsigned *base, int r0, bool live) __attribute__((always_inline)) {
+        const unsigned off = live ? (unsigned)(r0 / 32) * (unsigned)p.N * 4u : 0u;
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(reinterpret_cast<const char *>(base)) + off, 0,
+                                                 live ? (int)(p.maskbytes - off) : 0, 0x00020000);
+    };
     auto load_mask = [&](auto set_c, int r0, bool live) __attribute__((always_inline)) {
         constexpr int S = decltype(set_c)::value;
-        const __amdgpu_buffer_rsrc_t rr =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned *>(p.mask), 0, live ? (int)p.maskbytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rr = words_rsrc(p.mask, r0, live);
 #pragma unroll
         for (int q = 0; q < WT; ++q)
-            mw[S][q] = __builtin_amdgcn_raw_buffer_load_b32(rr, mvoff, (unsigned)((live ? r0 : 0) / 32 + q) * (unsigned)p.N * 4u, 0);
+            mw[S][q] = __builtin_amdgcn_raw_buffer_load_b32(rr, mvoff + (unsigned)q * (unsigned)p.N * 4u, 0, 0);
     };
     const unsigned mshift = 16u * (unsigned)(lane >> 5);
     unsigned mb[2][WT];  // EMIT: the halfword of set S's tile gathering while its elements are stored
@@ -224,9 +257,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // EMIT: after element 15 of block q of the tile at row r0 the halfword is complete
     auto emit_bits = [&](auto set_c, int q, int r0, bool live) __attribute__((always_inline)) {
         constexpr int S = decltype(set_c)::value;
-        const __amdgpu_buffer_rsrc_t rr =
-            __builtin_amdgcn_make_buffer_rsrc(p.emit, 0, live ? (int)p.maskbytes : 0, 0x00020000);
-        __builtin_amdgcn_raw_buffer_store_b16((short)mb[S][q], rr, emvoff, (unsigned)((live ? r0 : 0) / 32 + q) * (unsigned)p.N * 4u, 0);
+        __builtin_amdgcn_raw_buffer_store_b16((short)mb[S][q], words_rsrc(p.emit, r0, live),
+                                              emvoff + (unsigned)q * (unsigned)p.N * 4u, 0, 0);
     };
 #pragma unroll
     for (int q = 0; q < WT; ++q)
@@ -256,6 +288,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         xa.lo = wrap2 ? xn.lo : xc.lo;
         xa.hi = wrap2 ? xn.hi : xc.hi;
         xa.left = wrap2 ? xn.left : xc.left;
+        const __amdgpu_buffer_rsrc_t xd = rsrc_of(xa);
         const int a_st = wrap2 ? s + 2 - nst : s + 2;
         const bool wrap1 = s + 1 >= nst;
         const int b_st = wrap1 ? 0 : s + 1;
@@ -275,12 +308,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     if (m == 0 && kb < 3) read_a(buf, kb + 1, set ^ 1);
                     if constexpr (SE0 >= 0) if (D % SSTEP == 1 && SE0 + D / SSTEP < 16 * WT) {
                         const int q = (SE0 + D / SSTEP) / 16, e = (SE0 + D / SSTEP) % 16;
-                        __builtin_amdgcn_raw_buffer_store_b32(out_bits(IC<SET ^ 1>{}, q, e),
-                                                              rsrc_at(yp, 32 * q + (e & 3) + 8 * (e >> 2), p.N), evoff, 0, STORE_AUX);
+                        if (e == 0) yd = rsrc_at(yp, 32 * q, p.N);
+                        __builtin_amdgcn_raw_buffer_store_b32(out_bits(IC<SET ^ 1>{}, q, e), yd, evoff[e], 0, STORE_AUX);
                         if constexpr (EMIT) if (e == 15) emit_bits(IC<SET ^ 1>{}, q, r0p, plive);
                     }
                     if (D >= 4 && D < 4 + 12 * WT && (D - 4) % 12 == 0) store_a(buf ^ 1, (D - 4) / 12);
-                    if (D >= 6 && D < 6 + 12 * WT && (D - 6) % 12 == 0) load_a(xa, a_st, (D - 6) / 12);
+                    if (D >= 6 && D < 6 + 12 * WT && (D - 6) % 12 == 0) load_a(xd, a_st, (D - 6) / 12);
                     if (m == 11) load_b(b_live, b_st, kb);
                     if constexpr (RES) {
                         // (stage 2 first writes piece n of the first six out of its register, then requests piece
@@ -298,7 +331,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- prologue: the first tile's residual into its LDS copy, its stage 0 into LDS, stage 1 into the staging
     // registers, the B chunks of stage 0
     {
-        const RowRef x0 = row_ref(p.x, p.K, r0_of(0), true);
+        const __amdgpu_buffer_rsrc_t x0 = rsrc_of(row_ref(p.x, p.K, r0_of(0), true));
 #pragma unroll
         for (int j = 0; j < WT; ++j) load_a(x0, 0, j);
 #pragma unroll
@@ -391,8 +424,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int q = 0; q < WT; ++q)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                __builtin_amdgcn_raw_buffer_store_b32(out_bits(IC<SET>{}, q, e),
-                                                      rsrc_at(yl, 32 * q + (e & 3) + 8 * (e >> 2), p.N), evoff, 0, STORE_AUX);
+                if (e == 0) yd = rsrc_at(yl, 32 * q, p.N);
+                __builtin_amdgcn_raw_buffer_store_b32(out_bits(IC<SET>{}, q, e), yd, evoff[e], 0, STORE_AUX);
                 if constexpr (EMIT) if (e == 15) emit_bits(IC<SET>{}, q, r0s, r0s < p.M);
             }
     };
