@@ -29,6 +29,13 @@
 //     bit-identical to visiting the zero taps.
 //   * split_k > 1 writes raw partial tiles to a workspace; a second kernel reduces and applies the epilogue
 //     (used for the K = 18432 fully-connected layers where M = batch is small).
+//
+// Two kernels schedule this GEMM: conv_igemm_kernel (one tile per workgroup) and conv_sk_kernel (stream-K, persistent).
+// What a tile IS -- row decode, K-step cursor, bounds-tested load, LDS fill, MMA step, accumulator settle, epilogue --
+// is written once ("tile body" below) and called by both; a kernel owns only how it gets to a tile and a K range:
+// the XCD tile order, split-K slices, the DEPTH pipelines and the decode-free PLAIN / CLS loads in the first, the unit
+// ranges, slabs and ticket protocol in the second.
+// (The matrix-pipe microbenchmarks that used to sit at the end of this file are in microbench.hip.)
 #include <atomic>
 #include <mutex>
 #include <type_traits>
@@ -84,6 +91,293 @@ struct ConvParams {
     PixelClass cls[MAX_CLS];
 };
 
+// ------------------------------------------------------------------------------------------------ tile body
+// The pieces of one BM x BN tile's work that do not depend on how tiles and K ranges are handed out.  All forced
+// inline: each is a few statements of its caller's K loop or epilogue.
+
+// class row -> (y, x, linear NHWC pixel index); -1 for rows past the end of the class.  PLAIN (a 1x1 layer over whole
+// images): row r is pixel r.
+template <bool PLAIN>
+__device__ __forceinline__ int decode_row(const ConvParams &p, const PixelClass &pc, int row, int &yy, int &xx)
+{
+    if constexpr (PLAIN) {
+        yy = xx = 0;
+        return row < pc.rows ? row : -1;
+    }
+    if (row >= pc.rows) {
+        yy = -(1 << 20);  // fails every bounds test
+        xx = 0;
+        return -1;
+    }
+    const int img = fdiv(row, pc.fd_ppi), pp = row - img * (pc.h * pc.w);
+    const int py = fdiv(pp, pc.fd_w);
+    yy = pc.y0 + py;
+    xx = pc.x0 + (pp - py * pc.w);
+    return (img * p.H + yy) * p.W + xx;
+}
+
+// A thread's fixed rows of both operands: it loads row lrow + 32 * j of the A tile (pixel coordinates ay / ax, byte
+// offset abase) and of the B tile (byte offset bbase of filter n; past N an out-of-range offset -> zeros).  `col` is
+// the byte offset inside a row that the offsets already include, `apast` the A offset of rows past the end of the
+// class: 0 / 0 for the bounds-tested load (such a row's coordinates fail every test), the thread's column and an
+// out-of-range offset where the row offset is the whole vector offset.
+template <bool PLAIN, int AV, int BV>
+__device__ __forceinline__ void tile_rows(const ConvParams &p, const PixelClass &pc, int r0, int n0, int lrow,
+                                          unsigned col, unsigned apast, int (&ay)[AV], int (&ax)[AV],
+                                          unsigned (&abase)[AV], unsigned (&bbase)[BV])
+{
+#pragma unroll
+    for (int j = 0; j < AV; ++j) {
+        const int pix = decode_row<PLAIN>(p, pc, r0 + lrow + 32 * j, ay[j], ax[j]);
+        abase[j] = pix < 0 ? apast : (unsigned)pix * (unsigned)p.C * 4u + col;
+    }
+    const int Ktot = p.KH * p.KW * p.C;
+#pragma unroll
+    for (int j = 0; j < BV; ++j) {
+        const int n = n0 + lrow + 32 * j;
+        bbase[j] = n < p.N ? (unsigned)n * (unsigned)Ktot * 4u + col : p.wbytes;
+    }
+}
+
+// K-step state, advanced incrementally: taps fastest (kx, then ky over the class's taps), channel block slowest.
+// The taps of one 32-channel block re-read the same few KB of pixels (shifted), so their gathers hit L1 / L2;
+// with the channel block fastest a pixel came back after a whole channel sweep (1/9 of the K loop, far more than
+// the XCD's L2 holds across its resident tiles) and the 3x3 layers fetched their input ~4.7x from HBM.
+struct KCursor {
+    int cb, kx, ky;
+    // K step `ks` of a tile of class pc
+    __device__ __forceinline__ void seek(const PixelClass &pc, int ks)
+    {
+        const int ntx = pc.kx1 - pc.kx0 + 1;
+        const int ntaps = (pc.ky1 - pc.ky0 + 1) * ntx;
+        cb = ks / ntaps;
+        const int tap = ks - cb * ntaps;
+        const int ty = tap / ntx;
+        ky = pc.ky0 + ty;
+        kx = pc.kx0 + (tap - ty * ntx);
+    }
+    __device__ __forceinline__ void advance(const PixelClass &pc)
+    {
+        if (++kx > pc.kx1) {
+            kx = pc.kx0;
+            if (++ky > pc.ky1) {
+                ky = pc.ky0;
+                ++cb;
+            }
+        }
+    }
+};
+
+// Loads the A / B tile of K step `st` into registers, every load bounds-tested (any geometry); `live` false (past
+// the last K step) turns every load into an out-of-range one (no traffic).
+template <int AV, int BV>
+__device__ __forceinline__ void load_tile_checked(const ConvParams &p, __amdgpu_buffer_rsrc_t rx,
+                                                  __amdgpu_buffer_rsrc_t rw, const KCursor &st, int lcol, bool live,
+                                                  const int (&ay)[AV], const int (&ax)[AV],
+                                                  const unsigned (&abase)[AV], const unsigned (&bbase)[BV],
+                                                  float4 (&ra)[AV], float4 (&rb)[BV])
+{
+    const int dy = (st.ky - (p.KH >> 1)) * p.dil, dx = (st.kx - (p.KW >> 1)) * p.dil;
+    const int c = st.cb * BK + lcol;
+    const bool cok = (c < p.C) & live;
+    const int aoff = ((dy * p.W + dx) * p.C + c) * 4;
+#pragma unroll
+    for (int j = 0; j < AV; ++j) {
+        const int yy = ay[j] + dy, xx = ax[j] + dx;
+        const bool ok = cok & (yy >= 0) & (yy < p.H) & (xx >= 0) & (xx < p.W);
+        const unsigned off = ok ? abase[j] + (unsigned)aoff : p.xbytes;
+        ra[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
+    }
+    const unsigned boff = (unsigned)(((st.ky * p.KW + st.kx) * p.C + c) * 4);
+#pragma unroll
+    for (int j = 0; j < BV; ++j) {
+        const unsigned off = cok ? bbase[j] + boff : p.wbytes;
+        rb[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rw, off, 0, 0));
+    }
+}
+
+// Register tile -> LDS: thread (lrow, lcol) writes four floats of row lrow + 32 * j of both tiles.
+// bf16x3: a row keeps its 144-byte stride: [32 hi bf16 | 32 lo bf16 | 16 B pad]
+template <int MATH, int AV, int BV>
+__device__ __forceinline__ void fill_lds(float *As, float *Bs, int lrow, int lcol, const float4 (&ra)[AV],
+                                         const float4 (&rb)[BV])
+{
+    auto put = [&](float *row, const float4 &v4) {
+        if constexpr (MATH == MATH_BF16X3) {
+            const f32x4 v = {v4.x, v4.y, v4.z, v4.w};
+            const bf16x4 hi = __builtin_convertvector(v, bf16x4);
+            const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), bf16x4);
+            __bf16 *r = reinterpret_cast<__bf16 *>(row);
+            *reinterpret_cast<bf16x4 *>(r + lcol) = hi;
+            *reinterpret_cast<bf16x4 *>(r + BK + lcol) = lo;
+        } else {
+            *reinterpret_cast<float4 *>(row + lcol) = v4;
+        }
+    };
+#pragma unroll
+    for (int j = 0; j < AV; ++j) put(&As[(lrow + 32 * j) * LDS_STRIDE], ra[j]);
+#pragma unroll
+    for (int j = 0; j < BV; ++j) put(&Bs[(lrow + 32 * j) * LDS_STRIDE], rb[j]);
+}
+
+// One K step of a wave's TM x TN accumulator tiles from the LDS tiles.  Aw / Bw: the lane's fragment of the wave's first
+// A / B rows -- row lane & 31, byte 16 * (lane >> 5) of it (lds_fragment) -- in both arithmetic modes.
+__device__ __forceinline__ int lds_fragment(int lane) { return (lane & 31) * LDS_STRIDE + (lane >> 5) * 4; }
+
+template <int TM, int TN, int MATH>
+__device__ __forceinline__ void mma_tile(f32x16 (&acc)[TM][TN], const float *Aw, const float *Bw)
+{
+    if constexpr (MATH == MATH_BF16X3) {
+        // lane (i = l & 31, g = l >> 5) supplies k = 16*slice + 8*g .. +7 of row i for both operands (the same
+        // k assignment on the A and the B side is all the dot product needs)
+        const __bf16 *Ah = reinterpret_cast<const __bf16 *>(Aw), *Bh = reinterpret_cast<const __bf16 *>(Bw);
+#pragma unroll
+        for (int sl = 0; sl < BK / 16; ++sl) {
+            bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                ah[i] = *reinterpret_cast<const bf16x8 *>(Ah + i * 32 * LDS_STRIDE * 2 + sl * 16);
+                al[i] = *reinterpret_cast<const bf16x8 *>(Ah + i * 32 * LDS_STRIDE * 2 + BK + sl * 16);
+            }
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                bh[j] = *reinterpret_cast<const bf16x8 *>(Bh + j * 32 * LDS_STRIDE * 2 + sl * 16);
+                bl[j] = *reinterpret_cast<const bf16x8 *>(Bh + j * 32 * LDS_STRIDE * 2 + BK + sl * 16);
+            }
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+                }
+        }
+    } else {
+#pragma unroll
+        for (int kb = 0; kb < BK / 8; ++kb) {
+            float4 a[TM], b[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const float4 *>(Aw + i * 32 * LDS_STRIDE + kb * 8);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const float4 *>(Bw + j * 32 * LDS_STRIDE + kb * 8);
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
+                }
+        }
+    }
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void clear_acc(f32x16 (&acc)[TM][TN])
+{
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+}
+
+// The 16-pass fp32 MFMA needs 18 wait states before its result is read.  hipcc (ROCm 7.2) was seen to place
+// the first v_accvgpr_read too early on a loop-exit edge (wrong last accumulator element); the wait is made
+// explicit here and tied to the accumulators so nothing is scheduled across it.
+template <int TM, int TN>
+__device__ __forceinline__ void settle_acc(f32x16 (&acc)[TM][TN])
+{
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) asm volatile("s_nop 15\n\ts_nop 7" : "+a"(acc[i][j]));
+}
+
+// Epilogue of the tile at class row r0, channel n0: dst = act(tile + bias + residual) when `fused`, else the raw
+// tile (a split-K partial).  tile(i, j) yields the wave's 32x32 accumulator tile (i, j); it is asked for once per tile.
+// C/D layout of the 32x32 MFMA: column = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5).
+template <int TM, int TN, bool PLAIN, class TileFn>
+__device__ __forceinline__ void store_output(const ConvParams &p, const PixelClass &pc, float *lds, int r0, int n0,
+                                             int wm, int wn, int wave, int lane, bool fused, float *dst, TileFn tile)
+{
+    const int col = lane & 31, rsub = (lane >> 5) * 4;
+    int dy_, dx_;
+    if ((p.N & 3) == 0) {
+        // Vector path: each wave transposes one 32x32 accumulator tile at a time through its own 4.5 KiB LDS
+        // slice so that a lane owns 4 consecutive channels of a pixel: 16-byte residual loads / output stores
+        // (4x fewer memory instructions than the element-per-lane layout; the K = 256 conv3 layers are
+        // epilogue-bound otherwise).
+        __syncthreads();  // every wave is done with the last A/B tile
+        float *ep = lds + wave * (32 * LDS_STRIDE);
+        const int erow = lane >> 3, ecol = (lane & 7) * 4;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            int pix[4];
+#pragma unroll
+            for (int it = 0; it < 4; ++it)
+                pix[it] = decode_row<PLAIN>(p, pc, r0 + (wm * TM + i) * 32 + erow + 8 * it, dy_, dx_);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int n = n0 + (wn * TN + j) * 32 + ecol;
+                float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (fused && p.bias && n < p.N) bias = *reinterpret_cast<const float4 *>(p.bias + n);
+                const f32x16 tv = tile(i, j);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) ep[((e & 3) + 8 * (e >> 2) + rsub) * LDS_STRIDE + col] = tv[e];
+                __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                for (int it = 0; it < 4; ++it) {
+                    float4 v = *reinterpret_cast<const float4 *>(&ep[(erow + 8 * it) * LDS_STRIDE + ecol]);
+                    if (pix[it] >= 0 && n < p.N) {
+                        const size_t o = (size_t)pix[it] * p.N + n;
+                        if (fused) {
+                            v.x += bias.x; v.y += bias.y; v.z += bias.z; v.w += bias.w;
+                            if (p.residual) {
+                                const float4 rr = *reinterpret_cast<const float4 *>(p.residual + o);
+                                v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
+                            }
+                            if (p.relu) {
+                                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                            }
+                        }
+                        *reinterpret_cast<float4 *>(dst + o) = v;
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        return;
+    }
+    // scalar path (N not a multiple of 4: the 3-channel xyz head, the 27- and 2-wide head outputs)
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int n = n0 + (wn * TN + j) * 32 + col;
+            const f32x16 tv = tile(i, j);
+            if (n >= p.N) continue;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int pix = decode_row<PLAIN>(p, pc, r0 + (wm * TM + i) * 32 + rsub + (e & 3) + 8 * (e >> 2), dy_, dx_);
+                if (pix < 0) continue;
+                const size_t o = (size_t)pix * p.N + n;
+                float v = tv[e];
+                if (fused) {
+                    if (p.bias) v += p.bias[n];
+                    if (p.residual) v += p.residual[o];
+                    if (p.relu) v = fmaxf(v, 0.f);
+                }
+                dst[o] = v;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ one tile per workgroup
 // PLAIN: a 1x1 layer (convolution or fully connected) over whole images with C a multiple of 32 -- row r of the GEMM
 // is pixel r, a K step is the next 128 bytes of every row: no decode, and the K loop's loads take their per-step
 // offset in a scalar register (no vector-ALU work at all between the MFMAs).
@@ -127,9 +421,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p)
     if (ci < 0) return;  // block-uniform
     const PixelClass pc = p.cls[ci];
     const int r0 = (xcd + 8 * lm) * BM;  // first row of the tile inside its class
-    const int ppi = pc.h * pc.w;               // class pixels per image
-    const int ntx = pc.kx1 - pc.kx0 + 1;
-    const int ksteps_cls = (pc.ky1 - pc.ky0 + 1) * ntx * p.cblocks;
+    const int ksteps_cls = (pc.ky1 - pc.ky0 + 1) * (pc.kx1 - pc.kx0 + 1) * p.cblocks;
     // split-K: every class shares ITS K steps among the p.splits slices (an empty slice writes a zero partial)
     const int ks_per = p.splits > 1 ? (ksteps_cls + p.splits - 1) / p.splits : ksteps_cls;
     const int ks_begin = si * ks_per;
@@ -144,61 +436,21 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p)
     const __amdgpu_buffer_rsrc_t rw =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.w), 0, (int)p.wbytes, 0x00020000);
 
-    // class row -> (y, x, linear NHWC pixel index); -1 for rows past the end of the class
-    auto decode = [&](int row, int &yy, int &xx) -> int {
-        if constexpr (PLAIN) {
-            yy = xx = 0;
-            return row < pc.rows ? row : -1;
-        }
-        if (row >= pc.rows) {
-            yy = -(1 << 20);  // fails every bounds test
-            xx = 0;
-            return -1;
-        }
-        const int img = fdiv(row, pc.fd_ppi), pp = row - img * ppi;
-        const int py = fdiv(pp, pc.fd_w);
-        yy = pc.y0 + py;
-        xx = pc.x0 + (pp - py * pc.w);
-        return (img * p.H + yy) * p.W + xx;
-    };
-
-    // per-thread A rows: pixel coordinates and byte offset are fixed for the whole K loop
+    // per-thread A / B rows: pixel coordinates and byte offsets are fixed for the whole K loop
     int ay[AV], ax[AV];
-    unsigned abase[AV];
-#pragma unroll
-    for (int j = 0; j < AV; ++j) {
-        const int pix = decode(r0 + lrow + 32 * j, ay[j], ax[j]);
-        abase[j] = (unsigned)(pix < 0 ? 0 : pix) * (unsigned)p.C * 4u;
-        // the whole voffset; rows past the end get one that is out of range for the (CLS: enlarged) descriptor
-        if constexpr (PLAIN || CLS)
-            abase[j] = pix < 0 ? p.xbytes + (CLS ? (unsigned)(p.dil * (p.W + 1) * p.C * 4) : 0u)
-                               : abase[j] + (unsigned)lcol * 4u;
-    }
-    const int Ktot = p.KH * p.KW * p.C;
-    unsigned bbase[BV];
-#pragma unroll
-    for (int j = 0; j < BV; ++j) {
-        const int n = n0 + lrow + 32 * j;
-        bbase[j] = n < p.N ? (unsigned)n * (unsigned)Ktot * 4u : p.wbytes;  // past the end -> zeros
-        if constexpr (PLAIN || CLS) bbase[j] = n < p.N ? bbase[j] + (unsigned)lcol * 4u : p.wbytes;
-    }
+    unsigned abase[AV], bbase[BV];
+    // PLAIN / CLS: the whole voffset; rows past the end get one that is out of range for the (CLS: enlarged) descriptor
+    tile_rows<PLAIN>(p, pc, r0, n0, lrow, PLAIN || CLS ? (unsigned)lcol * 4u : 0u,
+                     PLAIN ? p.xbytes : CLS ? p.xbytes + (unsigned)(p.dil * (p.W + 1) * p.C * 4) : 0u, ay, ax, abase,
+                     bbase);
 
-    // K-step state, advanced incrementally: taps fastest (kx, then ky over the class's taps), channel block slowest.
-    // The taps of one 32-channel block re-read the same few KB of pixels (shifted), so their gathers hit L1 / L2;
-    // with the channel block fastest a pixel came back after a whole channel sweep (1/9 of the K loop, far more than
-    // the XCD's L2 holds across its resident tiles) and the 3x3 layers fetched their input ~4.7x from HBM.
-    int st_cb, st_kx, st_ky;
-    if (PLAIN || ks_begin == 0) {  // block-uniform; PLAIN has one tap, so st_cb counts K steps
-        st_cb = ks_begin;
-        st_ky = pc.ky0;
-        st_kx = pc.kx0;
+    KCursor st;
+    if (PLAIN || ks_begin == 0) {  // block-uniform; PLAIN has one tap, so st.cb counts K steps
+        st.cb = ks_begin;
+        st.ky = pc.ky0;
+        st.kx = pc.kx0;
     } else {
-        const int ntaps = (pc.ky1 - pc.ky0 + 1) * ntx;
-        st_cb = ks_begin / ntaps;
-        const int tap = ks_begin - st_cb * ntaps;
-        const int ty = tap / ntx;
-        st_ky = pc.ky0 + ty;
-        st_kx = pc.kx0 + (tap - ty * ntx);
+        st.seek(pc, ks_begin);
     }
     // register staging: one tile in flight (DEPTH 1) or two (DEPTH 2: the loads of K step k + 2 are issued while step k
     // computes, so a load has a whole K step of every resident wave to return -- what a launch's last tiles need,
@@ -209,7 +461,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p)
     auto load_tile = [&](auto set_c, bool live) {
         constexpr int set = decltype(set_c)::value;
         if constexpr (PLAIN) {
-            const int soff = st_cb * (BK * 4);
+            const int soff = st.cb * (BK * 4);
             // a dead load (DEPTH 2 runs past the last K step) goes through a zero-length descriptor: a scalar
             // select instead of a per-lane one
             const __amdgpu_buffer_rsrc_t rxl =
@@ -222,14 +474,12 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p)
 #pragma unroll
             for (int j = 0; j < BV; ++j)
                 rb[set][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rwl, bbase[j], soff, 0));
-            ++st_cb;
-            return;
-        }
-        if constexpr (CLS) {
-            const int dy = (st_ky - (p.KH >> 1)) * p.dil, dx = (st_kx - (p.KW >> 1)) * p.dil;
+            ++st.cb;
+        } else if constexpr (CLS) {
+            const int dy = (st.ky - (p.KH >> 1)) * p.dil, dx = (st.kx - (p.KW >> 1)) * p.dil;
             const int bias = p.dil * (p.W + 1) * p.C * 4;  // -(most negative tap offset)
-            const int soffa = ((dy * p.W + dx) * p.C + st_cb * BK) * 4 + bias;
-            const int soffb = ((st_ky * p.KW + st_kx) * p.C + st_cb * BK) * 4;
+            const int soffa = ((dy * p.W + dx) * p.C + st.cb * BK) * 4 + bias;
+            const int soffb = ((st.ky * p.KW + st.kx) * p.C + st.cb * BK) * 4;
             // the window starts `bias` bytes before the tensor, so it is `bias` bytes longer: a valid row + tap lands
             // in [bias, bias + xbytes) whether the hardware range-checks the scalar offset or not
             const __amdgpu_buffer_rsrc_t rxl = __builtin_amdgcn_make_buffer_rsrc(
@@ -243,127 +493,24 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p)
 #pragma unroll
             for (int j = 0; j < BV; ++j)
                 rb[set][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rwl, bbase[j], soffb, 0));
-            if (++st_kx > pc.kx1) {
-                st_kx = pc.kx0;
-                if (++st_ky > pc.ky1) {
-                    st_ky = pc.ky0;
-                    ++st_cb;
-                }
-            }
-            return;
-        }
-        const int dy = (st_ky - (p.KH >> 1)) * p.dil, dx = (st_kx - (p.KW >> 1)) * p.dil;
-        const int c = st_cb * BK + lcol;
-        const bool cok = (c < p.C) & live;
-        const int aoff = ((dy * p.W + dx) * p.C + c) * 4;
-#pragma unroll
-        for (int j = 0; j < AV; ++j) {
-            const int yy = ay[j] + dy, xx = ax[j] + dx;
-            const bool ok = cok & (yy >= 0) & (yy < p.H) & (xx >= 0) & (xx < p.W);
-            const unsigned off = ok ? abase[j] + (unsigned)aoff : p.xbytes;
-            ra[set][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
-        }
-        const unsigned boff = (unsigned)(((st_ky * p.KW + st_kx) * p.C + c) * 4);
-#pragma unroll
-        for (int j = 0; j < BV; ++j) {
-            const unsigned off = cok ? bbase[j] + boff : p.wbytes;
-            rb[set][j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rw, off, 0, 0));
-        }
-        if (++st_kx > pc.kx1) {
-            st_kx = pc.kx0;
-            if (++st_ky > pc.ky1) {
-                st_ky = pc.ky0;
-                ++st_cb;
-            }
+            st.advance(pc);
+        } else {
+            load_tile_checked(p, rx, rw, st, lcol, live, ay, ax, abase, bbase, ra[set], rb[set]);
+            st.advance(pc);
         }
     };
     using Set0 = std::integral_constant<int, 0>;
     using Set1 = std::integral_constant<int, DEPTH - 1>;
-    // bf16x3: a row keeps its 144-byte stride: [32 hi bf16 | 32 lo bf16 | 16 B pad]
-    auto store_split = [&](float *row, const float4 &v4) {
-        const f32x4 v = {v4.x, v4.y, v4.z, v4.w};
-        const bf16x4 hi = __builtin_convertvector(v, bf16x4);
-        const bf16x4 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x4), bf16x4);
-        __bf16 *r = reinterpret_cast<__bf16 *>(row);
-        *reinterpret_cast<bf16x4 *>(r + lcol) = hi;
-        *reinterpret_cast<bf16x4 *>(r + BK + lcol) = lo;
-    };
     auto store_tile = [&](auto set_c) {
         constexpr int set = decltype(set_c)::value;
-#pragma unroll
-        for (int j = 0; j < AV; ++j) {
-            if constexpr (MATH == MATH_BF16X3) store_split(&As[(lrow + 32 * j) * LDS_STRIDE], ra[set][j]);
-            else *reinterpret_cast<float4 *>(&As[(lrow + 32 * j) * LDS_STRIDE + lcol]) = ra[set][j];
-        }
-#pragma unroll
-        for (int j = 0; j < BV; ++j) {
-            if constexpr (MATH == MATH_BF16X3) store_split(&Bs[(lrow + 32 * j) * LDS_STRIDE], rb[set][j]);
-            else *reinterpret_cast<float4 *>(&Bs[(lrow + 32 * j) * LDS_STRIDE + lcol]) = rb[set][j];
-        }
+        fill_lds<MATH>(As, Bs, lrow, lcol, ra[set], rb[set]);
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int frag = (lane & 31) * LDS_STRIDE + (lane >> 5) * 4;
-    const float *Aw = As + (wm * TM * 32) * LDS_STRIDE + frag;
-    const float *Bw = Bs + (wn * TN * 32) * LDS_STRIDE + frag;
-
-    auto compute_tile = [&]() {
-        if constexpr (MATH == MATH_BF16X3) {
-            // lane (i = l & 31, g = l >> 5) supplies k = 16*slice + 8*g .. +7 of row i for both operands (the same
-            // k assignment on the A and the B side is all the dot product needs)
-            const __bf16 *Ah = reinterpret_cast<const __bf16 *>(As + (wm * TM * 32 + (lane & 31)) * LDS_STRIDE) +
-                               (lane >> 5) * 8;
-            const __bf16 *Bh = reinterpret_cast<const __bf16 *>(Bs + (wn * TN * 32 + (lane & 31)) * LDS_STRIDE) +
-                               (lane >> 5) * 8;
-#pragma unroll
-            for (int sl = 0; sl < BK / 16; ++sl) {
-                bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    ah[i] = *reinterpret_cast<const bf16x8 *>(Ah + i * 32 * LDS_STRIDE * 2 + sl * 16);
-                    al[i] = *reinterpret_cast<const bf16x8 *>(Ah + i * 32 * LDS_STRIDE * 2 + BK + sl * 16);
-                }
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    bh[j] = *reinterpret_cast<const bf16x8 *>(Bh + j * 32 * LDS_STRIDE * 2 + sl * 16);
-                    bl[j] = *reinterpret_cast<const bf16x8 *>(Bh + j * 32 * LDS_STRIDE * 2 + BK + sl * 16);
-                }
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                    }
-            }
-            return;
-        }
-#pragma unroll
-        for (int kb = 0; kb < BK / 8; ++kb) {
-            float4 a[TM], b[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const float4 *>(Aw + i * 32 * LDS_STRIDE + kb * 8);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const float4 *>(Bw + j * 32 * LDS_STRIDE + kb * 8);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
-                }
-        }
-    };
+    clear_acc(acc);
+    const float *Aw = As + (wm * TM * 32) * LDS_STRIDE + lds_fragment(lane);
+    const float *Bw = Bs + (wn * TN * 32) * LDS_STRIDE + lds_fragment(lane);
+    auto compute_tile = [&]() { mma_tile<TM, TN, MATH>(acc, Aw, Bw); };
 
     // K loop; last tile peeled so the body has no conditional.  ks_begin >= ks_end only for an empty split-K slice
     // (block-uniform).
@@ -406,86 +553,12 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p)
             }
         }
     }
+    settle_acc(acc);
 
-    // The 16-pass fp32 MFMA needs 18 wait states before its result is read.  hipcc (ROCm 7.2) was seen to place
-    // the first v_accvgpr_read too early on a loop-exit edge (wrong last accumulator element); the wait is made
-    // explicit here and tied to the accumulators so nothing is scheduled across it.
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) asm volatile("s_nop 15\n\ts_nop 7" : "+a"(acc[i][j]));
-
-    // epilogue.  C/D layout of the 32x32 MFMA: column = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5).
-    const int col = lane & 31, rsub = (lane >> 5) * 4;
-    float *dst = p.splits == 1 ? p.y : p.ws + (size_t)si * p.M * p.N;
-    const bool fused = p.splits == 1;
-    int dy_, dx_;
-    if ((p.N & 3) == 0) {
-        // Vector path: each wave transposes one 32x32 accumulator tile at a time through its own 4.5 KiB LDS
-        // slice so that a lane owns 4 consecutive channels of a pixel: 16-byte residual loads / output stores
-        // (4x fewer memory instructions than the element-per-lane layout; the K = 256 conv3 layers are
-        // epilogue-bound otherwise).
-        __syncthreads();  // every wave is done with the last A/B tile
-        float *ep = lds + wave * (32 * LDS_STRIDE);
-        const int erow = lane >> 3, ecol = (lane & 7) * 4;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            int pix[4];
-#pragma unroll
-            for (int it = 0; it < 4; ++it) pix[it] = decode(r0 + (wm * TM + i) * 32 + erow + 8 * it, dy_, dx_);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0 + (wn * TN + j) * 32 + ecol;
-                float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (fused && p.bias && n < p.N) bias = *reinterpret_cast<const float4 *>(p.bias + n);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) ep[((e & 3) + 8 * (e >> 2) + rsub) * LDS_STRIDE + col] = acc[i][j][e];
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    float4 v = *reinterpret_cast<const float4 *>(&ep[(erow + 8 * it) * LDS_STRIDE + ecol]);
-                    if (pix[it] >= 0 && n < p.N) {
-                        const size_t o = (size_t)pix[it] * p.N + n;
-                        if (fused) {
-                            v.x += bias.x; v.y += bias.y; v.z += bias.z; v.w += bias.w;
-                            if (p.residual) {
-                                const float4 rr = *reinterpret_cast<const float4 *>(p.residual + o);
-                                v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
-                            }
-                            if (p.relu) {
-                                v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-                            }
-                        }
-                        *reinterpret_cast<float4 *>(dst + o) = v;
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-        return;
-    }
-    // scalar path (N not a multiple of 4: the 3-channel xyz head, the 27- and 2-wide head outputs)
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int pix = decode(r0 + (wm * TM + i) * 32 + rsub + (e & 3) + 8 * (e >> 2), dy_, dx_);
-            if (pix < 0) continue;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0 + (wn * TN + j) * 32 + col;
-                if (n >= p.N) continue;
-                const size_t o = (size_t)pix * p.N + n;
-                float v = acc[i][j][e];
-                if (fused) {
-                    if (p.bias) v += p.bias[n];
-                    if (p.residual) v += p.residual[o];
-                    if (p.relu) v = fmaxf(v, 0.f);
-                }
-                dst[o] = v;
-            }
-        }
-    }
+    const bool fused = p.splits == 1;  // else: a raw split-K partial for splitk_reduce_kernel
+    store_output<TM, TN, PLAIN>(p, pc, lds, r0, n0, wm, wn, wave, lane, fused,
+                                fused ? p.y : p.ws + (size_t)si * p.M * p.N,
+                                [&](int i, int j) -> f32x16 { return acc[i][j]; });
 }
 
 // y = act(sum_s ws[s] + bias + residual)
@@ -560,7 +633,6 @@ __global__ __launch_bounds__(256) void conv_sk_kernel(const ConvParams p, const 
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.x), 0, (int)p.xbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rw =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.w), 0, (int)p.wbytes, 0x00020000);
-    const int Ktot = p.KH * p.KW * p.C;
 
     while (u < uend) {
         // the thread id is made opaque per segment so that nothing derived from it is hoisted out of this loop and
@@ -570,9 +642,6 @@ __global__ __launch_bounds__(256) void conv_sk_kernel(const ConvParams p, const 
         const int lane = tid & 63, wave = tid >> 6;
         const int wm = wave / WN, wn = wave % WN;
         const int lrow = tid >> 3, lcol = (tid & 7) * 4;
-        const int frag = (lane & 31) * LDS_STRIDE + (lane >> 5) * 4;
-        const float *Aw = As + (wm * TM * 32) * LDS_STRIDE + frag;
-        const float *Bw = Bs + (wn * TN * 32) * LDS_STRIDE + frag;
         int ci = 0;
         while (u >= sk.ubase[ci + 1]) ++ci;
         const PixelClass pc = p.cls[ci];
@@ -583,146 +652,24 @@ __global__ __launch_bounds__(256) void conv_sk_kernel(const ConvParams p, const 
         const int ks_end = min(ksc, ks_begin + (int)(uend - u));
         const int mt = (int)(tic / (unsigned)p.ntiles), ni = (int)(tic - (unsigned)mt * (unsigned)p.ntiles);
         const int r0 = mt * BM, n0 = ni * BN;
-        const int ppi = pc.h * pc.w;
-        const int ntx = pc.kx1 - pc.kx0 + 1;
 
-        auto decode = [&](int row, int &yy, int &xx) -> int {
-            if (row >= pc.rows) {
-                yy = -(1 << 20);
-                xx = 0;
-                return -1;
-            }
-            const int img = fdiv(row, pc.fd_ppi), pp = row - img * ppi;
-            const int py = fdiv(pp, pc.fd_w);
-            yy = pc.y0 + py;
-            xx = pc.x0 + (pp - py * pc.w);
-            return (img * p.H + yy) * p.W + xx;
-        };
         int ay[AV], ax[AV];
-        unsigned abase[AV];
-#pragma unroll
-        for (int j = 0; j < AV; ++j) {
-            const int pix = decode(r0 + lrow + 32 * j, ay[j], ax[j]);
-            abase[j] = (unsigned)(pix < 0 ? 0 : pix) * (unsigned)p.C * 4u;
-        }
-        unsigned bbase[BV];
-#pragma unroll
-        for (int j = 0; j < BV; ++j) {
-            const int n = n0 + lrow + 32 * j;
-            bbase[j] = n < p.N ? (unsigned)n * (unsigned)Ktot * 4u : p.wbytes;
-        }
-        int st_cb, st_kx, st_ky;
-        {
-            const int ntaps = (pc.ky1 - pc.ky0 + 1) * ntx;
-            st_cb = ks_begin / ntaps;
-            const int tap = ks_begin - st_cb * ntaps;
-            const int ty = tap / ntx;
-            st_ky = pc.ky0 + ty;
-            st_kx = pc.kx0 + (tap - ty * ntx);
-        }
+        unsigned abase[AV], bbase[BV];
+        tile_rows<false>(p, pc, r0, n0, lrow, 0u, 0u, ay, ax, abase, bbase);
+        KCursor st;
+        st.seek(pc, ks_begin);
         float4 ra[AV], rb[BV];
         auto load_tile = [&]() {
-            const int dy = (st_ky - (p.KH >> 1)) * p.dil, dx = (st_kx - (p.KW >> 1)) * p.dil;
-            const int c = st_cb * BK + lcol;
-            const bool cok = c < p.C;
-            const int aoff = ((dy * p.W + dx) * p.C + c) * 4;
-#pragma unroll
-            for (int j = 0; j < AV; ++j) {
-                const int yy = ay[j] + dy, xx = ax[j] + dx;
-                const bool ok = cok & (yy >= 0) & (yy < p.H) & (xx >= 0) & (xx < p.W);
-                const unsigned off = ok ? abase[j] + (unsigned)aoff : p.xbytes;
-                ra[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
-            }
-            const unsigned boff = (unsigned)(((st_ky * p.KW + st_kx) * p.C + c) * 4);
-#pragma unroll
-            for (int j = 0; j < BV; ++j) {
-                const unsigned off = cok ? bbase[j] + boff : p.wbytes;
-                rb[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rw, off, 0, 0));
-            }
-            if (++st_kx > pc.kx1) {
-                st_kx = pc.kx0;
-                if (++st_ky > pc.ky1) {
-                    st_ky = pc.ky0;
-                    ++st_cb;
-                }
-            }
+            load_tile_checked(p, rx, rw, st, lcol, true, ay, ax, abase, bbase, ra, rb);
+            st.advance(pc);
         };
-        auto store_split = [&](float *row, const float4 &v4) {
-            const f32x4 vv = {v4.x, v4.y, v4.z, v4.w};
-            const bf16x4 hi = __builtin_convertvector(vv, bf16x4);
-            const bf16x4 lo = __builtin_convertvector(vv - __builtin_convertvector(hi, f32x4), bf16x4);
-            __bf16 *r = reinterpret_cast<__bf16 *>(row);
-            *reinterpret_cast<bf16x4 *>(r + lcol) = hi;
-            *reinterpret_cast<bf16x4 *>(r + BK + lcol) = lo;
-        };
-        auto store_tile = [&]() {
-#pragma unroll
-            for (int j = 0; j < AV; ++j) {
-                if constexpr (MATH == MATH_BF16X3) store_split(&As[(lrow + 32 * j) * LDS_STRIDE], ra[j]);
-                else *reinterpret_cast<float4 *>(&As[(lrow + 32 * j) * LDS_STRIDE + lcol]) = ra[j];
-            }
-#pragma unroll
-            for (int j = 0; j < BV; ++j) {
-                if constexpr (MATH == MATH_BF16X3) store_split(&Bs[(lrow + 32 * j) * LDS_STRIDE], rb[j]);
-                else *reinterpret_cast<float4 *>(&Bs[(lrow + 32 * j) * LDS_STRIDE + lcol]) = rb[j];
-            }
-        };
-
+        auto store_tile = [&]() { fill_lds<MATH>(As, Bs, lrow, lcol, ra, rb); };
         f32x16 acc[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
+        clear_acc(acc);
+        // (the fragment pointers are formed at the use, like everything else that hangs on the thread id)
         auto compute_tile = [&]() {
-            if constexpr (MATH == MATH_BF16X3) {
-                const __bf16 *Ah = reinterpret_cast<const __bf16 *>(As + (wm * TM * 32 + (lane & 31)) * LDS_STRIDE) +
-                                   (lane >> 5) * 8;
-                const __bf16 *Bh = reinterpret_cast<const __bf16 *>(Bs + (wn * TN * 32 + (lane & 31)) * LDS_STRIDE) +
-                                   (lane >> 5) * 8;
-#pragma unroll
-                for (int sl = 0; sl < BK / 16; ++sl) {
-                    bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) {
-                        ah[i] = *reinterpret_cast<const bf16x8 *>(Ah + i * 32 * LDS_STRIDE * 2 + sl * 16);
-                        al[i] = *reinterpret_cast<const bf16x8 *>(Ah + i * 32 * LDS_STRIDE * 2 + BK + sl * 16);
-                    }
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        bh[j] = *reinterpret_cast<const bf16x8 *>(Bh + j * 32 * LDS_STRIDE * 2 + sl * 16);
-                        bl[j] = *reinterpret_cast<const bf16x8 *>(Bh + j * 32 * LDS_STRIDE * 2 + BK + sl * 16);
-                    }
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                        }
-                }
-                return;
-            }
-#pragma unroll
-            for (int kb = 0; kb < BK / 8; ++kb) {
-                float4 a[TM], b[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const float4 *>(Aw + i * 32 * LDS_STRIDE + kb * 8);
-#pragma unroll
-                for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const float4 *>(Bw + j * 32 * LDS_STRIDE + kb * 8);
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].x, b[j].x, acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].z, b[j].z, acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].w, b[j].w, acc[i][j], 0, 0, 0);
-                    }
-            }
+            mma_tile<TM, TN, MATH>(acc, As + (wm * TM * 32) * LDS_STRIDE + lds_fragment(lane),
+                                   Bs + (wn * TN * 32) * LDS_STRIDE + lds_fragment(lane));
         };
 
         // K loop over this segment (always at least one step)
@@ -737,10 +684,7 @@ __global__ __launch_bounds__(256) void conv_sk_kernel(const ConvParams p, const 
             __syncthreads();
         }
         compute_tile();
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) asm volatile("s_nop 15\n\ts_nop 7" : "+a"(acc[i][j]));
+        settle_acc(acc);
 
         const unsigned seg_first = u;
         u += (unsigned)(ks_end - ks_begin);
@@ -785,8 +729,8 @@ __global__ __launch_bounds__(256) void conv_sk_kernel(const ConvParams p, const 
         // accumulator tile (i, j) of this wave: its own registers for a whole tile; for a split tile the K-ordered
         // sum of every contributor's slab, this workgroup's own included (stored above) -- the same sum whoever
         // arrives last, and only one 32x32 tile of it is live at a time
-        auto tile_values = [&](int i, int j, const f32x16 &own) -> f32x16 {
-            if (pieces == 1) return own;
+        auto tile_values = [&](int i, int j) -> f32x16 {
+            if (pieces == 1) return acc[i][j];
             f32x16 t;
             for (int qq = 0; qq < pieces; ++qq) {
                 const unsigned vq = vfirst + (unsigned)qq;
@@ -804,71 +748,7 @@ __global__ __launch_bounds__(256) void conv_sk_kernel(const ConvParams p, const 
             }
             return t;
         };
-
-        if (finish) {
-            const int col = lane & 31, rsub = (lane >> 5) * 4;
-            int dy_, dx_;
-            if ((p.N & 3) == 0) {
-                __syncthreads();  // every wave is done with the last A/B tile
-                float *ep = lds + wave * (32 * LDS_STRIDE);
-                const int erow = lane >> 3, ecol = (lane & 7) * 4;
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    int pix[4];
-#pragma unroll
-                    for (int it = 0; it < 4; ++it) pix[it] = decode(r0 + (wm * TM + i) * 32 + erow + 8 * it, dy_, dx_);
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const int n = n0 + (wn * TN + j) * 32 + ecol;
-                        float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (p.bias && n < p.N) bias = *reinterpret_cast<const float4 *>(p.bias + n);
-                        const f32x16 tv = tile_values(i, j, acc[i][j]);
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) ep[((e & 3) + 8 * (e >> 2) + rsub) * LDS_STRIDE + col] = tv[e];
-                        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                        for (int it = 0; it < 4; ++it) {
-                            float4 vv = *reinterpret_cast<const float4 *>(&ep[(erow + 8 * it) * LDS_STRIDE + ecol]);
-                            if (pix[it] >= 0 && n < p.N) {
-                                const size_t o = (size_t)pix[it] * p.N + n;
-                                vv.x += bias.x; vv.y += bias.y; vv.z += bias.z; vv.w += bias.w;
-                                if (p.residual) {
-                                    const float4 rr = *reinterpret_cast<const float4 *>(p.residual + o);
-                                    vv.x += rr.x; vv.y += rr.y; vv.z += rr.z; vv.w += rr.w;
-                                }
-                                if (p.relu) {
-                                    vv.x = fmaxf(vv.x, 0.f); vv.y = fmaxf(vv.y, 0.f);
-                                    vv.z = fmaxf(vv.z, 0.f); vv.w = fmaxf(vv.w, 0.f);
-                                }
-                                *reinterpret_cast<float4 *>(p.y + o) = vv;
-                            }
-                        }
-                        __builtin_amdgcn_wave_barrier();
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const int n = n0 + (wn * TN + j) * 32 + col;
-                        const f32x16 tv = tile_values(i, j, acc[i][j]);
-                        if (n >= p.N) continue;
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) {
-                            const int pix = decode(r0 + (wm * TM + i) * 32 + rsub + (e & 3) + 8 * (e >> 2), dy_, dx_);
-                            if (pix < 0) continue;
-                            const size_t o = (size_t)pix * p.N + n;
-                            float vv = tv[e];
-                            if (p.bias) vv += p.bias[n];
-                            if (p.residual) vv += p.residual[o];
-                            if (p.relu) vv = fmaxf(vv, 0.f);
-                            p.y[o] = vv;
-                        }
-                    }
-                }
-            }
-        }
+        if (finish) store_output<TM, TN, false>(p, pc, lds, r0, n0, wm, wn, wave, lane, true, p.y, tile_values);
         __syncthreads();  // LDS (tiles, epilogue slices, flag) is reused by the next segment
     }
 }
@@ -922,13 +802,38 @@ void build_classes(ConvParams &p, int B, int BM, bool use_classes)
     for (int i = 0; i < p.ncls; ++i) p.mtiles_xcd += mpsr::ceil_div(p.cls[i].tiles, 8);
 }
 
+// What both schedules do first: the layer's pixel classes for BM-row tiles and its count of BN-wide N tiles.
+inline void plan_tiles(ConvParams &p, int B, int BM, int BN, bool use_classes)
+{
+    build_classes(p, B, BM, use_classes);
+    p.ntiles = mpsr::ceil_div(p.N, BN);
+}
+
+// The tile shapes, by their index in mpsr_debug_set_conv_tile: f gets the shape as compile-time constants.
+template <int BM_, int BN_, int WM_, int WN_>
+struct TileShape {
+    static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
+};
+
+template <class F>
+int with_tile(int sel, F &&f)
+{
+    switch (sel) {
+        case 0: return f(TileShape<128, 128, 2, 2>{});
+        case 1: return f(TileShape<128, 64, 2, 2>{});
+        case 2: return f(TileShape<64, 128, 2, 2>{});
+        case 3: return f(TileShape<64, 64, 2, 2>{});
+        case 5: return f(TileShape<96, 128, 1, 4>{});
+        default: return f(TileShape<128, 32, 4, 1>{});
+    }
+}
+
 std::atomic<int> g_plain_override{-1};  // 0: never use the PLAIN instantiation (tests / A-B), else whenever it applies
 
 template <int BM, int BN, int WM, int WN, int MATH = MATH_FP32, int DEPTH = 1>
 int launch(ConvParams &p, int B, bool use_classes, hipStream_t s)
 {
-    build_classes(p, B, BM, use_classes);
-    p.ntiles = mpsr::ceil_div(p.N, BN);
+    plan_tiles(p, B, BM, BN, use_classes);
     p.fd_ntiles = make_fastdiv(p.ntiles);
     p.fd_mtiles = make_fastdiv(p.mtiles_xcd);
     const long long blocks = 8LL * p.mtiles_xcd * p.ntiles * p.splits;
@@ -1017,8 +922,7 @@ template <int BM, int BN, int WM, int WN, int MATH = MATH_FP32>
 int launch_sk(ConvParams &p, int B, bool use_classes, int mode, bool counters_clean, hipStream_t s, bool &done)
 {
     done = false;
-    build_classes(p, B, BM, use_classes);
-    p.ntiles = mpsr::ceil_div(p.N, BN);
+    plan_tiles(p, B, BM, BN, use_classes);
     p.splits = 1;
     SkParams sk;
     unsigned long long U = 0, T = 0;
@@ -1305,19 +1209,12 @@ int conv2d(const float *x, int B, int H, int W, int C, const float *w, const flo
     if (sched < 0) sched = (split_k == 0 && ws && p.M <= 2048 && p.ksteps_total >= 128) ? 1 : 0;
     if (sched == 1 && split_k <= 1 && ws) {
         bool done = false;
-        int rc = MPSR_OK;
-#define MPSR_SK(BM_, BN_, WM_, WN_)                                                                               \
-    rc = math == MATH_BF16X3 ? launch_sk<BM_, BN_, WM_, WN_, MATH_BF16X3>(p, B, use_classes, sched, false, stream, done) \
-                             : launch_sk<BM_, BN_, WM_, WN_, MATH_FP32>(p, B, use_classes, sched, false, stream, done)
-        switch (sel) {
-            case 0: MPSR_SK(128, 128, 2, 2); break;
-            case 1: MPSR_SK(128, 64, 2, 2); break;
-            case 2: MPSR_SK(64, 128, 2, 2); break;
-            case 3: MPSR_SK(64, 64, 2, 2); break;
-            case 5: MPSR_SK(96, 128, 1, 4); break;
-            default: MPSR_SK(128, 32, 4, 1); break;
-        }
-#undef MPSR_SK
+        const int rc = with_tile(sel, [&](auto t) {
+            using T = decltype(t);
+            return math == MATH_BF16X3
+                       ? launch_sk<T::BM, T::BN, T::WM, T::WN, MATH_BF16X3>(p, B, use_classes, sched, false, stream, done)
+                       : launch_sk<T::BM, T::BN, T::WM, T::WN, MATH_FP32>(p, B, use_classes, sched, false, stream, done);
+        });
         if (rc) return rc;
         if (done) return MPSR_OK;
     }
@@ -1331,7 +1228,6 @@ int conv2d(const float *x, int B, int H, int W, int C, const float *w, const flo
             return fail(MPSR_ERR_WORKSPACE, "conv2d: split_k=%d needs %zu workspace floats, got %zu", p.splits,
                         (size_t)p.splits * p.M * N, ws_floats);
     }
-    int rc;
     // two staging register sets (loads two K steps ahead) pay on the atrous 3x3 layers of the trunk (block3 conv2:
     // 228 -> 213 us) and with the 96x128 tile at N = 256; elsewhere the lost occupancy costs as much as it buys
     int depth = g_depth_override.load();
@@ -1339,19 +1235,12 @@ int conv2d(const float *x, int B, int H, int W, int C, const float *w, const flo
     // 7 workgroups per CU (measured +2 % on block2 / block3 conv3 and conv1)
     const bool plain64 = sel == 3 && KH == 1 && KW == 1 && C % BK == 0 && p.ksteps_total >= 8 && math == MATH_FP32;
     if (depth < 0) depth = ((sel == 3 && use_classes) || (sel == 5 && N <= 256) || plain64) ? 2 : 1;
-#define MPSR_TILE(BM_, BN_, WM_, WN_)                                                                        \
-    rc = math == MATH_BF16X3 ? launch<BM_, BN_, WM_, WN_, MATH_BF16X3>(p, B, use_classes, stream)           \
-         : depth == 2        ? launch<BM_, BN_, WM_, WN_, MATH_FP32, 2>(p, B, use_classes, stream)          \
-                             : launch<BM_, BN_, WM_, WN_, MATH_FP32, 1>(p, B, use_classes, stream)
-    switch (sel) {
-        case 0: MPSR_TILE(128, 128, 2, 2); break;
-        case 1: MPSR_TILE(128, 64, 2, 2); break;
-        case 2: MPSR_TILE(64, 128, 2, 2); break;
-        case 3: MPSR_TILE(64, 64, 2, 2); break;
-        case 5: MPSR_TILE(96, 128, 1, 4); break;
-        default: MPSR_TILE(128, 32, 4, 1); break;
-    }
-#undef MPSR_TILE
+    const int rc = with_tile(sel, [&](auto t) {
+        using T = decltype(t);
+        return math == MATH_BF16X3 ? launch<T::BM, T::BN, T::WM, T::WN, MATH_BF16X3>(p, B, use_classes, stream)
+               : depth == 2        ? launch<T::BM, T::BN, T::WM, T::WN, MATH_FP32, 2>(p, B, use_classes, stream)
+                                   : launch<T::BM, T::BN, T::WM, T::WN, MATH_FP32, 1>(p, B, use_classes, stream);
+    });
     if (rc) return rc;
     if (p.splits > 1) {
         const long long MN = (long long)p.M * N;
@@ -1510,211 +1399,4 @@ extern "C" int mpsr_conv2d_relu_masked_f32(const float *x, int B, int H, int W, 
         return mpsr::conv3x3_winograd3(x, B, H, W, C, w, nullptr, 0, y, N, dilation, ws, ws_floats, s, mask);
     if (int rc = mpsr::conv2d(x, B, H, W, C, w, nullptr, nullptr, y, N, KH, KW, dilation, 0, 0, ws, ws_floats, s)) return rc;
     return mpsr_relu_grad(y, mask, y, (long long)B * H * W * N, stream);
-}
-
-// ------------------------------------------------------------------------------------------------ calibration
-// What this box's matrix pipes sustain in fp32: nothing but v_mfma_f32_32x32x2_f32 on `chains` independent
-// accumulators per wave (1 = one dependent chain, like a 32x32 wave tile; 4 = like a 64x64 wave tile).  MI355X boards
-// differ in sustained clock under this load by up to ~20 % (power capping), so bench.py and the tuning tools quote
-// kernel rates next to this figure measured in the same process, not only next to the 2.4 GHz datasheet peak.
-namespace {
-template <int CHAINS>
-__global__ __launch_bounds__(256) void mfma_peak_kernel(float *out, int iters, float a0, float b0)
-{
-    f32x16 acc[CHAINS];
-#pragma unroll
-    for (int c = 0; c < CHAINS; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[c][e] = 0.f;
-    float a = a0 + threadIdx.x * 1e-6f, b = b0;
-    for (int i = 0; i < iters; ++i) {
-#pragma unroll
-        for (int r = 0; r < 16 / CHAINS; ++r)
-#pragma unroll
-            for (int c = 0; c < CHAINS; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[c], 0, 0, 0);
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < CHAINS; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) s += acc[c][e];
-    if (s == 12345.678f) out[0] = s;  // keeps the chain live; never true for the inputs used
-}
-}  // namespace
-
-namespace {
-// The K loop's instruction mix without its memory traffic: per step 8 ds_read_b128 feeding 16 dependent MFMAs, waits
-// placed as hipcc places them in conv_igemm_kernel<64,64> (MODE 1), or reads issued but never waited for (MODE 0).
-template <int MODE>
-__global__ __launch_bounds__(256) void mfma_lds_kernel(float *out, int iters)
-{
-    __shared__ __attribute__((aligned(16))) float lds[128 * LDS_STRIDE];
-    for (int i = threadIdx.x; i < 128 * LDS_STRIDE; i += 256) lds[i] = 1e-3f * (float)(i & 15);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float *Aw = lds + ((wave >> 1) * 32 + (lane & 31)) * LDS_STRIDE + (lane >> 5) * 4;
-    const float *Bw = lds + (64 + (wave & 1) * 32 + (lane & 31)) * LDS_STRIDE + (lane >> 5) * 4;
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    f32x4 keep = {1.f, 1.f, 1.f, 1.f};
-    for (int i = 0; i < iters; ++i) {
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            f32x4 a = *reinterpret_cast<const f32x4 *>(Aw + kb * 8 + (i & 1) * 4);
-            f32x4 b = *reinterpret_cast<const f32x4 *>(Bw + kb * 8 + (i & 1) * 4);
-            if (MODE == 0) {
-                asm volatile("" ::"v"(a), "v"(b));
-                a = keep;
-                b = keep;
-            }
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-        }
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) s += acc[e];
-    if (s == 12345.678f) out[0] = s;
-}
-}  // namespace
-
-namespace {
-// One dependent MFMA chain per wave with NV independent vector-ALU instructions issued after every MFMA: does ordinary
-// VALU work of the resident waves take time away from the matrix pipe?  (tools/mfma_peak.py --valu)
-template <int NV, int KIND = 0>
-__global__ __launch_bounds__(256) void mfma_valu_kernel(float *out, int iters, float av, float bv)
-{
-    __shared__ __attribute__((aligned(16))) float buf[256 * 4 + 64];
-    buf[threadIdx.x * 4] = av;
-    __syncthreads();
-    const float *lp = buf + (threadIdx.x & 63) * 4;
-    __shared__ __attribute__((aligned(16))) float wbuf[256 * 4 + 2048];
-    const unsigned wp = (unsigned)(size_t)(wbuf + threadIdx.x), wp2 = (unsigned)(size_t)(wbuf + threadIdx.x * 2),
-                   wp4 = (unsigned)(size_t)(wbuf + threadIdx.x * 4);
-    __attribute__((ext_vector_type(2))) float w2 = {av, bv};
-    int sreg = iters;
-    f32x4 lv = {0.f, 0.f, 0.f, 0.f};
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    float v[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) v[e] = av * (float)(threadIdx.x + e);
-    for (int i = 0; i < iters; ++i) {
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-#pragma unroll
-            for (int q = 0; q < NV; ++q) {
-                if (KIND == 0) asm volatile("v_fma_f32 %0, %0, %1, %1" : "+v"(v[(u * NV + q) & 15]) : "v"(bv));
-                if (KIND == 1) asm volatile("s_add_u32 %0, %0, 1" : "+s"(sreg));
-                if (KIND == 2) asm volatile("ds_read_b128 %0, %1" : "=v"(lv) : "v"((unsigned)(size_t)lp) : "memory");
-                if (KIND == 3) asm volatile("s_nop 0");
-                // LDS stores of this thread's own slot (conflict-free): 4, 8, 16 bytes, and the paired 4-byte form
-                if (KIND == 4) asm volatile("ds_write_b32 %0, %1" ::"v"(wp), "v"(v[q & 15]) : "memory");
-                if (KIND == 5) asm volatile("ds_write_b64 %0, %1" ::"v"(wp2), "v"(w2) : "memory");
-                if (KIND == 6) asm volatile("ds_write_b128 %0, %1" ::"v"(wp4), "v"(lv) : "memory");
-                if (KIND == 7) asm volatile("ds_write2st64_b32 %0, %1, %2 offset1:4" ::"v"(wp), "v"(v[q & 15]), "v"(v[(q + 1) & 15]) : "memory");
-            }
-            if (KIND == 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) s += acc[e] + v[e];
-    s += lv.x + (float)sreg;
-    if (s == 12345.678f) out[0] = s;
-}
-}  // namespace
-
-namespace {
-__global__ __launch_bounds__(256) void empty_kernel(float *out, int spin)
-{
-    extern __shared__ float dyn[];
-    float v = 0.f;
-    for (int i = 0; i < spin; ++i) asm volatile("s_sleep 1");
-    if (out && threadIdx.x == 1000) out[0] = v + dyn[0];
-}
-}  // namespace
-
-// Workgroup dispatch rate: `blocks` workgroups of 256 threads with `lds_bytes` of LDS that do nothing (spin = 0) or
-// sleep for spin * 64 cycles.
-extern "C" int mpsr_debug_dispatch(float *out, int blocks, int lds_bytes, int spin, mpsr_stream_t stream)
-{
-    MPSR_REQUIRE(blocks > 0 && lds_bytes >= 0 && lds_bytes <= 64 * 1024, "dispatch: bad arguments");
-    hipLaunchKernelGGL(empty_kernel, dim3((unsigned)blocks), dim3(256), (size_t)lds_bytes, mpsr::as_stream(stream), out, spin);
-    MPSR_CHECK_LAUNCH("empty_kernel");
-    return MPSR_OK;
-}
-
-// kind 0: vector ALU, 1: scalar ALU, 2: LDS reads (ds_read_b128), 3: s_nop, 4-7: LDS stores (ds_write_b32 / _b64 /
-// _b128 / ds_write2st64_b32); nv = 1, 2 (stores only), 4 or 8 of them after every MFMA
-extern "C" int mpsr_debug_mfma_mix(float *out, int cus, int waves_per_simd, int nv, int kind, int iters,
-                                   mpsr_stream_t stream)
-{
-    MPSR_REQUIRE(out && cus > 0 && waves_per_simd >= 1 && waves_per_simd <= 8 && iters > 0 &&
-                     (nv == 4 || nv == 8 || ((nv == 1 || nv == 2) && kind >= 4)) && kind >= 0 && kind <= 7,
-                 "mfma_mix: bad arguments");
-    const dim3 grid((unsigned)(cus * waves_per_simd));
-    hipStream_t s = mpsr::as_stream(stream);
-#define MIX(NV_, K_) hipLaunchKernelGGL((mfma_valu_kernel<NV_, K_>), grid, dim3(256), 0, s, out, iters, 1.f, 1e-3f)
-    if (kind >= 4) {
-        if (nv == 1) { if (kind == 4) MIX(1, 4); else if (kind == 5) MIX(1, 5); else if (kind == 6) MIX(1, 6); else MIX(1, 7); }
-        else if (nv == 2) { if (kind == 4) MIX(2, 4); else if (kind == 5) MIX(2, 5); else if (kind == 6) MIX(2, 6); else MIX(2, 7); }
-        else if (nv == 4) { if (kind == 4) MIX(4, 4); else if (kind == 5) MIX(4, 5); else if (kind == 6) MIX(4, 6); else MIX(4, 7); }
-        else { if (kind == 4) MIX(8, 4); else if (kind == 5) MIX(8, 5); else if (kind == 6) MIX(8, 6); else MIX(8, 7); }
-    } else if (nv == 4) {
-        if (kind == 0) MIX(4, 0); else if (kind == 1) MIX(4, 1); else if (kind == 2) MIX(4, 2); else MIX(4, 3);
-    } else {
-        if (kind == 0) MIX(8, 0); else if (kind == 1) MIX(8, 1); else if (kind == 2) MIX(8, 2); else MIX(8, 3);
-    }
-#undef MIX
-    MPSR_CHECK_LAUNCH("mfma_valu_kernel");
-    return MPSR_OK;
-}
-
-extern "C" int mpsr_debug_mfma_valu(float *out, int cus, int waves_per_simd, int nv, int iters, mpsr_stream_t stream)
-{
-    MPSR_REQUIRE(out && cus > 0 && waves_per_simd >= 1 && waves_per_simd <= 8 && iters > 0, "mfma_valu: bad arguments");
-    const dim3 grid((unsigned)(cus * waves_per_simd));
-    hipStream_t s = mpsr::as_stream(stream);
-    switch (nv) {
-    case 0: hipLaunchKernelGGL(mfma_valu_kernel<0>, grid, dim3(256), 0, s, out, iters, 1.f, 1e-3f); break;
-    case 1: hipLaunchKernelGGL(mfma_valu_kernel<1>, grid, dim3(256), 0, s, out, iters, 1.f, 1e-3f); break;
-    case 2: hipLaunchKernelGGL(mfma_valu_kernel<2>, grid, dim3(256), 0, s, out, iters, 1.f, 1e-3f); break;
-    case 4: hipLaunchKernelGGL(mfma_valu_kernel<4>, grid, dim3(256), 0, s, out, iters, 1.f, 1e-3f); break;
-    case 6: hipLaunchKernelGGL(mfma_valu_kernel<6>, grid, dim3(256), 0, s, out, iters, 1.f, 1e-3f); break;
-    case 8: hipLaunchKernelGGL(mfma_valu_kernel<8>, grid, dim3(256), 0, s, out, iters, 1.f, 1e-3f); break;
-    case 12: hipLaunchKernelGGL(mfma_valu_kernel<12>, grid, dim3(256), 0, s, out, iters, 1.f, 1e-3f); break;
-    case 16: hipLaunchKernelGGL(mfma_valu_kernel<16>, grid, dim3(256), 0, s, out, iters, 1.f, 1e-3f); break;
-    default: return mpsr::fail(MPSR_ERR_INVALID_ARG, "mfma_valu: nv must be 0, 1, 2, 4, 6, 8, 12 or 16");
-    }
-    MPSR_CHECK_LAUNCH("mfma_valu_kernel");
-    return MPSR_OK;
-}
-
-extern "C" int mpsr_debug_mfma_lds(float *out, int cus, int waves_per_simd, int mode, int iters, mpsr_stream_t stream)
-{
-    MPSR_REQUIRE(out && cus > 0 && waves_per_simd >= 1 && waves_per_simd <= 8 && iters > 0, "mfma_lds: bad arguments");
-    const dim3 grid((unsigned)(cus * waves_per_simd));
-    if (mode == 0) hipLaunchKernelGGL(mfma_lds_kernel<0>, grid, dim3(256), 0, mpsr::as_stream(stream), out, iters);
-    else hipLaunchKernelGGL(mfma_lds_kernel<1>, grid, dim3(256), 0, mpsr::as_stream(stream), out, iters);
-    MPSR_CHECK_LAUNCH("mfma_lds_kernel");
-    return MPSR_OK;
-}
-
-// Launches `waves_per_simd` waves on every SIMD of `cus` CUs, each issuing iters * 16 MFMAs.  The caller times it
-// (FLOP = cus * 4 * waves_per_simd * iters * 16 * 4096).
-extern "C" int mpsr_debug_mfma_peak(float *out, int cus, int waves_per_simd, int chains, int iters, mpsr_stream_t stream)
-{
-    MPSR_REQUIRE(out && cus > 0 && waves_per_simd >= 1 && waves_per_simd <= 8 && iters > 0 && (chains == 1 || chains == 4),
-                 "mfma_peak: bad arguments");
-    const dim3 grid((unsigned)(cus * waves_per_simd));
-    if (chains == 1) hipLaunchKernelGGL(mfma_peak_kernel<1>, grid, dim3(256), 0, mpsr::as_stream(stream), out, iters, 1.f, 1e-3f);
-    else hipLaunchKernelGGL(mfma_peak_kernel<4>, grid, dim3(256), 0, mpsr::as_stream(stream), out, iters, 1.f, 1e-3f);
-    MPSR_CHECK_LAUNCH("mfma_peak_kernel");
-    return MPSR_OK;
 }

@@ -1180,6 +1180,43 @@ def test_conv2d_bf16x3_vs_fp64(case, tile, bf16x3):
     _close(got, ref, 4e-5, "bf16x3 conv %s tile %d" % (case, tile))
 
 
+SK_BF16X3_CASES = [
+    (2, 12, 12, 64, 256, 1, 1, True, True, True),     # 1x1 with residual; tiles split between workgroups
+    (2, 12, 12, 128, 128, 3, 2, True, False, True),   # border classes
+    (1, 9, 11, 36, 40, 3, 2, False, True, False),     # ragged M, N, C
+    (5, 1, 1, 96, 27, 1, 1, True, False, False),      # scalar epilogue; one tile summed from three slabs
+]
+assert all(c in CONV_CASES for c in SK_BF16X3_CASES)
+
+
+@pytest.mark.parametrize("groups", [-8, 3])
+@pytest.mark.parametrize("tile", [0, 3, 4, 5])
+@pytest.mark.parametrize("case", SK_BF16X3_CASES)
+def test_conv2d_stream_k_bf16x3_vs_fp64(case, tile, groups, bf16x3):
+    """The stream-K schedule in split-bfloat16 arithmetic (its own instantiations of the kernel): 8 workgroups and
+    3 per CU, within the 4e-5 of the one-tile bf16x3 test."""
+    from monopsr_amd import _lib
+    from monopsr_amd.core import device_net as dn
+    from monopsr_amd.core import weights as W
+    B, H, Wd, C, N, k, rate, has_bias, has_res, relu = case
+    rng = np.random.default_rng(hash(case) % (2 ** 31))
+    x = rng.standard_normal((B, H, Wd, C)).astype(np.float32)
+    w = (rng.standard_normal((k, k, C, N)) / np.sqrt(k * k * C)).astype(np.float32)
+    bias = rng.standard_normal(N).astype(np.float32) if has_bias else None
+    res = rng.standard_normal((B, H, Wd, N)).astype(np.float32) if has_res else None
+    ref = _conv_ref(x, w, bias, res, rate, relu)
+    w_ok, _ = W.fold_conv(w)
+    lib = _lib.lib()
+    lib.mpsr_debug_set_conv_tile(tile)
+    lib.mpsr_debug_set_conv_sched(1, groups)
+    try:
+        got = dn.conv2d(_dev(x), _dev(w_ok), _dev(bias) if has_bias else None, _dev(res) if has_res else None, k, k,
+                        rate, relu, split_k=0)
+    finally:
+        lib.mpsr_debug_set_conv_sched(-1, 0)
+    _close(got, ref, 4e-5, "stream-K bf16x3 conv %s tile %d groups %d" % (case, tile, groups))
+
+
 def test_network_drift_in_bf16x3_mode(bf16x3):
     """Whole instance path (full-width trunk, decoder, heads) in bf16x3 mode vs the fp32 CPU restatement: within
     2e-4 of tensor scale (measured 1e-5..4e-5), a fifth of the path's 1e-3 budget; fp32 mode: 1e-5."""
