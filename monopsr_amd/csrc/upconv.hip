@@ -11,10 +11,11 @@
 // the same 1/4 of the direct form's multiply-adds that F(4x4,3x3) on the upsampled map issues (a quarter of the pixels,
 // nine times the columns), but with no input / output transforms, no patch gathers, exact-fp32 GEMM error (1e-6 instead
 // of F(4x4)'s 1.5e-5), and the two resize launches (0.9 GB written and re-read per step) are gone.  Stage 2
-// (upconv_gather_kernel) is the 9-tap x 4-corner weighted sum above: one workgroup per (image, 8-channel block) rolls a
-// window of z rows through LDS and every thread sums 36 float4 for an output pixel's 4 channels -- LDS / vector-ALU work
-// on 1/9 of the GEMM's flops, reading z once and writing the layer's output once (channel-blocked for the F(4x4,3x3)
-// layer that follows, or NHWC).
+// (upconv_gather_kernel) is the 9-tap x 4-corner weighted sum above, as a horizontal pass per source row and a vertical
+// pass per output row (a[q][s] is a product of a row and a column weight): one workgroup per (image, 8-channel block)
+// rolls the source rows through LDS and a thread sums 6 float4 per pass item for 4 channels -- LDS / vector-ALU work on
+// 1/9 of the GEMM's flops, reading z once and writing the layer's output once (channel-blocked for the F(4x4,3x3) layer
+// that follows, or NHWC).
 //
 // Column order of z (ours to choose): j = (n / 8) * 72 + t * 8 + (n % 8) -- the nine taps of an 8-channel block are 288
 // contiguous bytes per source pixel.  The GEMM's weight matrix W'[j][c] = g[n][t][c] is a re-ordering of the filter
@@ -48,28 +49,36 @@ struct UpcParams {
     float *y;
     size_t part_stride;  // floats between the z parts (source pixels x 1152)
     int B, h, w, H, W, N, relu;
-    int RB, cap;         // output rows per band; source rows the LDS ring holds (>= the rows one band reaches)
+    int RB, cap, stg;    // output rows per band; source rows the Hrow ring holds (>= the rows one band reaches); z rows staged at once
     mpsr::FastDiv capdiv;  // r % cap by multiply-high (common.h)
     float hscale, wscale;
 };
 
-constexpr int kPf = 8;  // float4 registers per thread that carry source pixels on their way into LDS
+// float4 registers per thread that carry source pixels on their way into LDS (8 of them cost the kernel its fifth wave
+// per SIMD, i.e. the third workgroup per CU: 118 against 92 vector registers)
+constexpr int kPf = 4;
 std::atomic<int> g_upconv_band{0};  // mpsr_debug_set_upconv_band: output rows per band of the rolling window (0 = 8)
 
-// One workgroup per (8-channel block, image) walks the image in bands of RB output rows.  LDS is a ring of `cap` source
-// rows, [row % cap][column][tap][8 channels]; while a band is summed the source rows the NEXT band adds are already on
-// their way into registers, and move into the ring between two barriers -- every z row is read exactly once, and the
-// loads overlap the arithmetic inside the workgroup.  Two things measured on the way (r04): an integer division costs
-// hipcc ~35 vector instructions -- a version with index decodes per item / per load ran 1.5x longer than its arithmetic
-// -- so nothing in the loops divides: thread = (row of a pass, output column x, half of the 8 channels) with blockDim.x =
-// rpp * 2 W (a thread's column, its three tap columns, their LDS offsets and weights never change) and, as a loader,
-// (pixel group, 16-byte piece of a pixel's 288 bytes) walking pixels by addition.  And a load -> LDS-store loop waits for
-// every load in turn (12 round trips per workgroup were 3/4 of the first version's time): loads are issued kPf at a time
-// into registers, then stored.
-template <bool OUT_C8>
+// One workgroup per (8-channel block, image) walks the image in bands of RB output rows.  The 9-tap x 4-corner sum is
+// done in two passes (the bilinear weights are a product of a row and a column weight):
+//     Hrow[r][dy][x] = sum_dx sum_c wx[dx][c] z[r][col(x + dx, c)][(dy, dx)]      -- once per SOURCE row r: 6 LDS reads
+//     y[Y][x]        = bias + sum_dy sum_a wy[dy][a] Hrow[row(Y + dy, a)][dy][x]   -- once per output row:  6 LDS reads
+// (about h 18 + H 6 float4 reads per output column instead of H 36: the one-pass form sat at the LDS pipe's rate).  LDS is
+// a ring of `cap` Hrow rows, [row % cap][dy][column][half of the 8 channels], next to a staging area for the z rows a band
+// ADDS, [row][column][tap][8 channels], at most `stg` rows at a time: while a chunk of rows is summed the next chunk is
+// already on its way into registers, and moves into the staging area between two barriers -- every z row is read exactly
+// once and its horizontal pass runs once.  Two things measured on the way (r04): an integer division costs hipcc ~35
+// vector instructions, so nothing in the loops divides by a run-time value: thread = (row of a pass, output column x, half
+// of the 8 channels) with blockDim.x = rpp * 2 W (a thread's column, its three tap columns, their LDS offsets and weights
+// never change) and, as a loader, (pixel group, 16-byte piece of a pixel's 288 bytes) walking pixels by addition.  And a
+// load -> LDS-store loop waits for every load in turn: loads are issued kPf at a time into registers, then stored.
+// WIDE: a z row is wider than the prefetch registers (gather_geometry then stages ONE row per chunk): loaded in rounds,
+// nothing requested ahead.  (A template parameter: as a run-time branch it cost the kernel 8 vector registers, and with
+// them its fifth wave per SIMD.)
+template <bool OUT_C8, bool WIDE = false>
 __global__ __launch_bounds__(512) void upconv_gather_kernel(const UpcParams p)
 {
-    extern __shared__ __attribute__((aligned(16))) float4 src4[];
+    extern __shared__ __attribute__((aligned(16))) float4 lds4[];
     const int tid = threadIdx.x, nthr = blockDim.x;
     // Workgroup i runs on XCD i % 8 (speed only): XCD x takes the images x, x + 8, ... and the N / 8 channel blocks of an
     // image back to back.  A block's 288-byte slice of a pixel straddles cache lines it shares with its neighbours, and
@@ -82,17 +91,20 @@ __global__ __launch_bounds__(512) void upconv_gather_kernel(const UpcParams p)
     const int lpr = 2 * p.W, rpp = nthr / lpr;
     const int rr = tid / lpr, l = tid - rr * lpr, x = l >> 1, half = l & 1;
     const int n0 = blk * 8;
-    const int rowf4 = p.w * 18;  // float4 per source row
+    const int rowf4 = p.w * 18;  // float4 per staged z row
+    const int hrow4 = 3 * lpr;   // float4 per Hrow row
+    float4 *hr = lds4;                               // ring  [cap][3][W][2]
+    float4 *zs = lds4 + (size_t)p.cap * hrow4;       // stage [stg][w][18]
     auto slot = [&](int r) __attribute__((always_inline)) { return r - p.cap * mpsr::fdiv(r, p.capdiv); };  // r % cap
     const float *zp = p.z + (size_t)(blk >> 4) * p.part_stride + (size_t)(blk & 15) * 72 + (size_t)b * p.h * p.w * PART;
-    // loader role: piece `lpiece` of the pixels lgrp, lgrp + lgroups, ... of a block of whole rows (row-major, rows are
+    // loader role: piece `lpiece` of the pixels lgrp, lgrp + lgroups, ... of a chunk of whole rows (row-major, rows are
     // contiguous in z); (lrow0, lcol0) = this thread's first pixel, (drow, dcol) = the step of lgroups pixels
     const int lgroups = nthr / 18, lgrp = tid / 18, lpiece = tid - lgrp * 18;
     const bool loader = lgrp < lgroups;
     const int lrow0 = lgrp / p.w, lcol0 = lgrp - lrow0 * p.w;
     const int drow = lgroups / p.w, dcol = lgroups - drow * p.w;
     f32x4 pf[kPf];
-    // pixels [first, first + kPf * lgroups) of the block of rows that starts at row ra, npix pixels long
+    // pixels [first, first + kPf * lgroups) of the chunk of rows that starts at row ra, npix pixels long
     auto issue = [&](int ra, int npix, int first) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < kPf; ++j) {
@@ -103,13 +115,13 @@ __global__ __launch_bounds__(512) void upconv_gather_kernel(const UpcParams p)
             pf[j] = *reinterpret_cast<const f32x4 *>(live ? zp + ((size_t)ra * p.w + pix) * PART + 4 * lpiece : zp);
         }
     };
-    // (row, col) = position of this thread's pixel `first + lgrp` relative to row ra, kept by the caller
-    auto commit = [&](int ra, int npix, int first, int &row, int &col) __attribute__((always_inline)) {
+    // a chunk that fits the registers (npix <= kPf * lgroups), rows and columns walked by addition
+    auto commit = [&](int npix) __attribute__((always_inline)) {
+        int row = lrow0, col = lcol0;
 #pragma unroll
         for (int j = 0; j < kPf; ++j) {
-            const int pix = first + lgrp + j * lgroups;
-            if (loader && pix < npix)
-                reinterpret_cast<f32x4 *>(src4)[slot(ra + row) * rowf4 + col * 18 + lpiece] = pf[j];
+            const int pix = lgrp + j * lgroups;
+            if (loader && pix < npix) reinterpret_cast<f32x4 *>(zs)[row * rowf4 + col * 18 + lpiece] = pf[j];
             row += drow;
             col += dcol;
             if (col >= p.w) {
@@ -119,14 +131,24 @@ __global__ __launch_bounds__(512) void upconv_gather_kernel(const UpcParams p)
         }
     };
 
-    // source rows band k's taps (output rows k RB - 1 .. (k + 1) RB, clamped) interpolate between
-    auto band_rows = [&](int k, int &lo, int &hi) __attribute__((always_inline)) {
-        const int y0 = k * p.RB, yl = min(y0 + p.RB, p.H) - 1;
-        lo = (int)floorf((float)max(y0 - 1, 0) * p.hscale);
-        hi = min((int)floorf((float)min(yl + 1, p.H - 1) * p.hscale) + 1, p.h - 1);
+    // one round of a single staged row: pixel = column
+    auto commit_row = [&](int npix, int first) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < kPf; ++j) {
+            const int pix = first + lgrp + j * lgroups;
+            if (loader && pix < npix) reinterpret_cast<f32x4 *>(zs)[pix * 18 + lpiece] = pf[j];
+        }
     };
-    // tap column d - 1 of this thread's output column: LDS offsets of the two source columns and their weights (zero
-    // when the tap falls outside the upsampled image: the convolution's SAME padding)
+    constexpr bool wide = WIDE;
+
+    // last source row band k's taps (output rows k RB - 1 .. (k + 1) RB, clamped) interpolate from
+    auto band_hi = [&](int k) __attribute__((always_inline)) {
+        const int yl = min(k * p.RB + p.RB, p.H) - 1;
+        return min((int)floorf((float)min(yl + 1, p.H - 1) * p.hscale) + 1, p.h - 1);
+    };
+    // tap column d - 1 of this thread's output column: staging offsets of the two source columns (tap column and channel
+    // half folded in) and their weights (zero when the tap falls outside the upsampled image: the convolution's SAME
+    // padding)
     int co[3][2];
     float wx[3][2];
 #pragma unroll
@@ -136,34 +158,62 @@ __global__ __launch_bounds__(512) void upconv_gather_kernel(const UpcParams p)
         const float sx = (float)min(max(qx, 0), p.W - 1) * p.wscale;
         const int c0 = (int)floorf(sx), c1 = min(c0 + 1, p.w - 1);
         const float lx = sx - (float)c0;
-        co[d][0] = c0 * 18 + half;
-        co[d][1] = c1 * 18 + half;
+        co[d][0] = c0 * 18 + 2 * d + half;
+        co[d][1] = c1 * 18 + 2 * d + half;
         wx[d][0] = vx ? 1.f - lx : 0.f;
         wx[d][1] = vx ? lx : 0.f;
     }
     const float4 bias4 = p.bias ? *reinterpret_cast<const float4 *>(p.bias + n0 + 4 * half) : make_float4(0.f, 0.f, 0.f, 0.f);
 
     const int nbands = (p.H + p.RB - 1) / p.RB;
-    int lo, hi;
-    band_rows(0, lo, hi);
-    {  // the first band's rows
-        const int npix = (hi - lo + 1) * p.w;
-        int row = lrow0, col = lcol0;
-        for (int first = 0; first < npix; first += kPf * lgroups) {
-            issue(lo, npix, first);
-            commit(lo, npix, first, row, col);
-        }
-    }
-    __syncthreads();
-    // Every item stores its result at once.  (Holding a band's results in registers until the next band's rows are
-    // committed, so that the stores no longer share a wait with the prefetch loads, measured slower: 243 vs 176 us on
-    // conv2_1, the stores as one burst cost more than the loads they stopped draining -- DESIGN.md 4.1 (h).)
+    int have = -1;  // last source row whose Hrow is in the ring
+    int pn = wide ? 0 : min(band_hi(0) + 1, p.stg);  // rows of the chunk on its way: (have, have + pn]
+    if (pn > 0) issue(0, pn * p.w, 0);
+    // Every item stores its result at once.  (Holding a band's results in registers until the next rows are committed,
+    // so that the stores no longer share a wait with the prefetch loads, measured slower on the one-pass form: 243 vs
+    // 176 us on conv2_1 -- DESIGN.md 4.1 (h).)
     for (int k = 0; k < nbands; ++k) {
-        // rows the next band adds: (hi, nhi] -- at most kPf * lgroups pixels (gather_geometry)
-        int nlo = 0, nhi = hi;
-        if (k + 1 < nbands) band_rows(k + 1, nlo, nhi);
-        const int nnew = (nhi - hi) * p.w;
-        issue(hi + 1, nnew, 0);
+        const int bhi = band_hi(k);
+        while (have < bhi) {  // block-uniform
+            if (wide) {
+                for (int first = 0; first < p.w; first += kPf * lgroups) {
+                    issue(have + 1, p.w, first);
+                    commit_row(p.w, first);
+                }
+                pn = 1;
+            } else {
+                if (pn == 0) {  // (a band before this one added no rows: nothing was requested ahead)
+                    pn = min(bhi - have, p.stg);
+                    issue(have + 1, pn * p.w, 0);
+                }
+                commit(pn * p.w);
+            }
+            __syncthreads();  // the chunk is staged; every read of the ring for the previous band is done
+            const int c0 = have + 1, cn = pn;
+            have += pn;
+            // the chunk after this one: the rest of this band's rows, or the first rows the next band adds
+            const int tgt = (have < bhi || k + 1 == nbands) ? bhi : band_hi(k + 1);
+            pn = wide ? 0 : min(tgt - have, p.stg);
+            if (pn > 0) issue(have + 1, pn * p.w, 0);
+            // horizontal pass: item = (staged row, tap row) of this thread's column
+            for (int q = rr; q < 3 * cn; q += rpp) {
+                const int rl = q / 3, dy = q - 3 * rl;
+                const float4 *zr = zs + rl * rowf4 + 6 * dy;
+                f32x2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        const float4 v = zr[co[dx][c]];
+                        const f32x2 w2 = {wx[dx][c], wx[dx][c]};
+                        a01 = __builtin_elementwise_fma(w2, f32x2{v.x, v.y}, a01);
+                        a23 = __builtin_elementwise_fma(w2, f32x2{v.z, v.w}, a23);
+                    }
+                hr[(slot(c0 + rl) * 3 + dy) * lpr + l] = make_float4(a01.x, a01.y, a23.x, a23.y);
+            }
+            __syncthreads();  // the chunk's Hrow rows are in the ring; the staging area may be overwritten
+        }
+        // vertical pass: the band's output rows
         const int y0 = k * p.RB, ylast = min(y0 + p.RB, p.H) - 1;
         for (int y = y0 + rr; y <= ylast; y += rpp) {
             int ro[3][2];
@@ -175,8 +225,8 @@ __global__ __launch_bounds__(512) void upconv_gather_kernel(const UpcParams p)
                 const float sy = (float)min(max(qy, 0), p.H - 1) * p.hscale;
                 const int r0 = (int)floorf(sy), r1 = min(r0 + 1, p.h - 1);
                 const float ly = sy - (float)r0;
-                ro[d][0] = slot(r0) * rowf4;
-                ro[d][1] = slot(r1) * rowf4;
+                ro[d][0] = (slot(r0) * 3 + d) * lpr + l;
+                ro[d][1] = (slot(r1) * 3 + d) * lpr + l;
                 wy[d][0] = vy ? 1.f - ly : 0.f;
                 wy[d][1] = vy ? ly : 0.f;
             }
@@ -184,18 +234,11 @@ __global__ __launch_bounds__(512) void upconv_gather_kernel(const UpcParams p)
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    const int t2 = 2 * (dy * 3 + dx);
-#pragma unroll
-                    for (int a = 0; a < 2; ++a)
-#pragma unroll
-                        for (int c = 0; c < 2; ++c) {
-                            const float wgt = wy[dy][a] * wx[dx][c];
-                            const float4 v = src4[ro[dy][a] + co[dx][c] + t2];
-                            const f32x2 w2 = {wgt, wgt};
-                            a01 = __builtin_elementwise_fma(w2, f32x2{v.x, v.y}, a01);
-                            a23 = __builtin_elementwise_fma(w2, f32x2{v.z, v.w}, a23);
-                        }
+                for (int a = 0; a < 2; ++a) {
+                    const float4 v = hr[ro[dy][a]];
+                    const f32x2 w2 = {wy[dy][a], wy[dy][a]};
+                    a01 = __builtin_elementwise_fma(w2, f32x2{v.x, v.y}, a01);
+                    a23 = __builtin_elementwise_fma(w2, f32x2{v.z, v.w}, a23);
                 }
             float4 acc = make_float4(a01.x, a01.y, a23.x, a23.y);
             if (p.relu) {
@@ -208,14 +251,6 @@ __global__ __launch_bounds__(512) void upconv_gather_kernel(const UpcParams p)
                               : p.y + (((size_t)b * p.H + y) * p.W + x) * p.N + n0 + 4 * half;
             *reinterpret_cast<float4 *>(o) = acc;
         }
-        if (k + 1 == nbands) break;
-        __syncthreads();  // every thread has finished reading this band's rows: the ring may be overwritten
-        {
-            int row = lrow0, col = lcol0;
-            commit(hi + 1, nnew, 0, row, col);
-        }
-        __syncthreads();
-        hi = nhi;
     }
 }
 
@@ -454,25 +489,26 @@ __global__ __launch_bounds__(256) void upconv_fold_dw_kernel(const float *__rest
 }
 
 // Launch geometry of the gather: threads = rpp x 2 W (rows of a pass x (column, channel half)), rpp a power of two with
-// at most 512 threads; RB = output rows per band (8, or rpp if larger); cap = the ring's rows, a power of two >= the rows
-// any band reaches; the rows a band ADDS must fit the prefetch registers.  false: the map is too wide for this kernel.
-bool gather_geometry(int h, int w, int H, int W, float hscale, int *threads, int *RB, int *cap)
+// at most 512 threads; RB = output rows per band (8, or rpp if larger); cap = the Hrow ring's rows >= the rows any band
+// reaches; stage = the z rows staged at once (a band's new rows travel through the prefetch registers in chunks of that
+// many).  false: the map is too wide for this kernel.
+bool gather_geometry(int h, int w, int H, int W, float hscale, int *threads, int *RB, int *cap, int *stage)
 {
     if (2 * W > 512 || w < 1) return false;
     int rpp = 1;
     while (rpp * 2 <= 16 && rpp * 2 * 2 * W <= 512) rpp *= 2;
     const int nthr = rpp * 2 * W;
     if (nthr < 18) return false;
-    // a map whose source rows all fit a third of the LDS is ONE band (three workgroups per CU overlap each other's load
-    // and arithmetic phases); otherwise bands of 8 rows (or one pass) with the next band's rows prefetched
+    // a map whose source rows all fit a third of the LDS is ONE band (its Hrow rows all stay in the ring); otherwise bands
+    // of 8 rows (or one pass) with the next band's rows prefetched
     int rb = rpp > 8 ? rpp : 8;
     if (g_upconv_band.load() > 0) {  // (tuning knob: bands of this many rows, also where one band would do)
         rb = (g_upconv_band.load() + rpp - 1) / rpp * rpp;
     } else if ((size_t)h * w * 288 <= kGatherLdsBytes * 3 / 5) {
         rb = (H + rpp - 1) / rpp * rpp;
     }
-    // the kernel's own band arithmetic: the most rows a band reaches, the most a further band adds
-    int rows = 0, add = 0, prev_hi = -1;
+    // the kernel's own band arithmetic: the most rows a band reaches, the most a band adds (the first: all it reaches)
+    int rows = 0, add = 0, first = 0, prev_hi = -1;
     for (int k = 0; k * rb < H; ++k) {
         const int y0 = k * rb, yl = (y0 + rb < H ? y0 + rb : H) - 1;
         const int lo = (int)floorf((float)(y0 - 1 > 0 ? y0 - 1 : 0) * hscale);
@@ -480,14 +516,26 @@ bool gather_geometry(int h, int w, int H, int W, float hscale, int *threads, int
         if (hi > h - 1) hi = h - 1;
         if (hi - lo + 1 > rows) rows = hi - lo + 1;
         if (k > 0 && hi - prev_hi > add) add = hi - prev_hi;
+        if (k == 0) first = hi + 1;
         prev_hi = hi;
     }
-    if (add * w > kPf * (nthr / 18)) return false;  // the rows a band adds travel through the prefetch registers
-    const int c = rows;
-    if ((size_t)c * w * 288 > kGatherLdsBytes) return false;
+    // whole rows the prefetch registers carry (none: a wide row is staged alone, in rounds)
+    const int per_chunk = kPf * (nthr / 18) / w > 1 ? kPf * (nthr / 18) / w : 1;
+    // (the envelope stays inside the one-pass form's -- the decoder's plans are written against it: the rows a band
+    // reaches fit the LDS budget as z rows, the rows a band adds fit 8 float4 per loader thread.  What it loses: maps
+    // whose Hrow ring is too large, below -- an Hrow row outgrows its z row beyond a 3x upscale in width)
+    if ((size_t)rows * w * 288 > kGatherLdsBytes || add * w > 8 * (nthr / 18)) return false;
+    // three workgroups per CU (3/5 of the two-per-CU budget each) where the ring and one staged row leave room for it
+    const size_t ring = (size_t)rows * 3 * W * 32, zrow = (size_t)w * 288;
+    const size_t budget = ring + zrow <= kGatherLdsBytes * 3 / 5 ? kGatherLdsBytes * 3 / 5 : kGatherLdsBytes;
+    int stg = first > add ? first : add;
+    if (stg > per_chunk) stg = per_chunk;
+    while (stg > 1 && ring + stg * zrow > budget) --stg;
+    if (ring + stg * zrow > kGatherLdsBytes) return false;
     *threads = nthr;
     *RB = rb;
-    *cap = c;
+    *cap = rows;
+    *stage = stg;
     return true;
 }
 
@@ -502,9 +550,9 @@ namespace mpsr {
 
 static bool upconv_geometry_ok(int h, int w, int OH, int OW, int align_corners)
 {
-    int t, rb, cap;
+    int t, rb, cap, stg;
     const float hs = (align_corners && OH > 1) ? (float)(h - 1) / (float)(OH - 1) : (float)h / (float)OH;
-    return gather_geometry(h, w, OH, OW, hs, &t, &rb, &cap);
+    return gather_geometry(h, w, OH, OW, hs, &t, &rb, &cap, &stg);
 }
 
 size_t upconv_weight_floats(int C, int N) { return (size_t)9 * N * C; }
@@ -555,10 +603,10 @@ int conv3x3_upsampled(const float *x, int B, int h, int w, int C, int OH, int OW
     p.hscale = (align_corners && OH > 1) ? (float)(h - 1) / (float)(OH - 1) : (float)h / (float)OH;
     p.wscale = (align_corners && OW > 1) ? (float)(w - 1) / (float)(OW - 1) : (float)w / (float)OW;
     int threads = 0;
-    if (!gather_geometry(h, w, OH, OW, p.hscale, &threads, &p.RB, &p.cap))
+    if (!gather_geometry(h, w, OH, OW, p.hscale, &threads, &p.RB, &p.cap, &p.stg))
         return fail(MPSR_ERR_UNSUPPORTED, "conv3x3_upsampled: no gather geometry for a %dx%d -> %dx%d map", h, w, OH, OW);
     p.capdiv = make_fastdiv(p.cap);
-    const size_t lds = (size_t)p.cap * w * 288;
+    const size_t lds = (size_t)p.cap * 3 * OW * 32 + (size_t)p.stg * w * 288;  // Hrow ring | staged z rows
     // Images in chunks: GEMM of a chunk, then its gather -- with the chunk's z (images x h w x 9 N floats) no larger than
     // the Infinity Cache holds next to the other operands, the gather finds most of what the GEMM just wrote still on
     // the die instead of in HBM (g_upconv_chunk_mb; 0 = the whole batch at once)
@@ -583,15 +631,21 @@ int conv3x3_upsampled(const float *x, int B, int h, int w, int C, int OH, int OW
         p.y = y + (size_t)b0 * OH * OW * N;
         p.B = nb;
         const dim3 grid((unsigned)(8 * ceil_div(nb, 8) * (N / 8)));
+#define MPSR_UPC(...)                                                                                                 \
+    do {                                                                                                              \
+        MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(upconv_gather_kernel<__VA_ARGS__>),         \
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                    \
+        hipLaunchKernelGGL((upconv_gather_kernel<__VA_ARGS__>), grid, dim3(threads), lds, s, p);                      \
+    } while (0)
+        const bool wide = p.stg * w > kPf * (threads / 18);
         if (out_c8) {
-            MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(upconv_gather_kernel<true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(upconv_gather_kernel<true>, grid, dim3(threads), lds, s, p);
+            if (wide) MPSR_UPC(true, true);
+            else MPSR_UPC(true, false);
         } else {
-            MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(upconv_gather_kernel<false>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(upconv_gather_kernel<false>, grid, dim3(threads), lds, s, p);
+            if (wide) MPSR_UPC(false, true);
+            else MPSR_UPC(false, false);
         }
+#undef MPSR_UPC
         MPSR_CHECK_LAUNCH("upconv_gather_kernel");
     }
     return MPSR_OK;
