@@ -826,6 +826,38 @@ int mpsr_instance_xyz_crops_status(const float *depth, const unsigned char *inst
                                    int centroid_type, int rotate_view, float *xyz_local, float *xyz_global,
                                    float *valid, int *status, mpsr_stream_t stream);
 
+/* ---- Image noise (ABI 12): kitti_aug.apply_image_noise fused with a batch's frame gather and uint8 -> float32 ----
+ * What the reference's function (kitti_aug.py:124-170) does is not what its comments say: each of its five stages
+ * computes from the ORIGINAL image and overwrites the result, so only the last stage that fires is seen, and its
+ * "swap" of G and B, a tuple assignment on numpy views, copies B into G and leaves B.  The caller chooses:
+ *   MPSR_IMAGE_NOISE_REFERENCE  what the function does: the highest-numbered noise stage that fired applied to the
+ *                               original pixel; if none fired and the swap did, G := B; otherwise a copy.
+ *   MPSR_IMAGE_NOISE_COMPOSED   what it describes: from the original, every fired stage in order acts on the result of
+ *                               the one before; the swap exchanges G and B.
+ * A noise stage is np.uint8(np.clip(value + noise, 0, 255)): the sum in fp64, the clip, truncation toward zero.
+ * Stages (bit of `stages`): 0 swap, p < 0.10; 1 Gaussian per element, sigma 10, p < 0.40; 2 Gaussian per channel,
+ * sigma 8, p < 0.40; 3 brightness, one Gaussian, sigma 15, p < 0.40; 4 uniform per element in +-amount,
+ * amount = 10 u, p < 0.40.
+ * Random numbers as above (key, uniform, normal pair), counter = (c0, c1, the frame's index in the split file,
+ * (epoch << 4) | stream) with two more streams:
+ *   stream 2, per frame, c1 = 0: c0 = 0 -> random_values[0], [1] (words 0,1 and 2,3); c0 = 1 -> [2], [3];
+ *     c0 = 2 -> [4] and amount = 10 * u; c0 = 3 -> a normal pair, the channel offsets R, G (* 8.0);
+ *     c0 = 4 -> a normal pair, the channel offset B (* 8.0) and the brightness (* 15.0).
+ *   stream 3, per pair of elements, c0 = q for elements 2q, 2q + 1 of the frame flattened H W C, c1 = the stage's bit:
+ *     1 -> a normal pair * 10.0; 4 -> -amount + (2 * amount) * u for the call's two uniforms.
+ * So an image depends on (seed, epoch, the frame's index in the split file) alone.  Draws of a stage whose result is
+ * never seen are not made.
+ * frames (n_frames, h, w, 3) uint8; gather (nb) int32 picks the frames, in any order and with repeats; frame_index (nb)
+ * int32 is each gathered frame's RNG coordinate.  out (nb, h, w, 3) float32 holds the integers 0 .. 255; stages (nb)
+ * int32; params (nb, 5) fp64: amount, the channel offsets R, G, B, the brightness, drawn whether their stage fired or
+ * not.  h * w * 3 < 2^31 - 8.
+ * THE CALLER MUST GUARANTEE 0 <= gather < n_frames: the array is on the device; a value out of range is read as
+ * frame 0.  DESIGN.md section 7.4. */
+enum { MPSR_IMAGE_NOISE_REFERENCE = 1, MPSR_IMAGE_NOISE_COMPOSED = 2 };
+int mpsr_image_noise(const unsigned char *frames, int n_frames, int h, int w, const int *gather,
+                     const int *frame_index, int nb, unsigned long long seed, int epoch, int mode, float *out,
+                     int *stages, double *params, mpsr_stream_t stream);
+
 /* ---- Evaluation on 2-D detections (ABI 11): MSCNN merging and the evaluator's detection rows ----
  * DESIGN.md section 7.5. */
 

@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MPSR_LIB_PATH: development knob for A/B-ing two builds of the library inside one GPU session
 LIB_PATH = os.environ.get("MPSR_LIB_PATH") or os.path.join(_HERE, "libmonopsr_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _lib = None
 
@@ -202,6 +202,7 @@ SIGNATURES = {
                                 c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
     "mpsr_jitter_boxes_2d": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_uint64, c_i, ctypes.c_double, c_i, c_i,
                                    c_f, c_f, c_f, c_f, c_f, c_f]),
+    "mpsr_image_noise": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f, c_i, ctypes.c_uint64, c_i, c_i, c_f, c_f, c_f, c_f]),
     "mpsr_instance_xyz_crops_status": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i,
                                              c_i, c_f, c_f, c_f, c_f, c_f]),
     "mpsr_merge_detections": (c_i, [c_f, c_f, c_f, ctypes.c_longlong, c_f, c_f, c_f, ctypes.c_longlong, c_i,

@@ -8,6 +8,10 @@
 //   uniform = ((w0 >> 5) * 2^26 + (w1 >> 6)) / 2^53 from two words; a pair of normals by Box-Muller in fp64 from
 //             (1 - u0, u1); one Philox call gives one pair.
 // Built with -ffp-contract=off: every product and sum is rounded as tests/jitter_restatement.py rounds it.
+//
+// Image noise (kitti_aug.apply_image_noise, kitti_aug.py:124-170) of a batch's frames, fused with their gather and
+// their conversion to float32: stream 2 holds a frame's own draws, stream 3 its per-element ones (mpsr_image_noise
+// in include/monopsr_hip.h gives the counters; tests/image_noise_restatement.py restates the arithmetic).
 #include "common.h"
 
 #include <cmath>
@@ -15,7 +19,7 @@
 namespace {
 
 constexpr int kThreads = 64;
-constexpr unsigned kStreamOversample = 0u, kStreamJitter = 1u;
+constexpr unsigned kStreamOversample = 0u, kStreamJitter = 1u, kStreamImageFrame = 2u, kStreamImageElement = 3u;
 
 struct Words {
     unsigned w[4];
@@ -168,6 +172,158 @@ __global__ void __launch_bounds__(kThreads) jitter_boxes_kernel(
     out_view[t] = (float)atan2(((double)centre - p00_p02[2 * t + 1]) / p00_p02[2 * t], 1.0);
 }
 
+// ---- image noise
+
+constexpr int kNoiseThreads = 256;  // lanes of a block
+constexpr int kNoiseQuads = 8;      // quads (4 consecutive elements) per lane: a wave makes the frame's own draws once
+enum { kBitSwap = 0, kBitGaussian = 1, kBitChannel = 2, kBitBrightness = 3, kBitUniform = 4 };
+
+// np.uint8(np.clip(value + noise, 0.0, 255.0)): fp64 sum, clip, truncation toward zero
+__device__ __forceinline__ int add_clip_truncate(int value, double noise)
+{
+    return (int)fmin(fmax((double)value + noise, 0.0), 255.0);
+}
+
+// One block handles kNoiseThreads * kNoiseQuads quads of one gathered frame.  A quad starts at the frame's element
+// 4 t - shift, shift = 0 or 2 chosen per frame so that the quad's 16 output bytes are aligned whenever the frame's
+// output base is even (in elements); a quad therefore always covers two whole Philox pairs (2q, 2q + 1).  Quads that
+// hang over either end of the frame, frames whose output base is odd, and frames that exchange channels go element by
+// element.  Everything that selects a path is the same for all lanes of a frame.
+__global__ void __launch_bounds__(kNoiseThreads) image_noise_kernel(
+    const unsigned char *__restrict__ frames, int n_frames, int n, const int *__restrict__ gather,
+    const int *__restrict__ frame_index, int blocks_per_frame, unsigned k0, unsigned k1, unsigned epoch, int mode,
+    float *__restrict__ out, int *__restrict__ stages, double *__restrict__ params)
+{
+    const int k = (int)(blockIdx.x / (unsigned)blocks_per_frame);
+    const int chunk = (int)(blockIdx.x - (unsigned)k * (unsigned)blocks_per_frame);
+    int f = gather[k];
+    // (as in sample_slots_kernel: the indices are on the device; one out of range is read as frame 0)
+    if (f < 0 || f >= n_frames) f = 0;
+    const unsigned i = (unsigned)frame_index[k];
+
+    // the frame's own draws
+    const unsigned ef = (epoch << 4) | kStreamImageFrame, ee = (epoch << 4) | kStreamImageElement;
+    Words p = philox4x32_10(0u, 0u, i, ef, k0, k1);
+    int fired = (uniform53(p.w[0], p.w[1]) < 0.10) << kBitSwap | (uniform53(p.w[2], p.w[3]) < 0.40) << kBitGaussian;
+    p = philox4x32_10(1u, 0u, i, ef, k0, k1);
+    fired |= (uniform53(p.w[0], p.w[1]) < 0.40) << kBitChannel | (uniform53(p.w[2], p.w[3]) < 0.40) << kBitBrightness;
+    p = philox4x32_10(2u, 0u, i, ef, k0, k1);
+    fired |= (uniform53(p.w[0], p.w[1]) < 0.40) << kBitUniform;
+    const double amount = 10.0 * uniform53(p.w[2], p.w[3]);
+    double ch_r = 0.0, ch_g = 0.0, ch_b = 0.0, brightness = 0.0;
+    const bool reports = chunk == 0;
+    if (reports || (fired & (1 << kBitChannel | 1 << kBitBrightness))) {
+        double za, zb, zc, zd;
+        normal_pair(3u, 0u, i, ef, k0, k1, za, zb);
+        normal_pair(4u, 0u, i, ef, k0, k1, zc, zd);
+        ch_r = za * 8.0;
+        ch_g = zb * 8.0;
+        ch_b = zc * 8.0;
+        brightness = zd * 15.0;
+    }
+    if (reports && threadIdx.x == 0) {
+        stages[k] = fired;
+        params[5 * k] = amount;
+        params[5 * k + 1] = ch_r;
+        params[5 * k + 2] = ch_g;
+        params[5 * k + 3] = ch_b;
+        params[5 * k + 4] = brightness;
+    }
+
+    // the stages whose result is seen: in the reference's arithmetic the last noise stage alone (or none)
+    const int noise_bits = fired >> 1;
+    int first_stage = 1, last_stage = noise_bits ? 32 - __clz(noise_bits) : 0;
+    if (mode == MPSR_IMAGE_NOISE_REFERENCE) first_stage = last_stage;
+    // the exchange as a source offset per channel: G := B alone (what the tuple assignment on views does) or G <-> B
+    int from_g = 0, from_b = 0;
+    if (mode == MPSR_IMAGE_NOISE_REFERENCE) {
+        if (fired == 1 << kBitSwap) from_g = 1;
+    } else if (fired & (1 << kBitSwap)) {
+        from_g = 1;
+        from_b = -1;
+    }
+    const bool exchanges = from_g != 0;
+
+    const long long in_base = (long long)f * n, out_base = (long long)k * n;
+    const unsigned char *__restrict__ src = frames + in_base;
+    float *__restrict__ dst = out + out_base;
+    // (the pointers' own alignment counts too: a caller may pass a view that starts inside an allocation)
+    const int out_mis = (int)(((long long)(reinterpret_cast<size_t>(out) >> 2) + out_base) & 3);
+    const int shift = out_mis == 2 ? 2 : 0;
+    const bool wide_store = !(out_mis & 1);
+    const int in_mis = (int)(((long long)(reinterpret_cast<size_t>(frames) & 3) + in_base - shift) & 3);
+    const long long n_quads = ((long long)n + shift + 3) >> 2;
+
+    for (int u = 0; u < kNoiseQuads; ++u) {
+        const long long t = ((long long)chunk * kNoiseQuads + u) * kNoiseThreads + threadIdx.x;
+        if (t >= n_quads) break;
+        const long long e0 = 4 * t - shift;  // even; -2 for the first quad of a shifted frame
+        const bool whole = e0 >= 0 && e0 + 3 < n;
+        const int c0 = (int)((e0 + 3) % 3);  // the channel of element e0
+        int v[4] = {0, 0, 0, 0};
+        if (whole && !exchanges) {
+            if (in_mis == 0) {
+                const unsigned x = *reinterpret_cast<const unsigned *>(src + e0);
+                v[0] = x & 255u;
+                v[1] = (x >> 8) & 255u;
+                v[2] = (x >> 16) & 255u;
+                v[3] = x >> 24;
+            } else if (in_mis == 2) {
+                const unsigned lo = *reinterpret_cast<const unsigned short *>(src + e0);
+                const unsigned hi = *reinterpret_cast<const unsigned short *>(src + e0 + 2);
+                v[0] = lo & 255u;
+                v[1] = lo >> 8;
+                v[2] = hi & 255u;
+                v[3] = hi >> 8;
+            } else {
+                for (int j = 0; j < 4; ++j) v[j] = src[e0 + j];
+            }
+        } else {
+            for (int j = 0; j < 4; ++j) {
+                const long long e = e0 + j;
+                int c = c0 + j;
+                if (c >= 3) c -= 3;
+                // (a G or B element always has its partner inside the frame: n is a multiple of 3)
+                if (e >= 0 && e < n) v[j] = src[e + (c == 1 ? from_g : c == 2 ? from_b : 0)];
+            }
+        }
+        for (int s = first_stage; s >= 1 && s <= last_stage; ++s) {
+            if (!((fired >> s) & 1)) continue;
+            double nz[4];
+            if (s == kBitGaussian) {
+                for (int h = 0; h < 2; ++h) {
+                    double za, zb;
+                    normal_pair((unsigned)(e0 >> 1) + (unsigned)h, (unsigned)kBitGaussian, i, ee, k0, k1, za, zb);
+                    nz[2 * h] = za * 10.0;
+                    nz[2 * h + 1] = zb * 10.0;
+                }
+            } else if (s == kBitChannel) {
+                for (int j = 0; j < 4; ++j) {
+                    int c = c0 + j;
+                    if (c >= 3) c -= 3;
+                    nz[j] = c == 0 ? ch_r : c == 1 ? ch_g : ch_b;
+                }
+            } else if (s == kBitBrightness) {
+                for (int j = 0; j < 4; ++j) nz[j] = brightness;
+            } else {
+                for (int h = 0; h < 2; ++h) {
+                    const Words d = philox4x32_10((unsigned)(e0 >> 1) + (unsigned)h, (unsigned)kBitUniform, i, ee, k0,
+                                                  k1);
+                    nz[2 * h] = -amount + (2.0 * amount) * uniform53(d.w[0], d.w[1]);
+                    nz[2 * h + 1] = -amount + (2.0 * amount) * uniform53(d.w[2], d.w[3]);
+                }
+            }
+            for (int j = 0; j < 4; ++j) v[j] = add_clip_truncate(v[j], nz[j]);
+        }
+        if (whole && wide_store) {
+            *reinterpret_cast<float4 *>(dst + e0) = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+        } else {
+            for (int j = 0; j < 4; ++j)
+                if (e0 + j >= 0 && e0 + j < n) dst[e0 + j] = (float)v[j];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int mpsr_sample_slots(const int *slot_frame, const int *slot_s, int n, const int *num_objs,
@@ -217,5 +373,29 @@ extern "C" int mpsr_jitter_boxes_2d(const double *boxes_xyxy, const int *jitter_
         (unsigned)(seed >> 32), (unsigned)epoch, iou_threshold_min, max_trials, write_unjittered != 0, out_xyxy,
         out_boxes_2d, out_boxes_2d_norm, out_view_angs, out_trials);
     MPSR_CHECK_LAUNCH("jitter_boxes_kernel");
+    return MPSR_OK;
+}
+
+extern "C" int mpsr_image_noise(const unsigned char *frames, int n_frames, int h, int w, const int *gather,
+                                const int *frame_index, int nb, unsigned long long seed, int epoch, int mode,
+                                float *out, int *stages, double *params, mpsr_stream_t stream)
+{
+    MPSR_REQUIRE(n_frames >= 1 && h >= 1 && w >= 1 && nb >= 1, "image_noise: n_frames %d, h %d, w %d, nb %d (all >= 1)",
+                 n_frames, h, w, nb);
+    MPSR_REQUIRE((long long)h * w * 3 < (1LL << 31) - 8, "image_noise: a frame of %d x %d x 3 elements (< 2^31)", h, w);
+    MPSR_REQUIRE(epoch >= 0 && epoch < (1 << 28), "image_noise: epoch %d not in [0, 2^28)", epoch);
+    MPSR_REQUIRE(mode == MPSR_IMAGE_NOISE_REFERENCE || mode == MPSR_IMAGE_NOISE_COMPOSED,
+                 "image_noise: unknown mode %d", mode);
+    MPSR_REQUIRE(frames && gather && frame_index && out && stages && params, "image_noise: a pointer is null");
+    const int n = h * w * 3;
+    const long long per_block = (long long)kNoiseThreads * kNoiseQuads;
+    // (n + 2 + 3) / 4 quads at most: a frame whose output base is 2 mod 4 starts two elements early
+    const long long blocks_per_frame = ((((long long)n + 5) >> 2) + per_block - 1) / per_block;
+    MPSR_REQUIRE(blocks_per_frame * nb < (1LL << 31), "image_noise: %d frames of %d x %d need too many blocks", nb, h,
+                 w);
+    image_noise_kernel<<<(unsigned)(blocks_per_frame * nb), kNoiseThreads, 0, mpsr::as_stream(stream)>>>(
+        frames, n_frames, n, gather, frame_index, (int)blocks_per_frame, (unsigned)(seed & 0xffffffffull),
+        (unsigned)(seed >> 32), (unsigned)epoch, mode, out, stages, params);
+    MPSR_CHECK_LAUNCH("image_noise_kernel");
     return MPSR_OK;
 }

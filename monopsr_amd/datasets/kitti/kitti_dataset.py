@@ -184,13 +184,20 @@ class KittiDataset:
 
     dataset_config holds the reference's keys (configs/monopsr_model_000.yaml): dataset_dir, data_split,
     data_split_dir, num_boxes, classes, oversample, num_alpha_bins, alpha_bin_overlap, obj_filter_config,
-    aug_config.{use_image_aug, box_jitter_type}, use_mscnn_detections, depth_version, instance_version.  Depth maps
-    are read from <data_split_dir>/depth_2_<depth_version>/<name>.png and instance images from
+    aug_config.{use_image_aug, image_noise, box_jitter_type}, use_mscnn_detections, depth_version, instance_version.
+    Depth maps are read from <data_split_dir>/depth_2_<depth_version>/<name>.png and instance images from
     <data_split_dir>/instance_2_<instance_version>/<name>.png unless depth_dir / instance_dir name other directories.
 
     Frames that keep no label are left out of sample_list and counted in num_skipped (the reference returns None for
     them and its model draws again).  A frame's sample depends on (seed, epoch, the frame's index in the split file)
     only.  Unsupported recipes raise ValueError naming the option; see DESIGN.md section 7.4 for what is kept.
+
+    aug_config.use_image_aug: True (the reference's apply_image_noise on every 'train' frame) needs image_noise (the
+    argument, or aug_config.image_noise): 'reference' for what that function does (only the last stage that fires is
+    seen, and its swap copies B into G) or 'composed' for what it describes (the fired stages one after the other, a
+    true exchange of G and B).  rgb_image is then made by one mpsr_image_noise launch per image size and each sample
+    gains image_noise_stages (an int32 scalar on the device, bit k = kitti_aug.IMAGE_NOISE_STAGES[k] fired).  'val'
+    and 'test' never add noise.
 
     The two evaluation recipes need mscnn_label_dir (the argument, or the config key of that name): the directory of
     MSCNN detections in KITTI label format, one file per frame of the split.  'val' with use_mscnn_detections merges
@@ -200,7 +207,7 @@ class KittiDataset:
 
     def __init__(self, dataset_config, train_val_test, device=None, seed=0, max_resident_bytes=None, depth_dir=None,
                  instance_dir=None, map_roi_size=(48, 48), centroid_type=None, rotate_view=True, log=None,
-                 mscnn_label_dir=None):
+                 mscnn_label_dir=None, image_noise=None):
         self.dataset_config = dataset_config
         self.train_val_test = train_val_test
         self.seed = int(seed)
@@ -219,6 +226,7 @@ class KittiDataset:
         self.aug_config = _cfg(dataset_config, 'aug_config')
         self.box_jitter_type = _cfg(self.aug_config, 'box_jitter_type')
         self.use_image_aug = bool(_cfg(self.aug_config, 'use_image_aug', False))
+        self.image_noise = image_noise if image_noise is not None else _cfg(self.aug_config, 'image_noise')
         self.depth_version = _cfg(dataset_config, 'depth_version', 'multiscale')
         self.instance_version = _cfg(dataset_config, 'instance_version', 'depth_2_multiscale')
         self.iou_threshold_min = 0.7  # kitti_dataset.py:327-349
@@ -278,9 +286,17 @@ class KittiDataset:
             raise ValueError("use_mscnn_detections = True in 'val' mode merges MSCNN boxes into the labels: give "
                              "mscnn_label_dir, or set it to False to validate on KITTI's boxes")
         self.jitter_mode = 0
+        self.image_noise_mode = 0  # MPSR_IMAGE_NOISE_*; 0: the frames are gathered and converted as they are
         if self.train_val_test == 'train':
             if self.use_image_aug:
-                raise ValueError('aug_config.use_image_aug = True (image noise) is not built')
+                image_noise = getattr(self, 'image_noise', None)
+                if image_noise is None:
+                    raise ValueError(
+                        "aug_config.use_image_aug = True needs image_noise: the reference's apply_image_noise does not "
+                        "do what it describes, so choose 'reference' (what it does: only the last stage that fires is "
+                        "seen, and its swap copies B into G) or 'composed' (what it describes: the fired stages act "
+                        "one after the other, and the swap exchanges G and B)")
+                self.image_noise_mode = kitti_aug.image_noise_mode(image_noise)
             if self.box_jitter_type == 'oversample_gt':
                 raise ValueError("aug_config.box_jitter_type = 'oversample_gt' is not built")
             if self.box_jitter_type not in BOX_JITTER_TYPES:
@@ -490,8 +506,8 @@ class KittiDataset:
 
     def next_batch(self, batch_size, shuffle):
         """The next batch_size samples: a list of dicts with the keys of build_training_sample plus sample_name,
-        num_objs, oversample_indices and jitter_trials.  The batch that finishes an epoch takes its remaining samples
-        from the next one (kitti_dataset.py:504-556)."""
+        num_objs, oversample_indices and jitter_trials (and image_noise_stages with use_image_aug).  The batch that
+        finishes an epoch takes its remaining samples from the next one (kitti_dataset.py:504-556)."""
         samples = []
         for frames, epoch in self._epochs.next(batch_size, shuffle):
             samples.extend(self._build(frames, epoch))
@@ -577,6 +593,11 @@ class KittiDataset:
                 glob = torch.empty((n, roi_h, roi_w, 3), dtype=f32, device=dev)
                 valid = torch.empty((n, roi_h, roi_w, 1), dtype=f32, device=dev)
             rgb = [None] * nb
+            noise_stages = None
+            if self.image_noise_mode:
+                noise_stages = torch.empty(nb, dtype=i32, device=dev)
+                noise_params = torch.empty((nb, 5), dtype=torch.float64, device=dev)
+                batch_local32, batch_split = meta[2 * n + nb:], self._split_index.index_select(0, batch_frames)
             cam_p = self._cam_p.index_select(0, batch_frames)
             groups = self._group_host[sorted_frames]
             k0 = 0
@@ -594,7 +615,15 @@ class KittiDataset:
                         instance_utils._CENTROID_TYPES[self.centroid_type], int(self.rotate_view),
                         _lib.ptr(local[a:b]), _lib.ptr(glob[a:b]), _lib.ptr(valid[a:b]), _lib.ptr(self._status),
                         stream))
-                images = g.rgb.index_select(0, batch_local[k0:k1]).float()
+                if self.image_noise_mode:
+                    images = torch.empty((k1 - k0,) + g.shape + (3,), dtype=f32, device=dev)
+                    _lib.check(L.mpsr_image_noise(
+                        _lib.ptr(g.rgb), len(g.frames), g.shape[0], g.shape[1], _lib.ptr(batch_local32[k0:k1]),
+                        _lib.ptr(batch_split[k0:k1]), k1 - k0, self.seed & 0xFFFFFFFFFFFFFFFF, int(epoch),
+                        self.image_noise_mode, _lib.ptr(images), _lib.ptr(noise_stages[k0:k1]),
+                        _lib.ptr(noise_params[k0:k1]), stream))
+                else:
+                    images = g.rgb.index_select(0, batch_local[k0:k1]).float()
                 for k in range(k0, k1):
                     rgb[k] = images[k - k0]
                 k0 = k1
@@ -610,5 +639,7 @@ class KittiDataset:
                               gt_inst_xyz_maps_global=glob[a:b], gt_valid_mask_maps=valid[a:b],
                               sample_name=frame['name'], num_objs=frame['num_objs'],
                               oversample_indices=over_idx[a:b], jitter_trials=trials[a:b])
+                if noise_stages is not None:
+                    sample['image_noise_stages'] = noise_stages[k]
             samples[order[k]] = sample
         return samples

@@ -4,7 +4,9 @@
   (b) KittiDataset.next_batch at batch sizes 1 and 8 with box_jitter_type 'oversample': the split resident on the card.
 
 Each window runs for at least --seconds after a warm-up, with a device synchronise after every batch.  Also printed:
-the load time and resident_bytes.  --kernels-only runs batches alone, for
+the load time and resident_bytes.  --image-aug reference|composed turns aug_config.use_image_aug on for (b): the
+frames are then gathered, noised and converted by one mpsr_image_noise launch per batch.  --kernels-only runs batches
+alone, for
     rocprofv3 --kernel-trace --stats -- python tools/dataset_bench.py --kernels-only
 Numbers: DESIGN.md section 7.4.
 """
@@ -65,11 +67,12 @@ def make_split(top, n_frames, seed=0):
     return names
 
 
-def config(top, jitter='oversample'):
+def config(top, jitter='oversample', image_aug=None):
     return ConfigObj(dict(dataset_dir=top, data_split='train', data_split_dir='training', num_boxes=32, classes=['Car'],
                           oversample=True, num_alpha_bins=12, alpha_bin_overlap=0.0, use_mscnn_detections=True,
                           obj_filter_config=dict(kitti_dataset.DEFAULT_OBJ_FILTER),
-                          aug_config=dict(use_image_aug=False, box_jitter_type=jitter), depth_version='multiscale',
+                          aug_config=dict(use_image_aug=image_aug is not None, image_noise=image_aug,
+                                          box_jitter_type=jitter), depth_version='multiscale',
                           instance_version='depth_2_multiscale'))
 
 
@@ -92,6 +95,8 @@ def main(argv=None):
     p.add_argument('--frames', type=int, default=256)
     p.add_argument('--seconds', type=float, default=1.0, help='length of a timing window (default 1 s)')
     p.add_argument('--kernels-only', action='store_true', help='50 batches of 8 and nothing else (for rocprofv3)')
+    p.add_argument('--image-aug', choices=('reference', 'composed'), default=None,
+                   help="aug_config.use_image_aug with this image_noise (default: off)")
     a = p.parse_args(argv)
     if a.frames < 8:
         p.error('--frames must be >= 8')
@@ -100,7 +105,7 @@ def main(argv=None):
         names = make_split(top, 32 if a.kernels_only else a.frames)
         print('synthetic split: %d frames of %d x %d written in %.1f s' % (len(names), H, W, time.perf_counter() - t0))
         t0 = time.perf_counter()
-        ds = kitti_dataset.KittiDataset(config(top), 'train', seed=0)
+        ds = kitti_dataset.KittiDataset(config(top, image_aug=a.image_aug), 'train', seed=0)
         torch.cuda.synchronize()
         print('KittiDataset: loaded in %.2f s, %d samples, %d skipped, resident_bytes %d (%.1f MB per frame)'
               % (time.perf_counter() - t0, ds.num_samples, ds.num_skipped, ds.resident_bytes,
@@ -122,7 +127,8 @@ def main(argv=None):
         print('(a) build_training_sample, PNG reads included: %8.1f samples/s  %7.3f ms per sample' % (rate, ms))
         for bs in (1, 8):
             rate, ms = window(lambda: ds.next_batch(bs, True), bs, a.seconds)
-            print("(b) KittiDataset.next_batch(%d), 'oversample':    %8.1f samples/s  %7.3f ms per sample" % (bs, rate, ms))
+            print("(b) KittiDataset.next_batch(%d), 'oversample'%s:    %8.1f samples/s  %7.3f ms per sample"
+                  % (bs, ', image noise %r' % a.image_aug if a.image_aug else '', rate, ms))
         trials = torch.cat([s['jitter_trials'] for s in ds.next_batch(8, True)])
         print('jitter trials per jittered box in one batch: mean %.2f, max %d'
               % (float(trials[trials > 0].float().mean()), int(trials.max())))
