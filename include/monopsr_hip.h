@@ -277,7 +277,7 @@ int mpsr_conv2d_wgrad_f32(const float *x, const float *dy, int B, int H, int W, 
                           int dilation, float *dw, float *db, mpsr_stream_t stream);
 /* The same with caller scratch: `ws` of at least mpsr_conv2d_wgrad_scratch_floats(...) floats (0 when the layer does
  * not use any) lets the big dense 3x3 layers (the map decoder: stride 1, no dilation, H and W multiples of 4, C and N
- * multiples of 32, B*H*W >= 65536) run in the Winograd F(4x4,3x3) domain -- 36 products per channel pair and 4x4
+ * multiples of 32 and at least 128, B*H*W >= 131072) run in the Winograd F(4x4,3x3) domain -- 36 products per channel pair and 4x4
  * block where the direct weight gradient has 144; results agree with mpsr_conv2d_wgrad_f32 to ~1e-4 of the
  * gradient's scale.  ws = NULL or too small: exactly mpsr_conv2d_wgrad_f32.
  * Run-to-run reproducibility: BOTH forms combine the partial sums of their pixel / tile slices with fp32 atomics, so a
@@ -286,6 +286,16 @@ int mpsr_conv2d_wgrad_f32(const float *x, const float *dy, int B, int H, int W, 
 size_t mpsr_conv2d_wgrad_scratch_floats(int B, int H, int W, int C, int N, int KH, int KW, int dilation);
 int mpsr_conv2d_wgrad_ws_f32(const float *x, const float *dy, int B, int H, int W, int C, int N, int KH, int KW,
                              int dilation, float *dw, float *db, float *ws, size_t ws_floats, mpsr_stream_t stream);
+/* ABI 13: which kernel mpsr_conv2d_wgrad_ws_f32 launches for a shape when it is given ws_floats floats of scratch -- pure
+ * host code with the argument checks of mpsr_conv2d_wgrad_f32, reading the same predicates and slice arithmetic as the
+ * launchers.  kind: 0 = the general kernel (conv_wgrad_kernel), 1 = the 1x1 layers' direct-operand kernel
+ * (pw_wgrad_direct_kernel), 2 = the thin head kernel (N = 4; it also wants dy on a 16-byte boundary, which the plan
+ * assumes), 3 = the F(4x4,3x3) domain (only with ws_floats >= mpsr_conv2d_wgrad_scratch_floats), 4 = the F(3x3,3x3)
+ * domain.  For kinds 3 and 4 the tile sum is cut into `nslices` slices of `steps` K steps (8 tiles each for kind 3, 4
+ * for kind 4; steps is even) over `tiles` tiles: the last slice holds tiles - (nslices - 1) * steps * 8 (or 4) live
+ * tiles, the rest of it is zero-filled.  Other kinds: tiles = steps = nslices = 0.  Any out-pointer may be NULL. */
+int mpsr_conv2d_wgrad_plan(int B, int H, int W, int C, int N, int KH, int KW, int dilation, size_t ws_floats, int *kind,
+                           int *tiles, int *steps, int *nslices);
 
 /* Weight re-layout for the data gradient: wd[c][((KH*KW-1-t)*N) + n] = w[n][t*C + c].  Then
  * dx = mpsr_conv2d_nhwc_f32(dy, ..., w = wd, N := C, C := N) with the same KH, KW, dilation. */

@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MPSR_LIB_PATH: development knob for A/B-ing two builds of the library inside one GPU session
 LIB_PATH = os.environ.get("MPSR_LIB_PATH") or os.path.join(_HERE, "libmonopsr_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _lib = None
 
@@ -118,6 +118,7 @@ SIGNATURES = {
     "mpsr_conv2d_wgrad_f32": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f]),
     "mpsr_conv2d_wgrad_scratch_floats": (c_sz, [c_i] * 8),
     "mpsr_conv2d_wgrad_ws_f32": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_sz, c_f]),
+    "mpsr_conv2d_wgrad_plan": (c_i, [c_i] * 8 + [c_sz] + [ctypes.POINTER(c_i)] * 4),
     "mpsr_conv2d_dgrad_pack": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
     "mpsr_dgrad_pack_table_bytes": (c_sz, [ctypes.POINTER(PackJob), c_i]),
     "mpsr_dgrad_pack_table_build": (c_i, [ctypes.POINTER(PackJob), c_i, ctypes.c_void_p,

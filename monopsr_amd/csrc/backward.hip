@@ -656,23 +656,45 @@ inline int grid_for(long long total) { return (int)((total + 255) / 256 < 262144
 
 }  // namespace
 
-extern "C" int mpsr_conv2d_wgrad_f32(const float *x, const float *dy, int B, int H, int W, int C, int N, int KH, int KW,
-                                     int dilation, float *dw, float *db, mpsr_stream_t stream)
+namespace mpsr {
+
+int conv2d_wgrad_direct_plan(int B, int H, int W, int C, int N, int KH, int KW, int dilation, bool dy_aligned, int *kind)
 {
     MPSR_REQUIRE(B >= 0 && H > 0 && W > 0 && C > 0 && N > 0 && (KH & 1) && (KW & 1) && dilation >= 1,
                  "conv2d_wgrad: bad shape");
     MPSR_REQUIRE(C % 4 == 0 && N % 4 == 0, "conv2d_wgrad: C=%d and N=%d must be multiples of 4", C, N);
+    *kind = 0;
     if (B == 0) return MPSR_OK;
-    MPSR_REQUIRE(x && dy && dw, "conv2d_wgrad: null pointer");
     // a head with (at most) four output channels: reduce over the pixels on the vector ALU (thin_conv.hip)
     // (it reads dy as 16-byte pixels)
-    if (((uintptr_t)dy & 15) == 0 && mpsr::thin_wgrad_applies(B, H, W, C, N, KH, KW, dilation))
-        return mpsr::thin_wgrad(x, dy, B, H, W, C, dw, db, mpsr::as_stream(stream));
+    if (dy_aligned && thin_wgrad_applies(B, H, W, C, N, KH, KW, dilation)) {
+        *kind = 2;
+        return MPSR_OK;
+    }
     const long long M = (long long)B * H * W;
     MPSR_REQUIRE(M * C * 4 < 0xfffff000LL && M * N * 4 < 0xfffff000LL, "conv2d_wgrad: tensor exceeds 4 GiB");
     // the kernel decodes pixel indices with 24-bit multiplies and a float reciprocal
     MPSR_REQUIRE(M < (1LL << 24) && N < (1 << 24) && C < (1 << 24),
                  "conv2d_wgrad: more than 2^24 pixels (or channels) in one call; split the batch");
+    // 1x1 layers: operands straight from memory into the MFMA's source registers (no wrap-around of its running
+    // 32-bit offsets: the ring reads up to 2 * WD_RING rows past a slice, a slice ends up to 31 rows past M)
+    const long long slack = 2 * WD_RING + WG_K;
+    if (g_wgrad_direct && KH * KW == 1 && (M + slack) * C * 4 < 0xfffffff0LL && (M + slack) * N * 4 < 0xfffffff0LL)
+        *kind = 1;
+    return MPSR_OK;
+}
+
+}  // namespace mpsr
+
+extern "C" int mpsr_conv2d_wgrad_f32(const float *x, const float *dy, int B, int H, int W, int C, int N, int KH, int KW,
+                                     int dilation, float *dw, float *db, mpsr_stream_t stream)
+{
+    int kind = 0;
+    if (int rc = mpsr::conv2d_wgrad_direct_plan(B, H, W, C, N, KH, KW, dilation, ((uintptr_t)dy & 15) == 0, &kind)) return rc;
+    if (B == 0) return MPSR_OK;
+    MPSR_REQUIRE(x && dy && dw, "conv2d_wgrad: null pointer");
+    if (kind == 2) return mpsr::thin_wgrad(x, dy, B, H, W, C, dw, db, mpsr::as_stream(stream));
+    const long long M = (long long)B * H * W;
     WgradParams p;
     p.x = x; p.dy = dy; p.dw = dw; p.db = db;
     p.M = (int)M; p.H = H; p.W = W; p.C = C; p.N = N; p.KH = KH; p.KW = KW; p.dil = dilation;
@@ -737,10 +759,7 @@ extern "C" int mpsr_conv2d_wgrad_f32(const float *x, const float *dy, int B, int
     p.grouped = g_wgrad_grouped && group_ok && groups >= 8 && tiles > 1;
     p.ngroups = (int)groups;
     if (p.grouped) blocks = (groups + 7) / 8 * 8 * tiles;
-    // 1x1 layers: operands straight from memory into the MFMA's source registers (no wrap-around of its running
-    // 32-bit offsets: the ring reads up to 2 * WD_RING rows past a slice, a slice ends up to 31 rows past M)
-    const long long slack = 2 * WD_RING + WG_K;
-    if (g_wgrad_direct && taps == 1 && (M + slack) * C * 4 < 0xfffffff0LL && (M + slack) * N * 4 < 0xfffffff0LL) {
+    if (kind == 1) {
         hipLaunchKernelGGL(pw_wgrad_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, mpsr::as_stream(stream), p);
         MPSR_CHECK_LAUNCH("pw_wgrad_direct_kernel");
         return MPSR_OK;

@@ -115,8 +115,16 @@ int winograd_slices(long long blocks, int want_blocks, int cblocks, int min_step
 int winograd_finish_slices(const float *part, const float *bias, float *y, size_t y_floats, int nslices, int N, int relu,
                            hipStream_t s);
 
+// ---- winograd4_wgrad.hip: the tile slices of the two transform-domain weight gradients (launchers and
+// mpsr_conv2d_wgrad_plan): `nslices` slices of `steps` K steps of kt tiles cover `tiles` tiles
+struct WgradSlices {
+    int tiles, steps, nslices;
+};
+WgradSlices wgrad_tile_slices(int tiles, int blocks, int workgroups, int kt);
+
 // ---- winograd3_wgrad.hip: the atrous layers whose pixel sub-grids are single 3x3 tiles (block3's conv2)
 bool winograd3_wgrad_applies(int B, int H, int W, int C, int N, int KH, int KW, int dilation);
+WgradSlices winograd3_wgrad_slices(int B, int dilation, int C, int N);
 int conv3x3_wgrad_winograd3(const float *x, const float *dy, int B, int H, int W, int C, int N, int dilation, float *dw,
                             float *db, hipStream_t s);
 
@@ -136,6 +144,12 @@ int fc_rows_split(const float *x, long long M, int K, const float *w, const floa
                   float *ws, hipStream_t s);
 int fc_rows(const float *x, long long M, int K, const float *w, const float *bias, const float *residual, int relu,
             float *y, int N, hipStream_t s);
+
+// ---- backward.hip
+// The argument checks of mpsr_conv2d_wgrad_f32 and the kernel that serves the shape there: 0 = conv_wgrad_kernel, 1 =
+// pw_wgrad_direct_kernel, 2 = thin_wgrad (dy_aligned: dy sits on a 16-byte boundary).  The entry point and
+// mpsr_conv2d_wgrad_plan both go through it.
+int conv2d_wgrad_direct_plan(int B, int H, int W, int C, int N, int KH, int KW, int dilation, bool dy_aligned, int *kind);
 
 // ---- thin_conv.hip
 bool thin_input_conv_applies(int B, int H, int W, int C, int N, int KH, int KW, int dilation);

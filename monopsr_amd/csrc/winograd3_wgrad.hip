@@ -284,6 +284,11 @@ bool winograd3_wgrad_applies(int B, int H, int W, int C, int N, int KH, int KW, 
     return KH == 3 && KW == 3 && dilation >= 1 && H == W && H == 3 * dilation && C % 64 == 0 && N % 64 == 0 && C >= 128 &&
            N >= 128 && (long long)B * dilation * dilation >= 2048 && M * C * 4 < 0x7f000000LL && M * N * 4 < 0x7f000000LL;
 }
+// one workgroup per CU (one 400-accumulator wave per SIMD): one round of slices of 4-tile steps (wgrad_tile_slices)
+WgradSlices winograd3_wgrad_slices(int B, int dilation, int C, int N)
+{
+    return wgrad_tile_slices(B * dilation * dilation, (N / 64) * (C / 64), 256, w3g::KT);
+}
 // (no scratch: the kernel accumulates into dw directly)
 int conv3x3_wgrad_winograd3(const float *x, const float *dy, int B, int H, int W, int C, int N, int dilation, float *dw,
                             float *db, hipStream_t s)
@@ -299,14 +304,10 @@ int conv3x3_wgrad_winograd3(const float *x, const float *dy, int B, int H, int W
     p.div_d = make_fastdiv(dilation);
     p.xbytes = (unsigned)((long long)B * H * W * C * 4);
     p.dybytes = (unsigned)((long long)B * H * W * N * 4);
-    // one workgroup per CU (one 400-accumulator wave per SIMD): one round of slices, each an even number of 4-tile steps
     const int blocks = p.nblocks * p.cblocks;
-    int slices = (256 / blocks + 7) / 8 * 8;  // (a multiple of 8: slice i runs on XCD i % 8)
-    if (slices < 8) slices = 8;
-    int steps = (int)(((long long)p.T + (long long)slices * KT - 1) / ((long long)slices * KT));
-    steps = (steps + 1) / 2 * 2;
-    p.steps = steps;
-    p.nslices = (int)(((long long)p.T + (long long)steps * KT - 1) / ((long long)steps * KT));
+    const WgradSlices sl = winograd3_wgrad_slices(B, dilation, C, N);
+    p.steps = sl.steps;
+    p.nslices = sl.nslices;
     MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(wino3_wgrad_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDSF * sizeof(float))));
     const unsigned grid = (unsigned)(((p.nslices + 7) / 8) * 8 * blocks);

@@ -280,6 +280,25 @@ bool winograd4_wgrad_applies(int B, int H, int W, int C, int N, int KH, int KW, 
 }
 size_t winograd4_wgrad_scratch_floats(int C, int N) { return (size_t)36 * N * C; }
 
+// The tile slices of a transform-domain weight gradient (this file's and winograd3_wgrad.hip's; the launchers and
+// mpsr_conv2d_wgrad_plan read the same copy): about `workgroups` workgroups over the (n, c) blocks -- a multiple of 8
+// slices, slice i runs on XCD i % 8 and fewer than 8 would leave XCDs idle --, each slice an even number of K steps of
+// `kt` tiles (the K loops run two steps per iteration), then as many slices as still hold a tile.
+WgradSlices wgrad_tile_slices(int tiles, int blocks, int workgroups, int kt)
+{
+    int slices = (workgroups / blocks + 7) / 8 * 8;
+    if (slices < 8) slices = 8;
+    int steps = (int)(((long long)tiles + (long long)slices * kt - 1) / ((long long)slices * kt));
+    steps = (steps + 1) / 2 * 2;
+    const int nslices = (int)(((long long)tiles + (long long)steps * kt - 1) / ((long long)steps * kt));
+    return WgradSlices{tiles, steps, nslices};
+}
+// one workgroup per CU (144 KB of LDS): about two rounds of slices of 8-tile steps
+WgradSlices winograd4_wgrad_slices(int B, int H, int W, int C, int N)
+{
+    return wgrad_tile_slices(B * (H / 4) * (W / 4), (N / 32) * (C / 32), 512, w4g::KT);
+}
+
 int conv3x3_wgrad_winograd4(const float *x, const float *dy, int B, int H, int W, int C, int N, float *dw, float *ws,
                             size_t ws_floats, hipStream_t s)
 {
@@ -298,15 +317,10 @@ int conv3x3_wgrad_winograd4(const float *x, const float *dy, int B, int H, int W
     p.fd_tw = make_fastdiv(p.tw);
     p.xbytes = (unsigned)((long long)B * H * W * C * 4);
     p.dybytes = (unsigned)((long long)B * H * W * N * 4);
-    // one workgroup per CU (144 KB of LDS): about two rounds of slices, each an even number of 8-tile steps
     const int blocks = p.nblocks * p.cblocks;
-    // (a multiple of 8: slice i runs on XCD i % 8, fewer than 8 slices would leave XCDs idle)
-    int slices = (512 / blocks + 7) / 8 * 8;
-    if (slices < 8) slices = 8;
-    int steps = (int)(((long long)p.T + (long long)slices * KT - 1) / ((long long)slices * KT));
-    steps = (steps + 1) / 2 * 2;
-    p.steps = steps;
-    p.nslices = (int)(((long long)p.T + (long long)steps * KT - 1) / ((long long)steps * KT));
+    const WgradSlices sl = winograd4_wgrad_slices(B, H, W, C, N);
+    p.steps = sl.steps;
+    p.nslices = sl.nslices;
     MPSR_CHECK_HIP(hipMemsetAsync(ws, 0, need * sizeof(float), s));
     MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(wino4_wgrad_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDSF * sizeof(float))));
@@ -345,4 +359,29 @@ extern "C" int mpsr_conv2d_wgrad_ws_f32(const float *x, const float *dy, int B, 
         return mpsr::conv3x3_wgrad_winograd3(x, dy, B, H, W, C, N, dilation, dw, db, mpsr::as_stream(stream));
     }
     return mpsr_conv2d_wgrad_f32(x, dy, B, H, W, C, N, KH, KW, dilation, dw, db, stream);
+}
+
+// Which kernel the call above launches for a shape, and the tile slices of the two transform-domain forms: the same
+// predicates, switches and schedule helpers in the same order, no device work.
+extern "C" int mpsr_conv2d_wgrad_plan(int B, int H, int W, int C, int N, int KH, int KW, int dilation, size_t ws_floats,
+                                      int *kind, int *tiles, int *steps, int *nslices)
+{
+    int k = 0;
+    if (int rc = mpsr::conv2d_wgrad_direct_plan(B, H, W, C, N, KH, KW, dilation, true, &k)) return rc;
+    mpsr::WgradSlices sl{0, 0, 0};
+    if (g_wgrad_winograd && B > 0) {
+        if (mpsr::winograd4_wgrad_applies(B, H, W, C, N, KH, KW, dilation) &&
+            ws_floats >= mpsr::winograd4_wgrad_scratch_floats(C, N)) {
+            k = 3;
+            sl = mpsr::winograd4_wgrad_slices(B, H, W, C, N);
+        } else if (mpsr::winograd3_wgrad_applies(B, H, W, C, N, KH, KW, dilation)) {
+            k = 4;
+            sl = mpsr::winograd3_wgrad_slices(B, dilation, C, N);
+        }
+    }
+    if (kind) *kind = k;
+    if (tiles) *tiles = sl.tiles;
+    if (steps) *steps = sl.steps;
+    if (nslices) *nslices = sl.nslices;
+    return MPSR_OK;
 }

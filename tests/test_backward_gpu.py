@@ -738,7 +738,7 @@ def test_wgrad_winograd_domain_vs_direct_and_fp64():
     """The Winograd F(4x4,3x3)-domain weight gradient of the decoder's dense 3x3 layers (csrc/winograd4_wgrad.hip:
     dU = sum over tiles of (A dY A^T) (.) (B^T d B), dg = G^T dU G) against the direct kernel on a layer-sized problem
     and against float64 autograd on a slice of its filters."""
-    import ctypes
+    import wgrad_shape_cases as S
     from monopsr_amd import _lib
     lib = _lib.lib()
     B, H, W, C, N = 64, 48, 48, 128, 128
@@ -750,17 +750,21 @@ def test_wgrad_winograd_domain_vs_direct_and_fp64():
     assert lib.mpsr_conv2d_wgrad_scratch_floats(B, H, W, C, N, 3, 3, 2) == 0      # atrous: direct kernel
     assert lib.mpsr_conv2d_wgrad_scratch_floats(B, H + 2, W, C, N, 3, 3, 1) == 0  # not 4x4 blocks
     ws = torch.empty((nws,), device="cuda")
+    # which kernel serves the call is the library's own answer (tests/wgrad_shape_cases.py has this shape's schedule)
+    assert S.check_case_plan(S.BY_NAME["decoder"]) == (3, 9216, 36, 32)
+    assert S.BY_NAME["decoder"].shape == (B, H, W, C, N)
     outs = []
     for wino in (0, 1):
-        dw = torch.zeros((N, 9 * C), device="cuda")
+        dw = torch.full((N, 9 * C), 0.25, device="cuda")  # (the kernels ACCUMULATE into dw)
         db = torch.zeros((N,), device="cuda")
         lib.mpsr_debug_set_wgrad_winograd(wino)
         try:
+            assert S.wgrad_plan(B, H, W, C, N, 3, 1, nws)[0] == (3 if wino else 0)
             _lib.check(lib.mpsr_conv2d_wgrad_ws_f32(x.data_ptr(), dy.data_ptr(), B, H, W, C, N, 3, 3, 1, dw.data_ptr(),
                                                     db.data_ptr(), ws.data_ptr(), nws, _lib.stream()))
         finally:
             lib.mpsr_debug_set_wgrad_winograd(1)
-        outs.append((dw, db))
+        outs.append((dw - 0.25, db))
     scale = outs[0][0].abs().max().item()
     assert (outs[1][0] - outs[0][0]).abs().max().item() <= 1e-4 * scale
     assert not torch.equal(outs[1][0], outs[0][0])  # it really is the other evaluation
@@ -773,6 +777,7 @@ def test_wgrad_winograd_domain_vs_direct_and_fp64():
     ref = w.grad.permute(0, 2, 3, 1).reshape(4, 9 * C)
     assert (outs[1][0][:4].double() - ref).abs().max().item() <= 1e-4 * ref.abs().max().item()
     # scratch too small or absent: the direct kernel, same result as mpsr_conv2d_wgrad_f32
+    assert S.wgrad_plan(B, H, W, C, N, 3, 1, 0)[0] == 0
     dw2 = torch.zeros((N, 9 * C), device="cuda")
     _lib.check(lib.mpsr_conv2d_wgrad_ws_f32(x.data_ptr(), dy.data_ptr(), B, H, W, C, N, 3, 3, 1, dw2.data_ptr(), None,
                                             None, 0, _lib.stream()))
@@ -786,9 +791,12 @@ def test_wgrad_winograd3_domain_vs_direct_and_fp64(B, dil, C, N):
     dg = G'^T dU G'; one 400-accumulator wave per 32 x 32 block) against the border-class direct kernel on layer-sized
     problems (ragged tile counts: the last slice's steps run past the last tile) and against float64 autograd on a slice
     of the filters."""
+    import wgrad_shape_cases as S
     from monopsr_amd import _lib
     lib = _lib.lib()
     H = W = 3 * dil
+    case = [c for c in S.W3_CASES if (c.B, c.dil, c.C, c.N) == (B, dil, C, N)]
+    assert len(case) == 1 and S.check_case_plan(case[0])[0] == 4  # (the kernel and its schedule: the library's own answer)
     g = torch.Generator(device="cuda").manual_seed(B + C)
     x = torch.randn((B, H, W, C), device="cuda", generator=g).clamp_(min=0)
     dy = torch.randn((B, H, W, N), device="cuda", generator=g)
@@ -802,6 +810,7 @@ def test_wgrad_winograd3_domain_vs_direct_and_fp64(B, dil, C, N):
         db = torch.zeros((N,), device="cuda")
         lib.mpsr_debug_set_wgrad_winograd(wino)
         try:
+            assert S.wgrad_plan(B, H, W, C, N, 3, dil, nws)[0] == (4 if wino else 0)
             _lib.check(lib.mpsr_conv2d_wgrad_ws_f32(x.data_ptr(), dy.data_ptr(), B, H, W, C, N, 3, 3, dil, dw.data_ptr(),
                                                     db.data_ptr(), ws.data_ptr(), nws, _lib.stream()))
         finally:

@@ -197,4 +197,4 @@ def test_apply_image_noise_refuses_float_input_and_unknown_modes():
 
 
 def test_abi_12_declares_the_entry_point():
-    assert _lib.ABI_VERSION == 12 and 'mpsr_image_noise' in _lib.SIGNATURES
+    assert _lib.ABI_VERSION == 13 and 'mpsr_image_noise' in _lib.SIGNATURES
