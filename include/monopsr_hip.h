@@ -471,6 +471,18 @@ int mpsr_proj_err_norm_grad(const float *grad_proj_err_norm, const float *xyz_gl
                             const float *cam_p, const float *valid_mask, float *grad_xyz_global, int b, int h, int w,
                             mpsr_stream_t stream);
 
+/* Per-box cameras for the two projection-error entry points -- the boxes of several frames in one call, the convention
+ * of mpsr_heads_fwd_cams: cam_p (n_cams,12); cam_index (b) int32 picks each box's matrix; NULL: every box uses the first.
+ * An index outside [0, n_cams) is never dereferenced: that box's proj_err_maps / proj_err_norm / grad_xyz_global come
+ * back NaN, the other boxes are not affected and no error is recorded.  A box's arithmetic is that of the single-camera
+ * entry points (which are these with n_cams = 1 and a NULL index): one workgroup per box, same operation order. */
+int mpsr_proj_err_norm_cams(const float *xyz_global, const float *boxes_2d, const float *cam_p, int n_cams,
+                            const int *cam_index, const float *valid_mask, float *proj_err_maps, float *proj_err_norm,
+                            int b, int h, int w, mpsr_stream_t stream);
+int mpsr_proj_err_norm_grad_cams(const float *grad_proj_err_norm, const float *xyz_global, const float *boxes_2d,
+                                 const float *cam_p, int n_cams, const int *cam_index, const float *valid_mask,
+                                 float *grad_xyz_global, int b, int h, int w, mpsr_stream_t stream);
+
 /* instance_utils.py:605-680 tf_inst_depth_map_local_to_global: depth_global (b,h,w) = depth_local + cen_z[b]
  * (+ the view-normalisation offset, linear along the ROW axis as the reference lays it out, when rotate_view).
  * depth_local is read with a stride of depth_stride floats (3 to read the z channel of an xyz map in place). */
@@ -483,6 +495,17 @@ int mpsr_depth_map_local_to_global_grad(const float *grad_global, const float *b
                                         const float *cam_p, float *grad_cen_z, int b, int h, int w, int rotate_view,
                                         mpsr_stream_t stream);
 
+/* The same two with per-box cameras (cam_p (n_cams,12), cam_index (b) or NULL, as mpsr_proj_err_norm_cams).  The
+ * camera is read only when rotate_view is set; an index outside [0, n_cams) then gives NaN in that box's depth_global /
+ * grad_cen_z and is never dereferenced. */
+int mpsr_depth_map_local_to_global_cams(const float *depth_local, int depth_stride, const float *cen_z,
+                                        const float *boxes_2d, const float *view_angs, const float *cam_p, int n_cams,
+                                        const int *cam_index, float *depth_global, int b, int h, int w,
+                                        int rotate_view, mpsr_stream_t stream);
+int mpsr_depth_map_local_to_global_grad_cams(const float *grad_global, const float *boxes_2d, const float *view_angs,
+                                             const float *cam_p, int n_cams, const int *cam_index, float *grad_cen_z,
+                                             int b, int h, int w, int rotate_view, mpsr_stream_t stream);
+
 /* Per-instance sums behind WeightedNonZeroSmoothL1LocalizationLoss (losses_custom.py:93-132, tf.losses.huber_loss
  * with Reduction.SUM_BY_NONZERO_WEIGHTS): pred/target (b,p,c), weights (b,p) broadcast over c.
  * sums[b] = sum huber(pred-target)*w; counts[b] = c * #(w != 0).  loss = sum(sums)/sum(counts) (0 if none). */
@@ -493,6 +516,12 @@ int mpsr_huber_loss_sums(const float *pred, const float *target, const float *we
  * derive it from sums/counts without a host sync). */
 int mpsr_huber_loss_grad(const float *pred, const float *target, const float *weights, const float *scale, int b,
                          int p, int c, float delta, float *grad, mpsr_stream_t stream);
+
+/* mpsr_huber_loss_grad with one DEVICE scale per instance: grad (b,p,c) = scale[instance] * w * clamp(pred - target,
+ * -delta, delta).  A step over several frames normalises every frame's map loss by that frame's own valid-pixel count
+ * (MonoPSRModel.loss_batch): the scale of an instance is its frame's. */
+int mpsr_huber_loss_grad_scales(const float *pred, const float *target, const float *weights, const float *scale,
+                                int b, int p, int c, float delta, float *grad, mpsr_stream_t stream);
 
 /* monopsr_model.py:960-1071 format_predictions (test mode; lwh offset, alpha 'dc', view_ang est, centroids xyz)
  * with instance_utils.py:988-1032 postprocess_cen_x and monopsr_output_builder.py:805-860 score_boxes, one thread

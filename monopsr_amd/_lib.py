@@ -157,10 +157,15 @@ SIGNATURES = {
     "mpsr_xyz_map_local_to_global_grad": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_f]),
     "mpsr_proj_err_norm": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "mpsr_proj_err_norm_grad": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
+    "mpsr_proj_err_norm_cams": (c_i, [c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
+    "mpsr_proj_err_norm_grad_cams": (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "mpsr_depth_map_local_to_global": (c_i, [c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "mpsr_depth_map_local_to_global_grad": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "mpsr_depth_map_local_to_global_cams": (c_i, [c_f, c_i, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "mpsr_depth_map_local_to_global_grad_cams": (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "mpsr_huber_loss_sums": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_float, c_f, c_f, c_f]),
     "mpsr_huber_loss_grad": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_float, c_f, c_f]),
+    "mpsr_huber_loss_grad_scales": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_float, c_f, c_f]),
     "mpsr_format_boxes": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i,
                                 ctypes.c_float, c_f, c_f, c_f]),
     "mpsr_trunk_workspace_bytes": (c_sz, [c_i, c_i, c_i]),

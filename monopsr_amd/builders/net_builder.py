@@ -17,7 +17,8 @@ def get_net_config(model_config):
 
 def extract_features(model, net_type, model_config, input_dict, is_training):
     """model: object with `device_net` (DeviceNet), `pl_boxes_2d_norm` (B,4), `num_boxes`, `map_roi_size`,
-    `is_training`.  input_dict: NET_IN_RGB_CROP (B,h,w,3) and either NET_IN_FULL_IMG (1,H,W,3) or
+    `is_training`, optionally `pl_box_ind` (B) int32.  input_dict: NET_IN_RGB_CROP (B,h,w,3) and either NET_IN_FULL_IMG
+    (1,H,W,3) -- (N,H,W,3) with `pl_box_ind` naming each box's image -- or
     NET_IN_FULL_IMG_FEATURE_CROP (B, map_h/4, map_w/4, 1024)."""
     features_dict = {}
     if net_type == 'resnet101_4x_squash':
@@ -47,7 +48,9 @@ def build_resnet101_4x_squash(net_config, net_type, model, input_dict, features_
             crop_and_resize = getattr(net, 'crop_and_resize', dn.crop_and_resize)
             max_pool = getattr(net, 'max_pool', dn.max_pool)
             full_img_encoder_out = net.trunk(full_img, 'full')
-            large = crop_and_resize(full_img_encoder_out, model.pl_boxes_2d_norm, None, half)
+            # (box_ind: the image of each box when NET_IN_FULL_IMG holds several, MonoPSRModel.build_train_batch)
+            large = crop_and_resize(full_img_encoder_out, model.pl_boxes_2d_norm, getattr(model, 'pl_box_ind', None),
+                                    half)
             return max_pool(large, 2, 2, "VALID")
 
         # (a trainable net caps the box count, TrainNet.side_stream_max_boxes = 64: training step with both trunks 24.5 vs

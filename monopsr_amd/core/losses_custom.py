@@ -39,6 +39,51 @@ class _HuberNonZero(torch.autograd.Function):
         return grad, None, None, None
 
 
+class _HuberNonZeroFrames(torch.autograd.Function):
+    """sum_f frame_scale[f] * sum_{b in f} sums_b / max(sum_{b in f} counts_b, 1): the SUM_BY_NONZERO_WEIGHTS
+    reduction taken per FRAME of a step that holds the instances of several (MonoPSRModel.loss_batch).  The
+    per-instance sums and counts are mpsr_huber_loss_sums', pooled per frame by index_add_ over (B); the backward
+    gives mpsr_huber_loss_grad_scales one scale per instance, its frame's."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weights, delta, frame_index, n_frames, frame_scale):
+        b, c = pred.shape[0], pred.shape[-1]
+        p = pred[0].numel() // c if b else 0
+        pred, target = pred.contiguous().float(), target.contiguous().float()
+        weights = weights.contiguous().float()
+        both = torch.empty((2, b), dtype=torch.float32, device=pred.device)  # per-instance sums | non-zero counts
+        _lib.check(_lib.lib().mpsr_huber_loss_sums(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(weights), b, p, c,
+                                                   float(delta), both[0].data_ptr(), both[1].data_ptr(), _lib.stream()))
+        per_frame = torch.zeros((2, n_frames), dtype=torch.float32, device=pred.device)
+        per_frame.index_add_(1, frame_index, both)
+        k = frame_scale / torch.clamp(per_frame[1], min=1.0)  # (no non-zero weight in a frame: its sum is 0 too)
+        ctx.save_for_backward(pred, target, weights, k.index_select(0, frame_index))
+        ctx.meta = (b, p, c, float(delta))
+        return (per_frame[0] * k).sum()
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, weights, k = ctx.saved_tensors
+        b, p, c, delta = ctx.meta
+        scale = (g.float() * k).contiguous()  # (B)
+        grad = torch.empty_like(pred)
+        _lib.check(_lib.lib().mpsr_huber_loss_grad_scales(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(weights),
+                                                          _lib.ptr(scale), b, p, c, delta, _lib.ptr(grad),
+                                                          _lib.stream()))
+        return grad, None, None, None, None, None, None
+
+
+def huber_nonzero_frames(pred, target, weights, delta, frame_index, n_frames, frame_scale):
+    """pred / target (B, ..., C), weights (B, ..., 1), frame_index (B) int64 in [0, n_frames), frame_scale (n_frames)
+    -> the scalar of _HuberNonZeroFrames."""
+    if tuple(weights.shape) != tuple(pred.shape[:-1]) + (1,) or tuple(target.shape) != tuple(pred.shape):
+        raise _lib.InvalidArgumentError("weights must have shape prediction.shape[:-1] + (1,) and target the "
+                                        "prediction's shape")
+    if frame_index.numel() != pred.shape[0] or frame_scale.numel() != n_frames:
+        raise _lib.InvalidArgumentError("frame_index must be (B) and frame_scale (n_frames)")
+    return _HuberNonZeroFrames.apply(pred, target, weights, delta, frame_index, n_frames, frame_scale)
+
+
 class WeightedNonZeroSmoothL1LocalizationLoss(Loss):
     """losses_custom.py:93-132: tf.losses.huber_loss with Reduction.SUM_BY_NONZERO_WEIGHTS -> a scalar.
     weights must be prediction_tensor's shape with a last axis of 1 (a per-pixel / per-box mask)."""

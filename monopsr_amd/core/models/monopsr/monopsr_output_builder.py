@@ -42,15 +42,18 @@ class UniqueKeyDict:
 
 
 def tf_boxes_2d_ij_fmt(boxes_2d, cam_p):
-    """datasets/kitti/obj_utils.py:1016-1034: box coordinates relative to the principal point."""
-    centre_u, centre_v = cam_p[0, 2], cam_p[1, 2]
-    return boxes_2d - torch.stack([centre_v, centre_u, centre_v, centre_u])
+    """datasets/kitti/obj_utils.py:1016-1034: box coordinates relative to the principal point.  cam_p (3,4), or
+    (N,3,4): one camera per box."""
+    centre_u, centre_v = cam_p[..., 0, 2], cam_p[..., 1, 2]
+    return boxes_2d - torch.stack([centre_v, centre_u, centre_v, centre_u], dim=-1)
 
 
 def tf_est_y_from_box_2d_and_depth(cam_p, box_2d, depth, class_str=None, trend_data='kitti'):
-    """datasets/kitti/instance_utils.py:907-953."""
-    focal_length, centre_v = cam_p[0, 0], cam_p[1, 2]
+    """datasets/kitti/instance_utils.py:907-953.  cam_p (3,4), or (N,3,4): one camera per box."""
+    focal_length, centre_v = cam_p[..., 0, 0], cam_p[..., 1, 2]
     box_2d_centre_v = ((box_2d[:, 2] + box_2d[:, 0]) / 2. - centre_v).unsqueeze(1)
+    if focal_length.dim():
+        focal_length = focal_length.unsqueeze(1)
     cen_y_mid_estimate = box_2d_centre_v * (depth / focal_length)
     if (class_str, trend_data) not in CEN_Y_CLASS_OFFSET:
         raise ValueError('Invalid class_str', class_str)
@@ -60,7 +63,10 @@ def tf_est_y_from_box_2d_and_depth(cam_p, box_2d, depth, class_str=None, trend_d
 class MonoPSROutputBuilder:
 
     def __init__(self, output_config, model_config, dataset_config, features_dict, num_boxes, map_roi_size, cam_p,
-                 train_val_test, device_net=None):
+                 train_val_test, device_net=None, cam_index=None):
+        """cam_p (3,4): the frame's camera, as in the reference.  With cam_index (num_boxes) int32, cam_p is
+        (n_cams,3,4) and box b uses cam_p[cam_index[b]] -- the boxes of several frames in one pass
+        (MonoPSRModel.build_train_batch); every camera entry the methods read is then a per-box column."""
         self.output_config = output_config.__dict__ if hasattr(output_config, '__dict__') else dict(output_config)
         self.output_types = MonoPSROutputBuilder.get_output_types_list(output_config)
         self.model_config = model_config
@@ -70,7 +76,13 @@ class MonoPSROutputBuilder:
         self._gt_dict = UniqueKeyDict()
         self.num_boxes = num_boxes
         self.map_roi_size = map_roi_size
-        self.cam_p = cam_p.reshape(3, 4)
+        self.cam_index = cam_index
+        if cam_index is None:
+            self.cam_p = cam_p.reshape(3, 4)
+            self.box_cam_p = self.cam_p
+        else:
+            self.cam_p = cam_p.reshape(-1, 3, 4)
+            self.box_cam_p = self.cam_p.index_select(0, cam_index.reshape(-1).long())  # (num_boxes,3,4)
         self.features_for_map = features_dict[constants.FEATURES_FOR_MAP]
         self.features_for_box_3d = features_dict[constants.FEATURES_FOR_BOX_3D]
         self.train_val_test = train_val_test
@@ -94,6 +106,18 @@ class MonoPSROutputBuilder:
 
     def get_gt_dict(self):
         return self._gt_dict.dict
+
+    def _cam_el(self, i, j, ndim=1, n=None):
+        """cam_p[i, j]: a 0-d tensor, or with per-box cameras that entry of the first `n` boxes' matrices shaped
+        (n, 1, ...) with `ndim` axes, to broadcast against per-box tensors."""
+        if self.cam_index is None:
+            return self.cam_p[i, j]
+        col = self.box_cam_p[:, i, j] if n is None else self.box_cam_p[:n, i, j]
+        return col.reshape((-1,) + (1,) * (ndim - 1))
+
+    def get_x_offset(self):
+        """-P[0,3] / P[0,0] (the camera's x offset from camera 0): 0-d, or (num_boxes, 1) with per-box cameras."""
+        return -self._cam_el(0, 3, 2) / self._cam_el(0, 0, 2)
 
     # ------------------------------------------------------------------ local xyz map (:95-108)
     def add_inst_xyz_maps_local(self, gt_inst_xyz_maps_local):
@@ -133,7 +157,7 @@ class MonoPSROutputBuilder:
 
     # ------------------------------------------------------------------ shared scalar features
     def _box_features(self, boxes_2d, class_indices, image_shape):
-        box_2d_coords = tf_boxes_2d_ij_fmt(boxes_2d, self.cam_p)
+        box_2d_coords = tf_boxes_2d_ij_fmt(boxes_2d, self.box_cam_p)
         box_2d_heights = (boxes_2d[:, 2] - boxes_2d[:, 0]).unsqueeze(1)
         box_2d_heights_norm = box_2d_heights / image_shape[0]
         half_img_height, half_img_width = image_shape[0] / 2.0, image_shape[1] / 2.0
@@ -157,8 +181,12 @@ class MonoPSROutputBuilder:
         flat_img_features = self.features_for_box_3d.reshape(self.features_for_box_3d.shape[0], -1)
         coords_norm, heights_norm, one_hot = self._box_features(boxes_2d, class_indices, image_shape)
         img_fc = self.net.fully_connected(flat_img_features, p + 'img_fc', True)
-        cam_p_normalized = self.cam_p.reshape(1, -1) / dn.device_constant([CAM_P_NORM], self.cam_p.device)
-        cam_p_tiled = cam_p_normalized.repeat(self.num_boxes, 1)
+        if self.cam_index is None:
+            cam_p_normalized = self.cam_p.reshape(1, -1) / dn.device_constant([CAM_P_NORM], self.cam_p.device)
+            cam_p_tiled = cam_p_normalized.repeat(self.num_boxes, 1)
+        else:
+            cam_p_tiled = self.box_cam_p.reshape(self.num_boxes, -1) / dn.device_constant([CAM_P_NORM],
+                                                                                         self.cam_p.device)
         features_concat = torch.cat([img_fc, coords_norm, heights_norm, view_angs, one_hot, cam_p_tiled], dim=1)
         fc_drop = features_concat
         for fc_idx, _ in enumerate(self.model_config.proposal_fc_layers.layer_sizes):
@@ -267,7 +295,7 @@ class MonoPSROutputBuilder:
                                               output_key: gt_view_angs})
 
     def get_prop_cen_z(self, boxes_2d, offset):
-        f = self.cam_p[0, 0]
+        f = self._cam_el(0, 0)
         est_obj_h = self.get_output_dict()[constants.KEY_LWH][:, 2]
         boxes_2d_h = boxes_2d[:, 2] - boxes_2d[:, 0]
         prop_cen_z = (f * est_obj_h / boxes_2d_h + offset).unsqueeze(1)
@@ -275,7 +303,7 @@ class MonoPSROutputBuilder:
         return prop_cen_z
 
     def get_prop_cen_y(self, boxes_2d, depth, class_name):
-        return tf_est_y_from_box_2d_and_depth(self.cam_p, boxes_2d, depth, class_name, trend_data='kitti')
+        return tf_est_y_from_box_2d_and_depth(self.box_cam_p, boxes_2d, depth, class_name, trend_data='kitti')
 
     def add_cen_z_output(self, output_key, features_in, prop_cen_z, gt_cen_z):
         """:441-507.  'offset': FC output added to the proposal depth (scope cen_z_offs); 'direct': the FC output
@@ -319,7 +347,7 @@ class MonoPSROutputBuilder:
         if output_type != 'from_view_ang_and_z':
             raise ValueError('Invalid output_type', output_type)
         cam2_pred_cen_x = pred_cen_z * torch.tan(pred_view_angs)
-        x_offset = -self.cam_p[0, 3] / self.cam_p[0, 0]
+        x_offset = self.get_x_offset()
         self._output_dict.add_unique_to_dict({output_key: cam2_pred_cen_x + x_offset})
 
     def add_centroids_output(self, output_key, pred_cen_x, pred_cen_y, pred_cen_z, gt_centroids):
@@ -337,7 +365,8 @@ class MonoPSROutputBuilder:
         """:681-746 -> (proj_err_norm (N,), proj_err_debug_dict).  The debug dict holds the normalised error map
         only when `debug` (the reference's other debug entries are intermediate tensors of its TF graph)."""
         proj_err_norm, maps = instance_utils.proj_err_maps_norm(pred_inst_xyz_map_global, pred_boxes_2d, self.cam_p,
-                                                                valid_mask_maps, want_maps=debug)
+                                                                valid_mask_maps, want_maps=debug,
+                                                                cam_index=self.cam_index)
         proj_err_debug_dict = {'pred_inst_xyz_map_global': pred_inst_xyz_map_global}
         if debug:
             proj_err_debug_dict['proj_err_map_norm'] = maps
@@ -349,7 +378,8 @@ class MonoPSROutputBuilder:
         pred_cen_z = self._output_dict[constants.KEY_CEN_Z]
         inst_view_ang = self._output_dict[constants.KEY_VIEW_ANG]
         pred = instance_utils.tf_inst_depth_map_local_to_global(
-            pred_inst_depth_maps_local, pred_cen_z, box_2d, inst_view_ang, self.map_roi_size, self.cam_p, rotate_view)
+            pred_inst_depth_maps_local, pred_cen_z, box_2d, inst_view_ang, self.map_roi_size, self.cam_p, rotate_view,
+            cam_index=self.cam_index)
         self._output_dict.add_unique_to_dict({output_key: pred})
         if self.is_train_or_val:
             self._gt_dict.add_unique_to_dict({output_key: gt_inst_depth_maps_global})
@@ -371,9 +401,9 @@ class MonoPSROutputBuilder:
         ty = torch.linspace(0.0, 1.0, ny, device=d.device).reshape(1, ny)
         xs = (x1 + half_w) + ((x2 - half_w) - (x1 + half_w)) * tx  # (n, nx)
         ys = (y1 + half_h) + ((y2 - half_h) - (y1 + half_h)) * ty  # (n, ny)
-        ratio = d / self.cam_p[0, 0]
-        x = (xs.reshape(n, 1, nx) - self.cam_p[0, 2]) * ratio
-        y = (ys.reshape(n, ny, 1) - self.cam_p[1, 2]) * ratio
+        ratio = d / self._cam_el(0, 0, 3, n)
+        x = (xs.reshape(n, 1, nx) - self._cam_el(0, 2, 3, n)) * ratio
+        y = (ys.reshape(n, ny, 1) - self._cam_el(1, 2, 3, n)) * ratio
         pc_map = torch.stack((x, y, d), dim=1)  # (n, 3, h, w)
         output = pc_map.reshape(n, h, w, 3)
         self._output_dict.add_unique_to_dict({output_key: output})

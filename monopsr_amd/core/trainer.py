@@ -293,6 +293,41 @@ class InstanceTrainer:
         self.global_step += 1
         return loss.detach()
 
+    def step_batch(self, samples):
+        """One training step on SEVERAL frames: `step` with MonoPSRModel.build_train_batch / loss_batch in place of
+        build / loss -- `samples` is a non-empty list of step()'s sample dicts (box counts, image sizes and cameras may
+        differ; e.g. KittiDataset.next_batch(8, True)).  The full-image trunk runs once with batch N, every other layer
+        once over all boxes; the loss is the average of the frames' own losses (see loss_batch), so with
+        decoder_bn='frozen' the gradient is the mean of the frames' single-frame gradients.  With decoder_bn='batch' the
+        decoder's statistics are those of all boxes of the step, as 'batch_global' gives N ranks with one frame each.
+        Same order as step: zero grads, forward, losses, data-gradient bank refresh, backward, reducer.finish, fused
+        clip + Adam + moving average; ONE increment of global_step; net.grads keeps the reduced, unclipped gradient.
+        Argument errors are ValueErrors raised before anything is launched."""
+        self.model._check_train_batch(samples)
+        self.net.zero_grad()
+        out = self.model.build_train_batch(samples)
+        self.losses_dict, loss = self.model.loss_batch(out, self.model.gt_dict,
+                                                       self.model.batch_sample.get('gt_alpha_valid_bins'))
+        bank = getattr(self.net, "dgrad_bank", None)
+        if bank is not None:
+            bank.refresh()
+        try:
+            loss.backward()
+        finally:
+            if bank is not None:
+                bank.invalidate()
+        self.reducer.finish(average=True)
+        if self.fused_update:
+            if self._clip is None:
+                self._clip = self._clip_table()
+            self.optimizer.apply_clipped_gradients(self.net, self.global_step, self._clip, self.clip_norm)
+        else:
+            if self.clip_norm:
+                self.clip_per_variable()
+            self.optimizer.apply_gradients(self.net, self.global_step)
+        self.global_step += 1
+        return loss.detach()
+
     # ------------------------------------------------------------------ checkpoint / resume (core/trainer.py:85,149-185)
     def save(self, checkpoint_dir, name='monopsr'):
         """Write the training state as a TensorFlow-format checkpoint `<dir>/<name>-<global_step, 8 digits>` (the

@@ -26,6 +26,16 @@ __device__ __forceinline__ float block_sum(float v, float *scratch)
     return r;
 }
 
+// Per-box cameras (the convention of mpsr_heads_fwd_cams, network.hip): cam_p (n_cams,12), cam_index (b) picks each box's
+// matrix, nullptr = every box reads the first.  An index outside [0, n_cams) is never dereferenced: nullptr comes back and
+// the caller fills that box's camera-dependent outputs with NaN.
+__device__ __forceinline__ const float *cam_of(const float *cam_p, const int *cam_index, int n_cams, int b)
+{
+    if (!cam_index) return cam_p;
+    const int i = cam_index[b];
+    return (i >= 0 && i < n_cams) ? cam_p + 12 * i : nullptr;
+}
+
 // --------------------------------------------------------------------------------- local -> global xyz maps
 
 // instance_utils.py:567-602: p' = T(centroid) * R_y(view) * p  (transform_utils.py:92-104).
@@ -107,6 +117,7 @@ template <int MODE>
 __global__ __launch_bounds__(kThreads) void proj_err_kernel(const float *__restrict__ xyz,
                                                             const float *__restrict__ boxes,
                                                             const float *__restrict__ cam_p,
+                                                            const int *__restrict__ cam_index, int n_cams,
                                                             const float *__restrict__ mask,
                                                             const float *__restrict__ gnorm,
                                                             float *__restrict__ maps, float *__restrict__ out,
@@ -115,9 +126,12 @@ __global__ __launch_bounds__(kThreads) void proj_err_kernel(const float *__restr
     __shared__ float scratch[kThreads / 64];
     const int b = blockIdx.x, P = H * W;
     const BoxGrid g = box_grid(boxes + b * 4, H, W);
+    const float *cam = cam_of(cam_p, cam_index, n_cams, b);
+    const bool bad_cam = cam == nullptr;  // (the clips below would swallow a NaN projection: its outputs are set, not computed)
+    const float nan = __builtin_nanf("");
     float pm[12];
 #pragma unroll
-    for (int i = 0; i < 12; ++i) pm[i] = cam_p[i];
+    for (int i = 0; i < 12; ++i) pm[i] = bad_cam ? nan : cam[i];
     float nv = 0.f;
     for (int i = threadIdx.x; i < P; i += kThreads) nv += mask[(size_t)b * P + i];
     nv = block_sum(nv, scratch);
@@ -136,7 +150,8 @@ __global__ __launch_bounds__(kThreads) void proj_err_kernel(const float *__restr
         const float eu_raw = ((g.u0 + g.du * (float)cidx) - u) / g.bw * m;
         const float ev_raw = ((g.v0 + g.dv * (float)r) - v) / g.bh * m;
         if (MODE == 0) {
-            const float eu = fminf(fmaxf(eu_raw, -2.0f), 2.0f), ev = fminf(fmaxf(ev_raw, -2.0f), 2.0f);
+            float eu = fminf(fmaxf(eu_raw, -2.0f), 2.0f), ev = fminf(fmaxf(ev_raw, -2.0f), 2.0f);
+            if (bad_cam) eu = ev = nan;
             if (maps) {
                 maps[((size_t)b * P + i) * 2 + 0] = eu;
                 maps[((size_t)b * P + i) * 2 + 1] = ev;
@@ -148,7 +163,8 @@ __global__ __launch_bounds__(kThreads) void proj_err_kernel(const float *__restr
             const float kv = (ev_raw >= -2.0f && ev_raw <= 2.0f) ? -m / g.bh * gscale / Wc : 0.f;
             float *o = out + ((size_t)b * P + i) * 3;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) o[k] = ku * (pm[k] - u * pm[8 + k]) + kv * (pm[4 + k] - v * pm[8 + k]);
+            for (int k = 0; k < 3; ++k)
+                o[k] = bad_cam ? nan : ku * (pm[k] - u * pm[8 + k]) + kv * (pm[4 + k] - v * pm[8 + k]);
         }
     }
     if (MODE == 0) {
@@ -181,6 +197,7 @@ __global__ __launch_bounds__(kThreads) void depth_global_kernel(const float *__r
                                                                 const float *__restrict__ boxes,
                                                                 const float *__restrict__ view,
                                                                 const float *__restrict__ cam_p,
+                                                                const int *__restrict__ cam_index, int n_cams,
                                                                 float *__restrict__ out, int H, int W, int rotate)
 {
     const int b = blockIdx.y, P = H * W;
@@ -189,10 +206,15 @@ __global__ __launch_bounds__(kThreads) void depth_global_kernel(const float *__r
     const float z = cen_z[b];
     float off = 0.f;
     if (rotate) {
-        float a, k;
-        depth_row_coef(boxes + b * 4, view[b], cam_p, H, a, k);
-        const int r = i / W;
-        off = z * a + (z * k) * (float)r;
+        const float *cam = cam_of(cam_p, cam_index, n_cams, b);
+        if (cam) {
+            float a, k;
+            depth_row_coef(boxes + b * 4, view[b], cam, H, a, k);
+            const int r = i / W;
+            off = z * a + (z * k) * (float)r;
+        } else {
+            off = __builtin_nanf("");
+        }
     }
     out[(size_t)b * P + i] = d[((size_t)b * P + i) * stride] + z + off;
 }
@@ -202,13 +224,20 @@ __global__ __launch_bounds__(kThreads) void depth_global_grad_kernel(const float
                                                                      const float *__restrict__ boxes,
                                                                      const float *__restrict__ view,
                                                                      const float *__restrict__ cam_p,
+                                                                     const int *__restrict__ cam_index, int n_cams,
                                                                      float *__restrict__ grad_cen_z, int H, int W,
                                                                      int rotate)
 {
     __shared__ float scratch[kThreads / 64];
     const int b = blockIdx.x, P = H * W;
     float a = 0.f, k = 0.f;
-    if (rotate) depth_row_coef(boxes + b * 4, view[b], cam_p, H, a, k);
+    if (rotate) {
+        const float *cam = cam_of(cam_p, cam_index, n_cams, b);
+        if (cam)
+            depth_row_coef(boxes + b * 4, view[b], cam, H, a, k);
+        else
+            a = k = __builtin_nanf("");
+    }
     float s = 0.f;
     for (int i = threadIdx.x; i < P; i += kThreads) s += g[(size_t)b * P + i] * (1.0f + a + k * (float)(i / W));
     s = block_sum(s, scratch);
@@ -244,17 +273,21 @@ __global__ __launch_bounds__(kThreads) void huber_sum_kernel(const float *__rest
     }
 }
 
-// grad = scale[0] * w * clamp(pred - target, -delta, delta)
+// grad = scale * w * clamp(pred - target, -delta, delta); scale = scale[0], or with PER_INSTANCE scale[instance]
+// (per_inst = P * C elements per instance)
+template <bool PER_INSTANCE>
 __global__ __launch_bounds__(kThreads) void huber_grad_kernel(const float *__restrict__ pred,
                                                               const float *__restrict__ target,
                                                               const float *__restrict__ weights,
-                                                              const float *__restrict__ scale, long long n, int C,
-                                                              float delta, float *__restrict__ grad)
+                                                              const float *__restrict__ scale, long long n,
+                                                              long long per_inst, int C, float delta,
+                                                              float *__restrict__ grad)
 {
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
     const float e = pred[i] - target[i];
-    grad[i] = scale[0] * weights[i / C] * fminf(fmaxf(e, -delta), delta);
+    const float sc = PER_INSTANCE ? scale[i / per_inst] : scale[0];
+    grad[i] = sc * weights[i / C] * fminf(fmaxf(e, -delta), delta);
 }
 
 // --------------------------------------------------------------------------------------- post-processing
@@ -381,15 +414,39 @@ int mpsr_xyz_map_local_to_global_grad(const float *grad_global, const float *vie
     return MPSR_OK;
 }
 
-int mpsr_proj_err_norm(const float *xyz_global, const float *boxes_2d, const float *cam_p, const float *valid_mask,
-                       float *proj_err_maps, float *proj_err_norm, int b, int h, int w, mpsr_stream_t stream)
+int mpsr_proj_err_norm_cams(const float *xyz_global, const float *boxes_2d, const float *cam_p, int n_cams,
+                            const int *cam_index, const float *valid_mask, float *proj_err_maps, float *proj_err_norm,
+                            int b, int h, int w, mpsr_stream_t stream)
 {
-    MPSR_REQUIRE(b >= 0 && h > 0 && w > 0, "proj_err_norm: bad size b=%d h=%d w=%d", b, h, w);
+    MPSR_REQUIRE(b >= 0 && h > 0 && w > 0 && n_cams >= 1, "proj_err_norm: bad size b=%d h=%d w=%d n_cams=%d", b, h, w,
+                 n_cams);
     if (b == 0) return MPSR_OK;
     MPSR_REQUIRE(xyz_global && boxes_2d && cam_p && valid_mask && proj_err_norm, "proj_err_norm: null pointer");
     hipLaunchKernelGGL(proj_err_kernel<0>, dim3(b), dim3(kThreads), 0, mpsr::as_stream(stream), xyz_global, boxes_2d,
-                       cam_p, valid_mask, (const float *)nullptr, proj_err_maps, proj_err_norm, h, w);
+                       cam_p, cam_index, n_cams, valid_mask, (const float *)nullptr, proj_err_maps, proj_err_norm, h, w);
     MPSR_CHECK_LAUNCH("proj_err_norm");
+    return MPSR_OK;
+}
+
+int mpsr_proj_err_norm(const float *xyz_global, const float *boxes_2d, const float *cam_p, const float *valid_mask,
+                       float *proj_err_maps, float *proj_err_norm, int b, int h, int w, mpsr_stream_t stream)
+{
+    return mpsr_proj_err_norm_cams(xyz_global, boxes_2d, cam_p, 1, nullptr, valid_mask, proj_err_maps, proj_err_norm, b,
+                                   h, w, stream);
+}
+
+int mpsr_proj_err_norm_grad_cams(const float *grad_proj_err_norm, const float *xyz_global, const float *boxes_2d,
+                                 const float *cam_p, int n_cams, const int *cam_index, const float *valid_mask,
+                                 float *grad_xyz_global, int b, int h, int w, mpsr_stream_t stream)
+{
+    MPSR_REQUIRE(b >= 0 && h > 0 && w > 0 && n_cams >= 1, "proj_err_norm_grad: bad size b=%d h=%d w=%d n_cams=%d", b, h,
+                 w, n_cams);
+    if (b == 0) return MPSR_OK;
+    MPSR_REQUIRE(grad_proj_err_norm && xyz_global && boxes_2d && cam_p && valid_mask && grad_xyz_global,
+                 "proj_err_norm_grad: null pointer");
+    hipLaunchKernelGGL(proj_err_kernel<1>, dim3(b), dim3(kThreads), 0, mpsr::as_stream(stream), xyz_global, boxes_2d,
+                       cam_p, cam_index, n_cams, valid_mask, grad_proj_err_norm, (float *)nullptr, grad_xyz_global, h, w);
+    MPSR_CHECK_LAUNCH("proj_err_norm_grad");
     return MPSR_OK;
 }
 
@@ -397,19 +454,14 @@ int mpsr_proj_err_norm_grad(const float *grad_proj_err_norm, const float *xyz_gl
                             const float *cam_p, const float *valid_mask, float *grad_xyz_global, int b, int h, int w,
                             mpsr_stream_t stream)
 {
-    MPSR_REQUIRE(b >= 0 && h > 0 && w > 0, "proj_err_norm_grad: bad size b=%d h=%d w=%d", b, h, w);
-    if (b == 0) return MPSR_OK;
-    MPSR_REQUIRE(grad_proj_err_norm && xyz_global && boxes_2d && cam_p && valid_mask && grad_xyz_global,
-                 "proj_err_norm_grad: null pointer");
-    hipLaunchKernelGGL(proj_err_kernel<1>, dim3(b), dim3(kThreads), 0, mpsr::as_stream(stream), xyz_global, boxes_2d,
-                       cam_p, valid_mask, grad_proj_err_norm, (float *)nullptr, grad_xyz_global, h, w);
-    MPSR_CHECK_LAUNCH("proj_err_norm_grad");
-    return MPSR_OK;
+    return mpsr_proj_err_norm_grad_cams(grad_proj_err_norm, xyz_global, boxes_2d, cam_p, 1, nullptr, valid_mask,
+                                        grad_xyz_global, b, h, w, stream);
 }
 
-int mpsr_depth_map_local_to_global(const float *depth_local, int depth_stride, const float *cen_z,
-                                   const float *boxes_2d, const float *view_angs, const float *cam_p,
-                                   float *depth_global, int b, int h, int w, int rotate_view, mpsr_stream_t stream)
+int mpsr_depth_map_local_to_global_cams(const float *depth_local, int depth_stride, const float *cen_z,
+                                        const float *boxes_2d, const float *view_angs, const float *cam_p, int n_cams,
+                                        const int *cam_index, float *depth_global, int b, int h, int w,
+                                        int rotate_view, mpsr_stream_t stream)
 {
     MPSR_REQUIRE(b >= 0 && h > 0 && w > 0 && depth_stride >= 1, "depth_map_local_to_global: bad size b=%d h=%d w=%d",
                  b, h, w);
@@ -417,10 +469,35 @@ int mpsr_depth_map_local_to_global(const float *depth_local, int depth_stride, c
     MPSR_REQUIRE(depth_local && cen_z && depth_global, "depth_map_local_to_global: null pointer");
     MPSR_REQUIRE(!rotate_view || (boxes_2d && view_angs && cam_p),
                  "depth_map_local_to_global: rotate_view needs boxes_2d, view_angs and cam_p");
+    MPSR_REQUIRE(!rotate_view || n_cams >= 1, "depth_map_local_to_global: n_cams = %d", n_cams);
     hipLaunchKernelGGL(depth_global_kernel, dim3(mpsr::ceil_div(h * w, kThreads), b), dim3(kThreads), 0,
-                       mpsr::as_stream(stream), depth_local, depth_stride, cen_z, boxes_2d, view_angs, cam_p,
-                       depth_global, h, w, rotate_view);
+                       mpsr::as_stream(stream), depth_local, depth_stride, cen_z, boxes_2d, view_angs, cam_p, cam_index,
+                       n_cams, depth_global, h, w, rotate_view);
     MPSR_CHECK_LAUNCH("depth_map_local_to_global");
+    return MPSR_OK;
+}
+
+int mpsr_depth_map_local_to_global(const float *depth_local, int depth_stride, const float *cen_z,
+                                   const float *boxes_2d, const float *view_angs, const float *cam_p,
+                                   float *depth_global, int b, int h, int w, int rotate_view, mpsr_stream_t stream)
+{
+    return mpsr_depth_map_local_to_global_cams(depth_local, depth_stride, cen_z, boxes_2d, view_angs, cam_p, 1, nullptr,
+                                               depth_global, b, h, w, rotate_view, stream);
+}
+
+int mpsr_depth_map_local_to_global_grad_cams(const float *grad_global, const float *boxes_2d, const float *view_angs,
+                                             const float *cam_p, int n_cams, const int *cam_index, float *grad_cen_z,
+                                             int b, int h, int w, int rotate_view, mpsr_stream_t stream)
+{
+    MPSR_REQUIRE(b >= 0 && h > 0 && w > 0, "depth_map_local_to_global_grad: bad size b=%d h=%d w=%d", b, h, w);
+    if (b == 0) return MPSR_OK;
+    MPSR_REQUIRE(grad_global && grad_cen_z, "depth_map_local_to_global_grad: null pointer");
+    MPSR_REQUIRE(!rotate_view || (boxes_2d && view_angs && cam_p),
+                 "depth_map_local_to_global_grad: rotate_view needs boxes_2d, view_angs and cam_p");
+    MPSR_REQUIRE(!rotate_view || n_cams >= 1, "depth_map_local_to_global_grad: n_cams = %d", n_cams);
+    hipLaunchKernelGGL(depth_global_grad_kernel, dim3(b), dim3(kThreads), 0, mpsr::as_stream(stream), grad_global,
+                       boxes_2d, view_angs, cam_p, cam_index, n_cams, grad_cen_z, h, w, rotate_view);
+    MPSR_CHECK_LAUNCH("depth_map_local_to_global_grad");
     return MPSR_OK;
 }
 
@@ -428,15 +505,8 @@ int mpsr_depth_map_local_to_global_grad(const float *grad_global, const float *b
                                         const float *cam_p, float *grad_cen_z, int b, int h, int w, int rotate_view,
                                         mpsr_stream_t stream)
 {
-    MPSR_REQUIRE(b >= 0 && h > 0 && w > 0, "depth_map_local_to_global_grad: bad size b=%d h=%d w=%d", b, h, w);
-    if (b == 0) return MPSR_OK;
-    MPSR_REQUIRE(grad_global && grad_cen_z, "depth_map_local_to_global_grad: null pointer");
-    MPSR_REQUIRE(!rotate_view || (boxes_2d && view_angs && cam_p),
-                 "depth_map_local_to_global_grad: rotate_view needs boxes_2d, view_angs and cam_p");
-    hipLaunchKernelGGL(depth_global_grad_kernel, dim3(b), dim3(kThreads), 0, mpsr::as_stream(stream), grad_global,
-                       boxes_2d, view_angs, cam_p, grad_cen_z, h, w, rotate_view);
-    MPSR_CHECK_LAUNCH("depth_map_local_to_global_grad");
-    return MPSR_OK;
+    return mpsr_depth_map_local_to_global_grad_cams(grad_global, boxes_2d, view_angs, cam_p, 1, nullptr, grad_cen_z, b,
+                                                    h, w, rotate_view, stream);
 }
 
 int mpsr_huber_loss_sums(const float *pred, const float *target, const float *weights, int b, int p, int c,
@@ -458,9 +528,22 @@ int mpsr_huber_loss_grad(const float *pred, const float *target, const float *we
     const long long n = (long long)b * p * c;
     if (n == 0) return MPSR_OK;
     MPSR_REQUIRE(pred && target && weights && scale && grad, "huber_loss_grad: null pointer");
-    hipLaunchKernelGGL(huber_grad_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                       mpsr::as_stream(stream), pred, target, weights, scale, n, c, delta, grad);
+    hipLaunchKernelGGL(huber_grad_kernel<false>, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       mpsr::as_stream(stream), pred, target, weights, scale, n, (long long)p * c, c, delta, grad);
     MPSR_CHECK_LAUNCH("huber_loss_grad");
+    return MPSR_OK;
+}
+
+int mpsr_huber_loss_grad_scales(const float *pred, const float *target, const float *weights, const float *scale,
+                                int b, int p, int c, float delta, float *grad, mpsr_stream_t stream)
+{
+    MPSR_REQUIRE(b >= 0 && p >= 0 && c >= 1 && delta > 0.f, "huber_loss_grad_scales: bad size b=%d p=%d c=%d", b, p, c);
+    const long long n = (long long)b * p * c;
+    if (n == 0) return MPSR_OK;
+    MPSR_REQUIRE(pred && target && weights && scale && grad, "huber_loss_grad_scales: null pointer");
+    hipLaunchKernelGGL(huber_grad_kernel<true>, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       mpsr::as_stream(stream), pred, target, weights, scale, n, (long long)p * c, c, delta, grad);
+    MPSR_CHECK_LAUNCH("huber_loss_grad_scales");
     return MPSR_OK;
 }
 

@@ -71,9 +71,22 @@ def tf_inst_xyz_map_local_to_global(inst_xyz_map_local, map_roi_size, view_angs,
     return _XyzLocalToGlobal.apply(inst_xyz_map_local, view_angs, centroids)
 
 
+def _cam_index(cam_index):
+    return None if cam_index is None else cam_index.reshape(-1).to(torch.int32).contiguous()
+
+
+def _check_cams(cam_p, cam_index, n):
+    """cam_p (3,4) without an index, (n_cams,3,4) with cam_index (n)."""
+    if cam_index is None:
+        if cam_p.numel() != 12:
+            raise _lib.InvalidArgumentError("cam_p must be (3,4); per-box cameras (n_cams,3,4) need cam_index")
+    elif cam_p.numel() == 0 or cam_p.numel() % 12 or cam_index.numel() != n:
+        raise _lib.InvalidArgumentError("per-box cameras: cam_p must be (n_cams,3,4) and cam_index (N)")
+
+
 class _DepthLocalToGlobal(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, depth_local, global_depth, box_2d, inst_view_ang, cam_p, rotate_view):
+    def forward(ctx, depth_local, global_depth, box_2d, inst_view_ang, cam_p, rotate_view, cam_index=None):
         n, h, w = depth_local.shape[:3]
         # a (N,H,W,1) slice of an xyz map is read in place through its channel stride
         if depth_local.dim() == 4 and depth_local.stride(3) == 1 and depth_local.stride(2) > 1 and \
@@ -87,54 +100,77 @@ class _DepthLocalToGlobal(torch.autograd.Function):
         boxes = _f32(box_2d) if rotate_view else None
         va = _f32(inst_view_ang).reshape(-1) if rotate_view else None
         cam = _f32(cam_p).reshape(-1) if rotate_view else None
-        _lib.check(_lib.lib().mpsr_depth_map_local_to_global(src.data_ptr(), stride, _lib.ptr(z), _lib.ptr(boxes),
-                                                             _lib.ptr(va), _lib.ptr(cam), _lib.ptr(out), n, h, w,
-                                                             int(bool(rotate_view)), _lib.stream()))
-        ctx.save_for_backward(*(t for t in (boxes, va, cam) if t is not None))
+        idx = _cam_index(cam_index) if rotate_view else None
+        if idx is None:
+            _lib.check(_lib.lib().mpsr_depth_map_local_to_global(src.data_ptr(), stride, _lib.ptr(z), _lib.ptr(boxes),
+                                                                 _lib.ptr(va), _lib.ptr(cam), _lib.ptr(out), n, h, w,
+                                                                 int(bool(rotate_view)), _lib.stream()))
+        else:
+            _lib.check(_lib.lib().mpsr_depth_map_local_to_global_cams(
+                src.data_ptr(), stride, _lib.ptr(z), _lib.ptr(boxes), _lib.ptr(va), _lib.ptr(cam), cam.numel() // 12,
+                _lib.ptr(idx), _lib.ptr(out), n, h, w, 1, _lib.stream()))
+        ctx.save_for_backward(*(t for t in (boxes, va, cam, idx) if t is not None))
         ctx.meta = (n, h, w, bool(rotate_view), tuple(global_depth.shape))
         return out
 
     @staticmethod
     def backward(ctx, g):
         n, h, w, rotate, zshape = ctx.meta
-        boxes, va, cam = ctx.saved_tensors if rotate else (None, None, None)
+        boxes, va, cam, idx = (tuple(ctx.saved_tensors) + (None,))[:4] if rotate else (None, None, None, None)
         g = _f32(g)
         gz = None
         if ctx.needs_input_grad[1]:
             gz = torch.empty((n,), dtype=torch.float32, device=g.device)
-            _lib.check(_lib.lib().mpsr_depth_map_local_to_global_grad(_lib.ptr(g), _lib.ptr(boxes), _lib.ptr(va),
-                                                                      _lib.ptr(cam), _lib.ptr(gz), n, h, w,
-                                                                      int(rotate), _lib.stream()))
+            if idx is None:
+                _lib.check(_lib.lib().mpsr_depth_map_local_to_global_grad(_lib.ptr(g), _lib.ptr(boxes), _lib.ptr(va),
+                                                                          _lib.ptr(cam), _lib.ptr(gz), n, h, w,
+                                                                          int(rotate), _lib.stream()))
+            else:
+                _lib.check(_lib.lib().mpsr_depth_map_local_to_global_grad_cams(
+                    _lib.ptr(g), _lib.ptr(boxes), _lib.ptr(va), _lib.ptr(cam), cam.numel() // 12, _lib.ptr(idx),
+                    _lib.ptr(gz), n, h, w, 1, _lib.stream()))
             gz = gz.reshape(zshape)
-        return (g if ctx.needs_input_grad[0] else None), gz, None, None, None, None
+        return (g if ctx.needs_input_grad[0] else None), gz, None, None, None, None, None
 
 
 def tf_inst_depth_map_local_to_global(inst_depth_map_local, global_depth, box_2d=None, inst_view_ang=None,
-                                      map_roi_size=None, cam_p=None, rotate_view=False):
+                                      map_roi_size=None, cam_p=None, rotate_view=False, cam_index=None):
     """instance_utils.py:605-680.  (N,H,W,1) local depth + (N,1) centroid depth -> (N,H,W,1) global depth; with
     rotate_view the view-normalisation offset is added (interpolated between the box's edge rays with H samples
-    and laid out along the ROW axis, exactly as the reference does)."""
+    and laid out along the ROW axis, exactly as the reference does).
+    cam_index (N) int32 with cam_p (n_cams,3,4): the boxes of several frames, each with its frame's camera
+    (mpsr_depth_map_local_to_global_cams); without it cam_p is one (3,4) matrix, as in the reference."""
     if inst_depth_map_local.dim() != 4 or inst_depth_map_local.shape[3] != 1:
         raise _lib.InvalidArgumentError("inst_depth_map_local must be (N, H, W, 1)")
     if rotate_view and (box_2d is None or inst_view_ang is None or cam_p is None):
         raise _lib.InvalidArgumentError("rotate_view needs box_2d, inst_view_ang and cam_p")
     if map_roi_size is not None and tuple(inst_depth_map_local.shape[1:3]) != tuple(map_roi_size):
         raise _lib.InvalidArgumentError("inst_depth_map_local does not match map_roi_size")
-    return _DepthLocalToGlobal.apply(inst_depth_map_local, global_depth, box_2d, inst_view_ang, cam_p, rotate_view)
+    if rotate_view:
+        _check_cams(cam_p, cam_index, inst_depth_map_local.shape[0])
+    return _DepthLocalToGlobal.apply(inst_depth_map_local, global_depth, box_2d, inst_view_ang, cam_p, rotate_view,
+                                     cam_index)
 
 
 class _ProjErrNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xyz_global, boxes_2d, cam_p, valid_mask, want_maps):
+    def forward(ctx, xyz_global, boxes_2d, cam_p, valid_mask, want_maps, cam_index=None):
         n, h, w = xyz_global.shape[:3]
         xyz_global, boxes_2d = _f32(xyz_global), _f32(boxes_2d)
         cam_p, valid_mask = _f32(cam_p).reshape(-1), _f32(valid_mask).reshape(n, h, w)
         norm = torch.empty((n,), dtype=torch.float32, device=xyz_global.device)
         maps = torch.empty((n, h, w, 2), dtype=torch.float32, device=xyz_global.device) if want_maps else None
-        _lib.check(_lib.lib().mpsr_proj_err_norm(_lib.ptr(xyz_global), _lib.ptr(boxes_2d), _lib.ptr(cam_p),
-                                                 _lib.ptr(valid_mask), _lib.ptr(maps), _lib.ptr(norm), n, h, w,
-                                                 _lib.stream()))
-        ctx.save_for_backward(xyz_global, boxes_2d, cam_p, valid_mask)
+        idx = _cam_index(cam_index)
+        if idx is None:
+            _lib.check(_lib.lib().mpsr_proj_err_norm(_lib.ptr(xyz_global), _lib.ptr(boxes_2d), _lib.ptr(cam_p),
+                                                     _lib.ptr(valid_mask), _lib.ptr(maps), _lib.ptr(norm), n, h, w,
+                                                     _lib.stream()))
+            ctx.save_for_backward(xyz_global, boxes_2d, cam_p, valid_mask)
+        else:
+            _lib.check(_lib.lib().mpsr_proj_err_norm_cams(_lib.ptr(xyz_global), _lib.ptr(boxes_2d), _lib.ptr(cam_p),
+                                                          cam_p.numel() // 12, _lib.ptr(idx), _lib.ptr(valid_mask),
+                                                          _lib.ptr(maps), _lib.ptr(norm), n, h, w, _lib.stream()))
+            ctx.save_for_backward(xyz_global, boxes_2d, cam_p, valid_mask, idx)
         if maps is None:
             maps = norm.new_empty(0)
         ctx.mark_non_differentiable(maps)
@@ -142,25 +178,35 @@ class _ProjErrNorm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gnorm, _gmaps):
-        xyz_global, boxes_2d, cam_p, valid_mask = ctx.saved_tensors
+        xyz_global, boxes_2d, cam_p, valid_mask, idx = (tuple(ctx.saved_tensors) + (None,))[:5]
         n, h, w = xyz_global.shape[:3]
         gx = torch.empty_like(xyz_global)
-        _lib.check(_lib.lib().mpsr_proj_err_norm_grad(_lib.ptr(_f32(gnorm)), _lib.ptr(xyz_global), _lib.ptr(boxes_2d),
-                                                      _lib.ptr(cam_p), _lib.ptr(valid_mask), _lib.ptr(gx), n, h, w,
-                                                      _lib.stream()))
-        return gx, None, None, None, None
+        if idx is None:
+            _lib.check(_lib.lib().mpsr_proj_err_norm_grad(_lib.ptr(_f32(gnorm)), _lib.ptr(xyz_global),
+                                                          _lib.ptr(boxes_2d), _lib.ptr(cam_p), _lib.ptr(valid_mask),
+                                                          _lib.ptr(gx), n, h, w, _lib.stream()))
+        else:
+            _lib.check(_lib.lib().mpsr_proj_err_norm_grad_cams(
+                _lib.ptr(_f32(gnorm)), _lib.ptr(xyz_global), _lib.ptr(boxes_2d), _lib.ptr(cam_p), cam_p.numel() // 12,
+                _lib.ptr(idx), _lib.ptr(valid_mask), _lib.ptr(gx), n, h, w, _lib.stream()))
+        return gx, None, None, None, None, None
 
 
-def proj_err_maps_norm(pred_inst_xyz_map_global, pred_boxes_2d, cam_p, valid_mask_maps, want_maps=False):
+def proj_err_maps_norm(pred_inst_xyz_map_global, pred_boxes_2d, cam_p, valid_mask_maps, want_maps=False,
+                       cam_index=None):
     """The arithmetic of monopsr_output_builder.py:681-746 (get_proj_err_maps_norm) -> (proj_err_norm (N,),
-    proj_err_maps_norm (N,H,W,2) or None).  Differentiable w.r.t. the global map."""
+    proj_err_maps_norm (N,H,W,2) or None).  Differentiable w.r.t. the global map.
+    cam_index (N) int32 with cam_p (n_cams,3,4): each box projected with its own frame's camera
+    (mpsr_proj_err_norm_cams); without it cam_p is one (3,4) matrix, as in the reference."""
     if pred_inst_xyz_map_global.dim() != 4 or pred_inst_xyz_map_global.shape[3] != 3:
         raise _lib.InvalidArgumentError("pred_inst_xyz_map_global must be (N, H, W, 3)")
     n = pred_inst_xyz_map_global.shape[0]
-    if tuple(pred_boxes_2d.shape) != (n, 4) or cam_p.numel() != 12 or \
+    if tuple(pred_boxes_2d.shape) != (n, 4) or (cam_index is None and cam_p.numel() != 12) or \
             valid_mask_maps.numel() != pred_inst_xyz_map_global.numel() // 3:
         raise _lib.InvalidArgumentError("boxes_2d must be (N,4), cam_p (3,4), valid_mask_maps (N,H,W,1)")
-    norm, maps = _ProjErrNorm.apply(pred_inst_xyz_map_global, pred_boxes_2d, cam_p, valid_mask_maps, want_maps)
+    _check_cams(cam_p, cam_index, n)
+    norm, maps = _ProjErrNorm.apply(pred_inst_xyz_map_global, pred_boxes_2d, cam_p, valid_mask_maps, want_maps,
+                                    cam_index)
     return norm, (maps if want_maps else None)
 
 

@@ -3,6 +3,7 @@ forward + Chamfer / smooth-L1 losses + backward + gradient all-reduce (RCCL when
 Adam, synthetic inputs of BASELINE config 4 (256 crops per GPU, 1024-pt... here the full 2304-pt map vs GT map).
 
     python tools/train_bench.py [--batch 256] [--steps 5]
+    python tools/train_bench.py --full-image --batch 32 --frames 8     (InstanceTrainer.step_batch: 8 frames x 32 boxes)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/train_bench.py
 """
 import argparse
@@ -38,6 +39,10 @@ def main():
     ap.add_argument("--full-image", action="store_true",
                     help="train BOTH trunks from a raw 375x1242 image + `--batch` boxes (the reference's step shape at "
                          "--batch 32) instead of the crop trunk over a precomputed full-image feature crop")
+    ap.add_argument("--frames", type=int, default=0,
+                    help="with --full-image: N synthetic frames per step (different images, sizes and cameras), `--batch` "
+                         "boxes each, through InstanceTrainer.step_batch; the line gains ms_per_frame.  0 = step() on one "
+                         "frame")
     ap.add_argument("--wgrad-winograd", type=int, default=1, choices=[0, 1],
                     help="A/B: 0 = every weight gradient on the direct kernel (mpsr_debug_set_wgrad_winograd), 1 = the "
                          "decoder's dense 3x3 layers in the F(4x4,3x3) domain and block3's atrous layers in F(3x3,3x3)")
@@ -74,6 +79,8 @@ def main():
     ap.add_argument("--wgrad-direct", action="store_true",
                     help="A/B: 1x1 weight gradients on the LDS-free kernel (mpsr_debug_set_wgrad_direct(1))")
     args = ap.parse_args()
+    if args.frames < 0 or (args.frames and not args.full_image):
+        ap.error("--frames N (N >= 1) needs --full-image")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -134,13 +141,30 @@ def main():
         sample["rgb_image"] = torch.randint(0, 256, (375, 1242, 3), device=dev, generator=g).float()
         sample["boxes_2d_norm"] = sample["boxes_2d"] / torch.tensor([375.0, 1242.0, 375.0, 1242.0], device=dev)
     sample.update(trainer.synthetic_ground_truth(sample, seed=7 + rank))
+    frames = [sample]
+    for f in range(1, args.frames):  # further frames: other boxes, image, image size and camera
+        fi, _ = bench.make_inputs(B, 1024, rank + 17 * f, dev)
+        H, Wd = 375 - (f % 3), 1242 - 2 * (f % 5)
+        cam = fi["cam_p"].clone()
+        cam[0, 0] += 1.5 * f
+        cam[1, 1] += 1.5 * f
+        cam[0, 2] -= 0.75 * f
+        cam[0, 3] += 0.1 * f
+        s = dict(boxes_2d=fi["boxes"], cam_p=cam, est_view_angs=fi["view"], class_indices=fi["cls"],
+                 mean_lwh=fi["mean_lwh"], prop_cen_z_offset=fi["z_off"])
+        g = torch.Generator(device=dev).manual_seed(11 + rank + 100 * f)
+        s["rgb_image"] = torch.randint(0, 256, (H, Wd, 3), device=dev, generator=g).float()
+        s["boxes_2d_norm"] = s["boxes_2d"] / torch.tensor([float(H), float(Wd), float(H), float(Wd)], device=dev)
+        s.update(trainer.synthetic_ground_truth(s, seed=7 + rank + 100 * f))
+        frames.append(s)
+    step = (lambda: tr.step_batch(frames)) if args.frames else (lambda: tr.step(sample))
     losses = []
     if args.main_high_priority:
         hp = torch.cuda.Stream(device=dev, priority=-1)
         hp.wait_stream(torch.cuda.current_stream(dev))
         torch.cuda.set_stream(hp)
     for _ in range(args.warmup):
-        losses.append(float(tr.step(sample)))
+        losses.append(float(step()))
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
@@ -148,15 +172,22 @@ def main():
     host = 0.0
     for _ in range(args.steps):
         h0 = time.perf_counter()
-        losses.append(tr.step(sample))
+        losses.append(step())
         host += time.perf_counter() - h0  # (the call returns when everything is enqueued: the host's share of a step)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     dt = time.perf_counter() - t0
+    n_frames = max(args.frames, 1)
+    extra = {}
+    if args.frames:
+        extra = {"frames": args.frames, "boxes_per_frame": B,
+                 "ms_per_frame": round(1e3 * dt / args.steps / args.frames, 2),
+                 "peak_memory_mib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 20, 1)}
     if rank == 0:
         print(json.dumps({"metric": "instance-crops/sec (train: fwd+bwd+allreduce+Adam)",
-                          "value": round(B * world * args.steps / dt, 1), "unit": "crops/s", "n_gpus": world,
+                          "value": round(B * n_frames * world * args.steps / dt, 1), "unit": "crops/s", "n_gpus": world,
+                          **extra,
                           "host_enqueue_ms_per_step": round(1e3 * host / args.steps, 2),
                           "ms_per_step": round(1e3 * dt / args.steps, 2), "params": int(net.params.numel()),
                           "grad_bytes": int(net.grads.numel() * 4),
