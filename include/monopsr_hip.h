@@ -936,6 +936,27 @@ int mpsr_kitti_detection_rows(const float *box_3d, const float *box_2d, const in
                               const int *image_wh, int n, int n_frames, double score_threshold, int project,
                               double *rows, int *cls, int *keep, mpsr_stream_t stream);
 
+/* ---- The evaluator's per-object error statistics (additive to ABI 13) ----
+ * The reference's save_metrics (core/evaluator_utils.py:294-403) over a device-resident table: values (n_rows, n_cols)
+ * float32, row-major, one row per object; frame (n_rows) int32 in [0, n_frames), the rows of a frame in any order and
+ * not necessarily adjacent.  column_metric (n_cols) is a HOST array: column c feeds metric column_metric[c] in
+ * [0, n_metrics); several columns may feed one metric (its values are then the columns flattened), a metric without a
+ * column has count 0.  n_cols <= MPSR_METRIC_STATS_MAX_COLS.
+ * nan_rule MPSR_NAN_RULE_ENTRY leaves out the NaN entries alone; frame, n_frames and frame_flags are not used and may
+ * be null / 0.  MPSR_NAN_RULE_FRAME is the reference's rule (core/evaluator.py:270-281): one NaN among a frame's values
+ * of a metric, over all the metric's columns, leaves out all of that frame's values of that metric; a row whose frame
+ * is outside [0, n_frames) is left out as well.  frame_flags: caller-owned scratch of n_metrics * n_frames int32,
+ * overwritten.
+ * stats (n_metrics, 6) fp64: count, mean, std (population, np.std), mean of |x|, std of |x|, dropped = the number of
+ * values left out.  count 0 gives NaN in the four statistics.  Every element is written on every call (n_rows == 0
+ * included).  fp64 throughout, two passes (the mean, then the centred squares), one workgroup per metric, a fixed
+ * summation order and no atomics: two calls on one table return the same bits.  DESIGN.md section 7.5. */
+enum { MPSR_NAN_RULE_ENTRY = 0, MPSR_NAN_RULE_FRAME = 1 };
+#define MPSR_METRIC_STATS_MAX_COLS 32
+int mpsr_metric_stats(const float *values, const int *frame, int n_rows, int n_cols, const int *column_metric,
+                      int n_metrics, int n_frames, int nan_rule, int *frame_flags, double *stats,
+                      mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,7 @@ SIGNATURES = {
     "mpsr_merge_detections": (c_i, [c_f, c_f, c_f, ctypes.c_longlong, c_f, c_f, c_f, ctypes.c_longlong, c_i,
                                     ctypes.c_double, c_i, c_f, c_f, c_f, c_f]),
     "mpsr_kitti_detection_rows": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_double, c_i, c_f, c_f, c_f, c_f]),
+    "mpsr_metric_stats": (c_i, [c_f, c_f, c_i, c_i, ctypes.POINTER(c_i), c_i, c_i, c_i, c_f, c_f, c_f]),
 }
 
 

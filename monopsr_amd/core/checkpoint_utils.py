@@ -88,6 +88,19 @@ def save_checkpoint(prefix, weights, global_step=None):
     return prefix
 
 
+def list_checkpoints(checkpoint_dir):
+    """[(step, prefix)] of every `<name>-<step, 8 digits>.index` in a directory, ordered by step (then by name).  The
+    directory's `checkpoint` state file names only the latest one and is not consulted."""
+    import os
+    import re
+    found = []
+    for entry in os.listdir(checkpoint_dir):
+        m = re.match(r"^(.+)-(\d{8})\.index$", entry)
+        if m:
+            found.append((int(m.group(2)), os.path.join(checkpoint_dir, entry[:-len(".index")])))
+    return sorted(found)
+
+
 def load_npz(path):
     with np.load(path) as f:
         return {k: f[k] for k in f.files}

@@ -14,11 +14,23 @@ detection and its ground truth counts as missed, as in the reference, which writ
 In 'val' mode it also reports the means of the per-object EMD / Chamfer metrics and of the loss terms
 (MonoPSRModel.loss on the 'val'-mode build of each frame), accumulated on the device; NaN entries are skipped.
 
-Not built: checkpoint sweeps, the metrics CSV, TF summaries.
+With metric_stats=True it also keeps one row per object of the reference's eight metrics (METRIC_COLUMNS) in a device
+table and takes count / mean / std / mean |x| / std |x| of each in one mpsr_metric_stats launch at the end, under the
+reference's NaN rule (a NaN drops its frame's values of that metric): result['metric_stats'], and with
+predictions_base_dir the four metrics CSVs of the reference's save_metrics (evaluator_utils.save_metric_stats).
+
+Checkpoint sweeps (the reference's run_latest_checkpoints / repeated_checkpoint_run, core/evaluator.py:387-526):
+run_latest_checkpoints and repeated_checkpoint_run over checkpoint_utils.list_checkpoints, with the evaluated steps kept
+in <predictions_base_dir>/evaluated_<split>.txt and every report in kitti_reports/<split>/.  The order and the skipping
+are sweep_checkpoints / repeated_sweep, plain functions of a checkpoint list, the evaluated set and a callable.
+python -m monopsr_amd.experiments.run_evaluation is the command line of a sweep.
+
+Not built: TF summaries and metrics_to_show, both IoU settings in one pass.
 """
 import argparse
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -30,11 +42,67 @@ from monopsr_amd.datasets.kitti import instance_utils
 # truncation and occlusion: alpha | x1 y1 x2 y2 | h w l | x y z | ry score
 _LINE_COLUMNS = [4, 0, 1, 2, 3, 5, 6, 7, 8, 9, 10, 11, 12]
 
+# the metric table's columns, in order: (metric, number of columns).  The three columns of the dimension error are one
+# metric: the reference flattens them into one list.
+METRIC_COLUMNS = ((constants.METRIC_EMD, 1), (constants.METRIC_CHAMFER, 1), (constants.METRIC_VIEW_ANG_ERR, 1),
+                  (constants.METRIC_PROP_CEN_Z_ERR, 1), (constants.METRIC_CEN_X_ERR, 1), (constants.METRIC_CEN_Y_ERR, 1),
+                  (constants.METRIC_CEN_Z_ERR, 1), (constants.METRIC_DIM_ERR, 3))
+METRIC_NAMES = tuple(name for name, _ in METRIC_COLUMNS)
+COLUMN_METRIC = tuple(k for k, (_, width) in enumerate(METRIC_COLUMNS) for _ in range(width))
+
+
+def sweep_checkpoints(checkpoints, evaluated, run, ckpt_indices=None):
+    """The order and the skipping of a sweep.  checkpoints: [(step, prefix)]; evaluated: a set of steps, updated in
+    place; run(step, prefix) evaluates one.  ckpt_indices None: every checkpoint whose step is not in `evaluated`, in
+    step order; -1 (or [-1]): the latest; otherwise the listed steps, in the order given (a step that is no checkpoint
+    is a KeyError naming it, raised before anything runs).  Listed steps and the latest run whether evaluated before
+    or not, as in the reference.  -> [run's results]."""
+    by_step = dict(checkpoints)
+    if ckpt_indices is None:
+        todo = [step for step in sorted(by_step) if step not in evaluated]
+    else:
+        wanted = [int(i) for i in np.atleast_1d(np.asarray(ckpt_indices))]
+        todo = []
+        for i in wanted:
+            if i == -1:
+                if not by_step:
+                    raise KeyError('no checkpoint to take the latest of')
+                i = max(by_step)
+            if i not in by_step:
+                raise KeyError('no checkpoint of step %d (there are: %s)' % (i, sorted(by_step)))
+            todo.append(i)
+    results = []
+    for step in todo:
+        results.append(run(step, by_step[step]))
+        evaluated.add(step)
+    return results
+
+
+def repeated_sweep(list_checkpoints, evaluated, run, max_iterations, eval_wait_interval=30, max_idle_seconds=None,
+                   sleep=time.sleep, clock=time.monotonic):
+    """Lists (list_checkpoints() -> [(step, prefix)]), evaluates what is new with sweep_checkpoints, and sleeps
+    eval_wait_interval seconds when nothing is.  Returns the results once a step >= max_iterations is in `evaluated`,
+    or once max_idle_seconds (None: never) have passed without a new checkpoint."""
+    results = []
+    last_new = clock()
+    while True:
+        new = sweep_checkpoints(list_checkpoints(), evaluated, run)
+        results.extend(new)
+        if evaluated and max(evaluated) >= max_iterations:
+            return results
+        if new:
+            last_new = clock()
+            continue
+        if max_idle_seconds is not None and clock() - last_new >= max_idle_seconds:
+            return results
+        sleep(eval_wait_interval)
+
 
 class Evaluator:
 
     def __init__(self, model, dataset, score_threshold=0.1, predictions_base_dir=None, batch_size=8,
-                 project_3d_box=False, iou='standard', compute_metrics=True, compute_losses=True):
+                 project_3d_box=False, iou='standard', compute_metrics=True, compute_losses=True, metric_stats=False,
+                 skip_evaluated_checkpoints=True):
         if iou not in kitti_eval.MIN_OVERLAP:
             raise ValueError('iou must be one of %s' % sorted(kitti_eval.MIN_OVERLAP))
         if int(batch_size) < 1:
@@ -45,6 +113,10 @@ class Evaluator:
         self.model = model
         self.compute_metrics = bool(compute_metrics)
         self.compute_losses = bool(compute_losses)
+        self.metric_stats = bool(metric_stats)
+        self.skip_evaluated_checkpoints = bool(skip_evaluated_checkpoints)
+        # after a run_once with metric_stats: (values (n,10) float32, frame (n,) int32) on the device
+        self.metric_table = None
         self._loss_model = None
         self.dataset = dataset
         self.score_threshold = round(float(score_threshold), 3)
@@ -58,7 +130,7 @@ class Evaluator:
     def _predict(self):
         """-> (box_3d (N,9), box_2d (N,7), frame (N,) int32: rows of the dataset's frame tables; metric sums (2,2):
         [emd, chamfer] x [sum of the entries that are not NaN, their number]; loss names and their sums (n,2) in the
-        same form), all on the device."""
+        same form; the metric table (N, 10) float32 in METRIC_COLUMNS' order, or None), all on the device."""
         ds, model = self.dataset, self.model
         dev = ds.device
         # the frames in split order, whatever the epoch's shuffle made of sample_list
@@ -67,8 +139,10 @@ class Evaluator:
         sums = torch.zeros((2, 2), dtype=torch.float64, device=dev)
         with_metrics = ds.train_val_test == 'val' and self.compute_metrics
         with_losses = ds.train_val_test == 'val' and self.compute_losses
+        with_table = ds.train_val_test == 'val' and self.metric_stats
         loss_names, loss_sums = [], None
-        if with_losses:
+        table = []
+        if with_losses or with_table:
             # the 'val'-mode graph of the same net: method by method, with the ground truth and the offsets
             from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
             if self._loss_model is None:
@@ -90,7 +164,7 @@ class Evaluator:
                     b3s.append(b3[0:n])
                     b2s.append(b2[0:n])
                     frames.append(torch.full((n,), int(r), dtype=torch.int32, device=dev))
-                    if with_metrics:
+                    if with_metrics or with_table:
                         m = model.evaluate_predictions(
                             {constants.KEY_INST_XYZ_MAP_LOCAL: o[constants.KEY_INST_XYZ_MAP_LOCAL]},
                             {constants.KEY_INST_XYZ_MAP_LOCAL: s['gt_inst_xyz_maps_local'],
@@ -100,9 +174,19 @@ class Evaluator:
                             ok = ~torch.isnan(v)  # the reference's np.nanmean
                             sums[k, 0] += torch.where(ok, v, torch.zeros_like(v)).sum()
                             sums[k, 1] += ok.sum()
-                    if with_losses:
+                    if with_losses or with_table:
                         lm = self._loss_model
                         out, _ = lm.build(s)
+                    if with_table:
+                        keys = (constants.KEY_PROP_CEN_Z, constants.KEY_CENTROIDS, constants.KEY_LWH + '_offs',
+                                constants.KEY_VIEW_ANG)
+                        m.update(lm.evaluate_predictions({k: out[k] for k in keys if k in out}, lm.gt_dict, n))
+                        # (a metric this model does not produce is a column of NaN: count 0)
+                        table.append(torch.cat(
+                            [m[name].float().reshape(n, width) if name in m else
+                             torch.full((n, width), float('nan'), dtype=torch.float32, device=dev)
+                             for name, width in METRIC_COLUMNS], 1))
+                    if with_losses:
                         losses, total = lm.loss(out, lm.gt_dict, s['gt_alpha_valid_bins'])
                         losses = dict(losses, total_loss=total)
                         if loss_sums is None:
@@ -112,7 +196,8 @@ class Evaluator:
                         ok = ~torch.isnan(v)
                         loss_sums[:, 0] += torch.where(ok, v, torch.zeros_like(v))
                         loss_sums[:, 1] += ok
-        return torch.cat(b3s), torch.cat(b2s), torch.cat(frames), sums, loss_names, loss_sums
+        return (torch.cat(b3s), torch.cat(b2s), torch.cat(frames), sums, loss_names, loss_sums,
+                torch.cat(table).contiguous() if with_table else None)
 
     def _rows_to_host(self, b3, b2, frame):
         """One launch, one compaction, one copy: -> (rows (m,14) float64, class index (m,), frame (m,)) of the kept
@@ -136,7 +221,7 @@ class Evaluator:
 
     def run_once(self, global_step=None):
         ds = self.dataset
-        b3, b2, frame, sums, loss_names, loss_sums = self._predict()
+        b3, b2, frame, sums, loss_names, loss_sums, table = self._predict()
         rows, cls, frame_h = self._rows_to_host(b3, b2, frame)
         names = ds.sample_names
         per_frame = {}
@@ -146,14 +231,27 @@ class Evaluator:
         result = dict(num_frames=len(ds.split_sample_names), num_frames_with_detections=len(per_frame),
                       num_detections=int(len(rows)), num_predictions=int(b3.shape[0]), global_step=global_step,
                       kitti=None, report=None, metrics={}, losses={})
-        if ds.train_val_test == 'val' and (self.compute_metrics or loss_names):
-            # one copy for both tables
+        if ds.train_val_test == 'val' and (self.compute_metrics or loss_names or table is not None):
+            # one copy for all tables
             names = [constants.METRIC_EMD, constants.METRIC_CHAMFER] + list(loss_names)
-            s = (sums if loss_sums is None else torch.cat([sums, loss_sums])).cpu().numpy()
+            parts = [sums] + ([] if loss_sums is None else [loss_sums])
+            if table is not None:
+                self.metric_table = (table, frame)
+                stats = evaluator_utils.metric_stats(table, frame, COLUMN_METRIC, len(METRIC_NAMES), ds.num_samples,
+                                                     evaluator_utils.NAN_RULE_FRAME)
+                parts.append(stats)
+            s = torch.cat([t.reshape(-1) for t in parts]).cpu().numpy()
+            if table is not None:
+                result['metric_stats'] = evaluator_utils.metric_stats_dict(
+                    METRIC_NAMES, s[-6 * len(METRIC_NAMES):].reshape(len(METRIC_NAMES), 6))
+            s = s[:2 * len(names)].reshape(len(names), 2)
             means = {key: float(s[k, 0] / s[k, 1]) if s[k, 1] else float('nan') for k, key in enumerate(names)}
             if self.compute_metrics:
                 result['metrics'] = {key: means[key] for key in names[:2]}
             result['losses'] = {key: means[key] for key in loss_names}
+        if 'metric_stats' in result and self.predictions_base_dir is not None:
+            result['metrics_csv'] = evaluator_utils.save_metric_stats(self.predictions_base_dir, ds.data_split,
+                                                                      global_step, result['metric_stats'])
         if self.predictions_base_dir is not None:
             out_dir = evaluator_utils.kitti_output_dir(self.predictions_base_dir, ds.data_split, self.score_threshold,
                                                        global_step)
@@ -199,6 +297,59 @@ class Evaluator:
                                                      full_trunk=True)
         step = checkpoint.get('global_step')
         return self.run_once(None if step is None else int(np.asarray(step)))
+
+    # ---- sweeps over a checkpoint directory
+
+    def _evaluated_path(self):
+        return os.path.join(self.predictions_base_dir, 'evaluated_%s.txt' % self.dataset.data_split)
+
+    def get_evaluated_ckpts(self):
+        """The steps <predictions_base_dir>/evaluated_<split>.txt lists, as a set."""
+        path = self._evaluated_path()
+        if not os.path.exists(path):
+            return set()
+        with open(path) as f:
+            return {int(line) for line in f.read().split()}
+
+    def _run_and_record(self, step, prefix, width_div):
+        result = self.run_checkpoint_once(prefix, width_div=width_div)
+        base = self.predictions_base_dir
+        if result.get('report') is not None:
+            report_dir = os.path.join(base, 'kitti_reports', self.dataset.data_split)
+            os.makedirs(report_dir, exist_ok=True)
+            with open(os.path.join(report_dir, '%08d_%s.txt' % (step, self.iou)), 'w') as f:
+                f.write(result['report'])
+        os.makedirs(base, exist_ok=True)
+        with open(self._evaluated_path(), 'a') as f:
+            f.write('%d\n' % step)
+        return result
+
+    def _sweep_setup(self, width_div):
+        if self.predictions_base_dir is None:
+            raise ValueError('a checkpoint sweep needs predictions_base_dir: the evaluated steps, the reports and the '
+                             'metrics CSVs are kept there')
+        evaluated = self.get_evaluated_ckpts() if self.skip_evaluated_checkpoints else set()
+        return evaluated, lambda step, prefix: self._run_and_record(step, prefix, width_div)
+
+    def run_latest_checkpoints(self, checkpoint_dir, ckpt_indices=None, width_div=1):
+        """Evaluates the checkpoints `<name>-<step, 8 digits>` of a directory (sweep_checkpoints): None = every one not
+        yet evaluated (evaluated_<split>.txt, with skip_evaluated_checkpoints), in step order; -1 = the latest;
+        otherwise the listed steps (KeyError for a step that is not there).  After each: its report into
+        <predictions_base_dir>/kitti_reports/<split>/<step>_<iou>.txt and its step appended to evaluated_<split>.txt.
+        -> [run_checkpoint_once's results]."""
+        from monopsr_amd.core import checkpoint_utils
+        evaluated, run = self._sweep_setup(width_div)
+        return sweep_checkpoints(checkpoint_utils.list_checkpoints(checkpoint_dir), evaluated, run, ckpt_indices)
+
+    def repeated_checkpoint_run(self, checkpoint_dir, max_iterations, eval_wait_interval=30, max_idle_seconds=None,
+                                width_div=1):
+        """run_latest_checkpoints again and again next to a running trainer (repeated_sweep): returns once a checkpoint
+        of step >= max_iterations has been evaluated, or after max_idle_seconds without a new one (None: waits for
+        ever, as the reference does)."""
+        from monopsr_amd.core import checkpoint_utils
+        evaluated, run = self._sweep_setup(width_div)
+        return repeated_sweep(lambda: checkpoint_utils.list_checkpoints(checkpoint_dir), evaluated, run,
+                              max_iterations, eval_wait_interval, max_idle_seconds)
 
 
 def build_parser():

@@ -12,9 +12,13 @@ vectorised over the boxes of a frame; it needs the frame's P2 matrix and image s
 
 The native KITTI evaluator the reference compiles and runs (evaluator_utils.py:457-560) is replaced by
 `monopsr_amd.core.kitti_eval`, which computes the same AP on the GPU from these label files (`evaluate_dirs`) or
-straight from format_predictions output (`evaluate_predictions`, through `kitti_label_array`).  The metrics CSV,
-checkpoint sweeps and summaries (evaluator_utils.py:280-456) are out of scope.
+straight from format_predictions output (`evaluate_predictions`, through `kitti_label_array`).
+
+The metrics CSVs of the reference's save_metrics (evaluator_utils.py:280-403) are written by `save_metric_stats` from
+the statistics `metric_stats` (one mpsr_metric_stats launch) takes of the evaluator's device-resident table.  The
+TensorBoard summaries (evaluator_utils.py:376-456) are out of scope.
 """
+import csv
 import os
 
 import numpy as np
@@ -93,6 +97,81 @@ def detection_rows(box_3d, box_2d, score_threshold, frame=None, p2=None, image_w
             p(image_wh) if project_3d_box else None, n, n_frames, float(score_threshold), int(bool(project_3d_box)),
             p(rows), p(ints[0]), p(ints[1]), _lib.stream()))
     return rows, ints[0], ints[1]
+
+
+NAN_RULE_ENTRY, NAN_RULE_FRAME = 0, 1
+STAT_NAMES = ('count', 'mean', 'std', 'mean_abs', 'std_abs', 'dropped')
+
+
+def metric_stats(values, frame, column_metric, n_metrics, n_frames, nan_rule=NAN_RULE_FRAME, out=None):
+    """count, mean, np.std, mean |x|, std |x| and the number of dropped values per metric, in fp64, of a device-resident
+    table in one mpsr_metric_stats launch.  values (n_rows, n_cols) float32 and frame (n_rows) int32 in [0, n_frames)
+    CUDA tensors; column_metric: n_cols ints, the metric each column feeds (several columns may feed one).
+    nan_rule NAN_RULE_FRAME: a NaN drops its frame's values of that metric (the reference's rule); NAN_RULE_ENTRY: the
+    NaN entries alone.  -> (n_metrics, 6) float64 on the device, columns STAT_NAMES; `out` is written when given."""
+    import torch
+    from monopsr_amd import _lib
+    import ctypes
+    column_metric = [int(c) for c in column_metric]
+    n_rows, n_cols = (int(v) for v in values.shape) if values.dim() == 2 else (-1, -1)
+    if values.dtype != torch.float32 or n_cols != len(column_metric) or frame.dtype != torch.int32 \
+            or frame.numel() != n_rows:
+        raise ValueError('metric_stats: values (n_rows, %d) float32 and frame (n_rows,) int32, got %s %s and %s %s' % (
+            len(column_metric), tuple(values.shape), values.dtype, tuple(frame.shape), frame.dtype))
+    dev = values.device
+    _lib.ptr(values), _lib.ptr(frame)  # (refuses tensors that are not on the GPU)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((int(n_metrics), 6), dtype=torch.float64, device=dev)
+        elif tuple(out.shape) != (int(n_metrics), 6) or out.dtype != torch.float64:
+            raise ValueError('metric_stats: out must be (%d, 6) float64' % int(n_metrics))
+        flags = None
+        if nan_rule == NAN_RULE_FRAME:
+            flags = torch.empty((max(int(n_metrics) * int(n_frames), 1),), dtype=torch.int32, device=dev)
+        p = _lib.ptr
+        _lib.check(_lib.lib().mpsr_metric_stats(
+            p(values), p(frame), n_rows, n_cols, (ctypes.c_int * max(n_cols, 1))(*column_metric), int(n_metrics),
+            int(n_frames), int(nan_rule), p(flags), p(out), _lib.stream()))
+    return out
+
+
+def metric_stats_dict(names, stats):
+    """{metric name: {count, mean, std, mean_abs, std_abs, dropped}} of a host copy of metric_stats' output."""
+    return {name: dict(zip(STAT_NAMES, (int(row[0]), float(row[1]), float(row[2]), float(row[3]), float(row[4]),
+                                        int(row[5])))) for name, row in zip(names, stats)}
+
+
+def metrics_dir(predictions_base_dir, data_split):
+    return os.path.join(predictions_base_dir, 'metrics', data_split)
+
+
+# file name stem -> the statistic it holds
+METRIC_FILES = (('metrics_avg', 'mean'), ('metrics_std', 'std'), ('metrics_avg_abs', 'mean_abs'),
+                ('metrics_std_abs', 'std_abs'))
+
+
+def save_metric_stats(predictions_base_dir, data_split, global_step, metric_stats):
+    """Appends one line per call to metrics_avg_<split>.csv, metrics_std_<split>.csv, metrics_avg_abs_<split>.csv and
+    metrics_std_abs_<split>.csv under <predictions_base_dir>/metrics/<split>/, in the format of the reference's
+    save_metrics (evaluator_utils.py:280-403): the metric names sorted; into an empty file first a header of 'step'
+    right-justified to 8 and every name without its 'metric_' prefix right-justified to 12; then the step
+    right-justified to 8 and every value as '{:.5f}' right-justified to 12; ',' between the fields and the csv
+    module's line ending.  metric_stats: {name: {mean, std, mean_abs, std_abs, ...}}.  Returns the four paths."""
+    out_dir = metrics_dir(predictions_base_dir, data_split)
+    os.makedirs(out_dir, exist_ok=True)
+    names = sorted(metric_stats)
+    header = ['step'.rjust(8)] + [(n[len('metric_'):] if n.startswith('metric_') else n).rjust(12) for n in names]
+    paths = []
+    for stem, stat in METRIC_FILES:
+        path = os.path.join(out_dir, '%s_%s.csv' % (stem, data_split))
+        with open(path, 'a', newline='') as f:
+            writer = csv.writer(f, delimiter=',')
+            if f.tell() == 0:
+                writer.writerow(header)
+            writer.writerow(['{}'.format(global_step).rjust(8)] +
+                            ['{:.5f}'.format(metric_stats[n][stat]).rjust(12) for n in names])
+        paths.append(path)
+    return paths
 
 
 def kitti_label_rows(box_3d, box_2d, classes, score_threshold, image_boxes=None, keep=None):

@@ -561,23 +561,50 @@ class MonoPSRModel:
 
     # ------------------------------------------------------------------ metrics (:1112-1170)
     def evaluate_predictions(self, prediction_dict, gt_dict, num_objs=None):
-        """gt_dict: KEY_INST_XYZ_MAP_LOCAL (B,h,w,3) and KEY_VALID_MASK_MAPS (B,h,w,1).  Returns METRIC_EMD and
-        METRIC_CHAMFER per object, each divided by its number of valid pixels."""
+        """The per-object metrics of monopsr_model.py:1112-1219, each group only when the keys it needs are in both
+        dictionaries (the reference's `if KEY in self.output_types` blocks):
+          KEY_INST_XYZ_MAP_LOCAL (B,h,w,3), with KEY_VALID_MASK_MAPS (B,h,w,1) in gt_dict -> METRIC_EMD and
+            METRIC_CHAMFER (num_objs), each divided by its number of valid pixels;
+          KEY_PROP_CEN_Z (B,1) in prediction_dict and KEY_CENTROIDS (B,3) in both -> METRIC_PROP_CEN_Z_ERR (num_objs,1),
+            METRIC_CEN_X_ERR / _CEN_Y_ERR / _CEN_Z_ERR (num_objs);
+          KEY_LWH + '_offs' (B,3) -> METRIC_DIM_ERR (num_objs,3);  KEY_VIEW_ANG (B,1) -> METRIC_VIEW_ANG_ERR (num_objs,1).
+        Every error is ground truth minus prediction over the first num_objs rows."""
         metrics_dict = {}
-        pred = prediction_dict[constants.KEY_INST_XYZ_MAP_LOCAL]
-        gt = gt_dict[constants.KEY_INST_XYZ_MAP_LOCAL]
-        mask = gt_dict[constants.KEY_VALID_MASK_MAPS]
-        B = pred.shape[0]
-        num_objs = B if num_objs is None else int(num_objs)
-        valid_pred_inst_points = (pred * mask).reshape(B, -1, 3)
-        valid_gt_points = (gt * mask).reshape(B, -1, 3)
-        num_valid_pixels = mask[0:num_objs].sum(dim=(1, 2, 3))
+        if constants.KEY_INST_XYZ_MAP_LOCAL in prediction_dict and constants.KEY_INST_XYZ_MAP_LOCAL in gt_dict:
+            pred = prediction_dict[constants.KEY_INST_XYZ_MAP_LOCAL]
+            gt = gt_dict[constants.KEY_INST_XYZ_MAP_LOCAL]
+            mask = gt_dict[constants.KEY_VALID_MASK_MAPS]
+            B = pred.shape[0]
+            n = B if num_objs is None else int(num_objs)
+            valid_pred_inst_points = (pred * mask).reshape(B, -1, 3)
+            valid_gt_points = (gt * mask).reshape(B, -1, 3)
+            num_valid_pixels = mask[0:n].sum(dim=(1, 2, 3))
+            with torch.no_grad():
+                # approx_match + match_cost (monopsr_model.py:1143-1149), fused: no match tensor
+                all_distances = tf_approxmatch.emd_loss_fwd_bwd(valid_pred_inst_points, valid_gt_points,
+                                                                want_grads=False)[0]
+                metrics_dict[constants.METRIC_EMD] = all_distances[0:n] / num_valid_pixels
+                dist1, _, dist2, _ = tf_nndistance.nn_distance(valid_pred_inst_points, valid_gt_points)
+                all_chamfer_dists = dist1.sum(dim=1) + dist2.sum(dim=1)
+                metrics_dict[constants.METRIC_CHAMFER] = all_chamfer_dists[0:n] / num_valid_pixels
+
+        def first(d, key):
+            return d[key] if num_objs is None else d[key][0:int(num_objs)]
+
         with torch.no_grad():
-            # approx_match + match_cost (monopsr_model.py:1143-1149), fused: no match tensor
-            all_distances = tf_approxmatch.emd_loss_fwd_bwd(valid_pred_inst_points, valid_gt_points,
-                                                            want_grads=False)[0]
-            metrics_dict[constants.METRIC_EMD] = all_distances[0:num_objs] / num_valid_pixels
-            dist1, _, dist2, _ = tf_nndistance.nn_distance(valid_pred_inst_points, valid_gt_points)
-            all_chamfer_dists = dist1.sum(dim=1) + dist2.sum(dim=1)
-            metrics_dict[constants.METRIC_CHAMFER] = all_chamfer_dists[0:num_objs] / num_valid_pixels
+            if constants.KEY_PROP_CEN_Z in prediction_dict and constants.KEY_CENTROIDS in prediction_dict \
+                    and constants.KEY_CENTROIDS in gt_dict:
+                gt_cens = first(gt_dict, constants.KEY_CENTROIDS)
+                cen_errs = gt_cens - first(prediction_dict, constants.KEY_CENTROIDS)
+                metrics_dict[constants.METRIC_PROP_CEN_Z_ERR] = gt_cens[:, 2:3] - first(prediction_dict,
+                                                                                        constants.KEY_PROP_CEN_Z)
+                metrics_dict[constants.METRIC_CEN_X_ERR] = cen_errs[:, 0]
+                metrics_dict[constants.METRIC_CEN_Y_ERR] = cen_errs[:, 1]
+                metrics_dict[constants.METRIC_CEN_Z_ERR] = cen_errs[:, 2]
+            key = constants.KEY_LWH + '_offs'
+            if key in prediction_dict and key in gt_dict:
+                metrics_dict[constants.METRIC_DIM_ERR] = first(gt_dict, key) - first(prediction_dict, key)
+            key = constants.KEY_VIEW_ANG
+            if key in prediction_dict and key in gt_dict:
+                metrics_dict[constants.METRIC_VIEW_ANG_ERR] = first(gt_dict, key) - first(prediction_dict, key)
         return metrics_dict

@@ -357,6 +357,18 @@ class InstanceTrainer:
         tf_checkpoint.write_checkpoint_state(checkpoint_dir, os.path.basename(prefix))
         return prefix
 
+    def export_checkpoint(self, checkpoint_dir, name='monopsr', width_div=1):
+        """Write the plain, trained variables under the reference's names (TrainNet.export_weights) with the global
+        step as `<dir>/<name>-<global_step, 8 digits>`: what Evaluator.run_checkpoint_once and a sweep restore.  Not the
+        moving average: the reference's evaluator restores the variables themselves.  Use a directory other than
+        `save`'s: both write the directory's `checkpoint` state file, and `save`'s files do not restore into an
+        evaluator.  Returns the prefix written."""
+        import os
+        from monopsr_amd.core import checkpoint_utils
+        os.makedirs(checkpoint_dir, exist_ok=True)
+        return checkpoint_utils.save_checkpoint(os.path.join(checkpoint_dir, name), self.net.export_weights(width_div),
+                                                self.global_step)
+
     def restore(self, path):
         """Resume from `save`'s output (a prefix, or a directory holding a `checkpoint` state file)."""
         from monopsr_amd.core import tf_checkpoint

@@ -891,7 +891,9 @@ __device__ __forceinline__ double wave_sum_d(double v)
 
 // ---------------------------------------------------------------------------------------------------- fused loss
 // Cost and gradients straight from the ratios: match is never stored.  ROLE 0: own = givers k -> grad1[k] and the
-// cloud's cost (atomic add of per-workgroup sums into the pre-zeroed output); ROLE 1: own = receivers l -> grad2[l].
+// cloud's cost (per-workgroup sums, as float32, into the first words of the cloud's remL, which nothing reads after the
+// passes; emd_cost_finish_kernel adds them in workgroup order: one of the orders in which the float32 atomics that
+// stood here before could have met, and the same one on every call); ROLE 1: own = receivers l -> grad2[l].
 // Every pair's match entry is recomputed in both roles (13 flops + 3 exponentials each) instead of being written once
 // and read three times.  grid (ceil(own / 256), b).
 constexpr int kLossTile = 256;
@@ -965,8 +967,23 @@ __global__ __launch_bounds__(256) void emd_loss_kernel(int n, int m, const float
         __syncthreads();
         if ((tid & 63) == 0) part[tid >> 6] = v;
         __syncthreads();
-        if (tid == 0) atomicAdd(&cost[cloud], (float)(part[0] + part[1] + part[2] + part[3]));
+        // (remL is dead once the passes are done: it now carries the workgroups' partial costs to emd_cost_finish_kernel)
+        if (tid == 0) st.remL[blockIdx.x] = (float)(part[0] + part[1] + part[2] + part[3]);
     }
+}
+
+// cost[cloud] = the cloud's `parts` partial costs added in float32 in workgroup order, starting from 0: one thread per
+// cloud (parts is ceil(n / 256) or ceil(n / 512): 9 or 5 for the evaluator's 2304 points).
+template <bool HOST>
+__global__ __launch_bounds__(64) void emd_cost_finish_kernel(int b, int n, int m, void *temp, int parts,
+                                                             float *__restrict__ cost)
+{
+    const int cloud = blockIdx.x * 64 + threadIdx.x;
+    if (cloud >= b) return;
+    const State<HOST> st(temp, cloud, n, m, Sem<HOST>::levels);
+    float c = 0.f;
+    for (int i = 0; i < parts; ++i) c += (float)st.remL[i];
+    cost[cloud] = c;
 }
 
 // DEVICE semantics, two own points per thread in the halves of 2-wide vectors: the ~45 full-rate instructions a pair
@@ -1115,7 +1132,8 @@ __global__ __launch_bounds__(256) void emd_loss_pk_kernel(int n, int m, const fl
         __syncthreads();
         if ((tid & 63) == 0) part[tid >> 6] = v;
         __syncthreads();
-        if (tid == 0) atomicAdd(&cost[cloud], (float)(part[0] + part[1] + part[2] + part[3]));
+        // (remL is dead once the passes are done: it now carries the workgroups' partial costs to emd_cost_finish_kernel)
+        if (tid == 0) st.remL[blockIdx.x] = (float)(part[0] + part[1] + part[2] + part[3]);
     }
 }
 
@@ -1437,12 +1455,13 @@ extern "C" int mpsr_emd_loss(int b, int n, int m, const float *xyz1, const float
         return mpsr::fail(MPSR_ERR_WORKSPACE, "emd_loss: temp holds %zu floats, needs %zu (mpsr_emd_temp_floats)",
                           temp_floats, full);
     hipStream_t s = mpsr::as_stream(stream);
-    MPSR_CHECK_HIP(hipMemsetAsync(cost, 0, sizeof(float) * b, s));
     const dim3 g1(mpsr::ceil_div(n, 256), b), g2(mpsr::ceil_div(m, 256), b);
+    const dim3 gf(mpsr::ceil_div(b, 64));
     if (semantics == MPSR_EMD_HOST) {
         MPSR_REQUIRE(((uintptr_t)temp & 7) == 0, "emd_loss: temp must be 8-byte aligned for the host semantics");
         if (int rc = run_passes<true>(b, n, m, xyz1, xyz2, temp, Sem<true>::levels, s, [](int) { return 0; })) return rc;
         hipLaunchKernelGGL((emd_loss_kernel<true, 0>), g1, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, cost, grad1);
+        hipLaunchKernelGGL(emd_cost_finish_kernel<true>, gf, dim3(64), 0, s, b, n, m, (void *)temp, (int)g1.x, cost);
         if (grad2)
             hipLaunchKernelGGL((emd_loss_kernel<true, 1>), g2, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, cost,
                                grad2);
@@ -1460,6 +1479,7 @@ extern "C" int mpsr_emd_loss(int b, int n, int m, const float *xyz1, const float
             const int flags = g_emd_cull.load() == 2 ? kNeverCull : 0;
             hipLaunchKernelGGL((emd_loss_pk_kernel<0, true>), p1, dim3(256), 0, s, n, m, s1, s2, (void *)temp, cost, grad1,
                                (const int *)perm1, flags);
+            hipLaunchKernelGGL(emd_cost_finish_kernel<false>, gf, dim3(64), 0, s, b, n, m, (void *)temp, (int)p1.x, cost);
             if (grad2)
                 hipLaunchKernelGGL((emd_loss_pk_kernel<1, true>), p2, dim3(256), 0, s, n, m, s1, s2, (void *)temp, cost,
                                    grad2, (const int *)perm2, flags);
@@ -1468,6 +1488,7 @@ extern "C" int mpsr_emd_loss(int b, int n, int m, const float *xyz1, const float
                 return rc;
             hipLaunchKernelGGL(emd_loss_pk_kernel<0>, p1, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, cost, grad1,
                                (const int *)nullptr, 0);
+            hipLaunchKernelGGL(emd_cost_finish_kernel<false>, gf, dim3(64), 0, s, b, n, m, (void *)temp, (int)p1.x, cost);
             if (grad2)
                 hipLaunchKernelGGL(emd_loss_pk_kernel<1>, p2, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, cost, grad2,
                                    (const int *)nullptr, 0);

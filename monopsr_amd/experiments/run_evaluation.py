@@ -1,0 +1,76 @@
+"""Scores the checkpoints of a directory on a split with MSCNN 2-D detections: KITTI AP and the per-object error
+statistics, one row per checkpoint (the reference's experiments/run_evaluation.py over Evaluator.run_latest_checkpoints /
+repeated_checkpoint_run).
+
+    python -m monopsr_amd.experiments.run_evaluation CONFIG --checkpoint-dir DIR --mscnn-dir DIR --predictions-dir DIR
+
+Under --predictions-dir: kitti_predictions_3d/ (the label files), metrics/<split>/metrics_{avg,std,avg_abs,std_abs}_<split>.csv,
+kitti_reports/<split>/<step>_<iou>.txt and evaluated_<split>.txt, which a later run reads to skip what is done.
+"""
+import argparse
+import sys
+
+from monopsr_amd.core import evaluator
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description='KITTI AP and metric statistics of the checkpoints of a directory')
+    ap.add_argument('config', help='experiment config (yaml)')
+    ap.add_argument('--checkpoint-dir', required=True, help='directory of <name>-<step, 8 digits> checkpoints')
+    ap.add_argument('--mscnn-dir', required=True, help='MSCNN detections in KITTI label format, one file per frame')
+    ap.add_argument('--predictions-dir', required=True, help='where the label files, CSVs and reports are written')
+    ap.add_argument('--data-split', default='val')
+    ap.add_argument('--ckpt-indices', type=int, nargs='+', default=None,
+                    help='steps to evaluate (-1: the latest); default: every checkpoint not yet evaluated')
+    ap.add_argument('--repeat', action='store_true', help='keep watching the directory for new checkpoints')
+    ap.add_argument('--wait-interval', type=float, default=30.0, help='seconds between two looks (--repeat)')
+    ap.add_argument('--max-idle', type=float, default=None,
+                    help='stop after this many seconds without a new checkpoint (--repeat; default: never)')
+    ap.add_argument('--width-div', type=int, default=1, help='channel divisor of the net the checkpoints were saved from')
+    ap.add_argument('--low-iou', action='store_true', help='MIN_OVERLAP 0.5 / 0.25 / 0.25')
+    return ap
+
+
+def format_result(result):
+    """The report of one checkpoint and a line of its four statistics per metric."""
+    lines = [result['report'] or '']
+    for name, st in sorted(result.get('metric_stats', {}).items()):
+        lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
+            name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
+    return ''.join(lines)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    from monopsr_amd.core import config_utils
+    from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
+    from monopsr_amd.datasets.kitti.kitti_dataset import KittiDataset
+    cfg = config_utils.parse_yaml_config(args.config)
+    cfg.dataset_config.data_split = args.data_split
+    cfg.dataset_config.use_mscnn_detections = True
+    dataset = KittiDataset(cfg.dataset_config, 'val', mscnn_label_dir=args.mscnn_dir)
+    model = MonoPSRModel(cfg.model_config, cfg.dataset_config, None, 'test')
+    train_config = cfg.get('train_config')
+    threshold = getattr(train_config, 'kitti_score_threshold', 0.1)
+    ev = evaluator.Evaluator(model, dataset, score_threshold=threshold, predictions_base_dir=args.predictions_dir,
+                             iou='low' if args.low_iou else 'standard', metric_stats=True)
+    if args.repeat:
+        max_iterations = getattr(train_config, 'max_iterations', None)
+        if max_iterations is None and args.max_idle is None:
+            raise SystemExit('--repeat needs train_config.max_iterations in the config or --max-idle: it would never end')
+        results = ev.repeated_checkpoint_run(args.checkpoint_dir, float('inf') if max_iterations is None else max_iterations,
+                                             args.wait_interval, args.max_idle, width_div=args.width_div)
+    else:
+        indices = args.ckpt_indices
+        if indices is not None and len(indices) == 1:
+            indices = indices[0]
+        results = ev.run_latest_checkpoints(args.checkpoint_dir, indices, width_div=args.width_div)
+    for result in results:
+        sys.stdout.write('step %s\n%s' % (result['global_step'], format_result(result)))
+    if not results:
+        sys.stdout.write('no checkpoint to evaluate in %s\n' % args.checkpoint_dir)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

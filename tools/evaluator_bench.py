@@ -9,6 +9,9 @@ with synthetic MSCNN detection files (every label's box shifted by a few pixels,
 Both run on the same resident KittiDataset in 'val' mode with the detections merged, the same random-weight net
 (--width-div) and the same chunk size.  Each is run once to warm up and then timed over --repeats passes; the
 device-to-host copies of one pass of each are counted with torch.profiler.  Numbers: DESIGN.md section 7.5.
+
+--metric-stats times mpsr_metric_stats alone with device events on a synthetic table of a full val split (3769 frames
+of 32 rows, the Evaluator's ten columns) and ends.
 """
 import argparse
 import os
@@ -80,6 +83,29 @@ def timed(fn, repeats):
     return (time.perf_counter() - t0) / repeats
 
 
+def time_metric_stats(frames=3769, rows_per_frame=32, repeats=20):
+    """Mean device time of one mpsr_metric_stats launch (both NaN rules) over `repeats` launches after a warm-up."""
+    from monopsr_amd.core import evaluator_utils
+    g = torch.Generator(device='cuda').manual_seed(0)
+    n = frames * rows_per_frame
+    values = torch.randn((n, len(evaluator.COLUMN_METRIC)), device='cuda', generator=g)
+    frame = torch.arange(frames, dtype=torch.int32, device='cuda').repeat_interleave(rows_per_frame)
+    out = torch.empty((len(evaluator.METRIC_NAMES), 6), dtype=torch.float64, device='cuda')
+    for rule, what in ((evaluator_utils.NAN_RULE_FRAME, 'frame rule'), (evaluator_utils.NAN_RULE_ENTRY, 'entry rule')):
+        run = lambda: evaluator_utils.metric_stats(values, frame, evaluator.COLUMN_METRIC, len(evaluator.METRIC_NAMES),
+                                                   frames, rule, out=out)
+        run()
+        torch.cuda.synchronize()
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(repeats):
+            run()
+        end.record()
+        torch.cuda.synchronize()
+        print('mpsr_metric_stats, %d rows x %d columns, %s: %.1f us per launch (device events, mean of %d)'
+              % (n, values.shape[1], what, 1e3 * start.elapsed_time(end) / repeats, repeats))
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument('--frames', type=int, default=64)
@@ -88,7 +114,11 @@ def main(argv=None):
     p.add_argument('--no-metrics', action='store_true',
                    help='run_once without the EMD / Chamfer metrics and the loss terms: the same work as the host path')
     p.add_argument('--width-div', type=int, default=1, help='channel divisor of the random-weight net (1: full size)')
+    p.add_argument('--metric-stats', action='store_true', help='time mpsr_metric_stats on a full-split table and end')
     a = p.parse_args(argv)
+    if a.metric_stats:
+        time_metric_stats()
+        return 0
     from monopsr_amd.core import device_net as dn
     from monopsr_amd.core import weights as W
     from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
