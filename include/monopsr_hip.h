@@ -957,6 +957,33 @@ int mpsr_metric_stats(const float *values, const int *frame, int n_rows, int n_c
                       int n_metrics, int n_frames, int nan_rule, int *frame_flags, double *stats,
                       mpsr_stream_t stream);
 
+/* ---- One step's row of the training log (additive to ABI 13) ----
+ * Writes row `row` of the caller-owned table rows (n_rows, n_cols) float32, row-major, n_cols == n_terms +
+ * MPSR_TRAIN_LOG_STAT_COLS, and steps[row] = step (steps: n_rows int64); no other element of either is touched.  One
+ * launch of one workgroup, no host synchronisation, no allocation: a training loop logs its losses without waiting for
+ * them (core/train_log.py).
+ * Columns [0, n_terms): the DEVICE scalars *terms.p[i] (the step's loss terms and their total); a null pointer writes
+ * NaN, "term absent this step".  The struct is passed BY VALUE; entries from n_terms on are not read.
+ * The other five columns come from sumsq, the first n_segments floats of the clip table's scratch, where
+ * mpsr_clip_adam_ema_step / mpsr_clip_by_norm_segments leave the squared norm of every variable's reduced, unclipped
+ * gradient:
+ *   n_terms + 0  grad_norm         sqrt(sum_s (double)sumsq[s]), rounded to float32
+ *   n_terms + 1  max_var_norm      the largest sqrtf(sumsq[s])
+ *   n_terms + 2  n_clipped         the number of s with sqrtf(sumsq[s]) > clip_norm (strict, as the clip itself compares);
+ *                                  0 when clip_norm <= 0
+ *   n_terms + 3  n_nonfinite_vars  the number of s whose sumsq[s] is NaN or +-inf; these are left out of the three above
+ *   n_terms + 4  lr
+ * sumsq == NULL or n_segments == 0: 0 in the four gradient columns.  The sum is fp64 in a fixed order (strided per-thread
+ * partials, then a tree over LDS), no atomics: two calls on the same inputs return the same bits.
+ * MPSR_ERR_INVALID_ARG before any launch: n_terms outside [1, MPSR_TRAIN_LOG_MAX_TERMS], n_cols != n_terms +
+ * MPSR_TRAIN_LOG_STAT_COLS, row outside [0, n_rows), null rows / steps, n_segments < 0. */
+#define MPSR_TRAIN_LOG_MAX_TERMS 16
+#define MPSR_TRAIN_LOG_STAT_COLS 5
+typedef struct { const float *p[MPSR_TRAIN_LOG_MAX_TERMS]; } mpsr_train_log_terms;
+int mpsr_train_log_append(mpsr_train_log_terms terms, int n_terms, const float *sumsq, int n_segments, float clip_norm,
+                          float lr, long long step, float *rows, long long *steps, int n_rows, int n_cols, int row,
+                          mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

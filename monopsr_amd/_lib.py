@@ -81,6 +81,11 @@ class DepthFillOpts(ctypes.Structure):
                 ("kernels", (ctypes.c_uint8 * (15 * 15)) * 3)]
 
 
+class TrainLogTerms(ctypes.Structure):
+    """struct mpsr_train_log_terms (passed by value)"""
+    _fields_ = [("p", ctypes.c_void_p * 16)]
+
+
 # per-call option values (MPSR_CALL_MATH_*, MPSR_CALL_WINOGRAD_*): None / "inherit" = the process-wide default
 CALL_MATH = {None: 0, "inherit": 0, "fp32": 1, "bf16x3": 2}
 CALL_WINOGRAD = {None: 0, "inherit": 0, "auto": 1, "off": 2, "accurate": 3}
@@ -215,6 +220,8 @@ SIGNATURES = {
                                     ctypes.c_double, c_i, c_f, c_f, c_f, c_f]),
     "mpsr_kitti_detection_rows": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_double, c_i, c_f, c_f, c_f, c_f]),
     "mpsr_metric_stats": (c_i, [c_f, c_f, c_i, c_i, ctypes.POINTER(c_i), c_i, c_i, c_i, c_f, c_f, c_f]),
+    "mpsr_train_log_append": (c_i, [TrainLogTerms, c_i, c_f, c_i, ctypes.c_float, ctypes.c_float, ctypes.c_longlong, c_f,
+                                    c_f, c_i, c_i, c_i, c_f]),
 }
 
 

@@ -101,6 +101,29 @@ def list_checkpoints(checkpoint_dir):
     return sorted(found)
 
 
+def prune_checkpoints(checkpoint_dir, keep):
+    """Remove the files of all but the newest `keep` steps of a directory: every `<name>-<step, 8 digits>.<suffix>`
+    (.index, .data-00000-of-00001, and what a training loop puts beside them, .dataset.npz) of an older step.  None or 0
+    keeps everything, as tf.train.Saver(max_to_keep=None / 0) does.  The `checkpoint` state file is left alone: it names
+    the newest step, which is never removed.  Returns the steps removed, ascending."""
+    import os
+    import re
+    if not keep:
+        return []
+    if int(keep) < 0:
+        raise ValueError('keep %r < 0' % (keep,))
+    by_step = {}
+    for entry in os.listdir(checkpoint_dir):
+        m = re.match(r"^.+-(\d{8})\..+$", entry)
+        if m:
+            by_step.setdefault(int(m.group(1)), []).append(entry)
+    removed = sorted(by_step)[:-int(keep)]
+    for step in removed:
+        for entry in by_step[step]:
+            os.remove(os.path.join(checkpoint_dir, entry))
+    return removed
+
+
 def load_npz(path):
     with np.load(path) as f:
         return {k: f[k] for k in f.files}

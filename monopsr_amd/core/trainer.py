@@ -5,7 +5,7 @@ What it mirrors of the reference's training setup (core/trainer.py:58-81, builde
 configs/monopsr_model_000.yaml:100-152): model.build() in 'train' mode -> model.loss() (the configured weighted sum
 of per-output losses) -> Adam with the exponential-decay learning rate and the parameter moving average ->
 per-variable clip_by_norm(1.0) as slim.learning.create_train_op(clip_gradient_norm=1.0) applies it.
-Not mirrored: TF summaries and the checkpoint schedule.
+The checkpoint schedule and the summaries are core/train_loop.py's; TF event files are not written.
 """
 import os
 

@@ -14,6 +14,7 @@ PNG is read once, and a batch is a few small launches without file I/O or a devi
         trainer.step(sample)
     dataset.check_status()          # once per epoch: reads the crop kernels' device status word
 """
+import json
 import os
 
 import numpy as np
@@ -167,6 +168,35 @@ class EpochIndex:
             return parts
         self._index_in_epoch += batch_size
         return [(self.sample_list[start:self._index_in_epoch].copy(), self.epochs_completed)]
+
+    def state_dict(self):
+        """Where the epoch bookkeeping stands, as values np.savez stores without pickling: the bit generator's state
+        (JSON: PCG64's words are 128-bit integers), sample_list, _index_in_epoch and epochs_completed.  An object that
+        loads it draws the batches this one draws from here on."""
+        return {'num_samples': np.asarray(self.num_samples, np.int64),
+                'bit_generator_state': np.asarray(json.dumps(self._rng.bit_generator.state)),
+                'sample_list': np.asarray(self.sample_list, np.int64).copy(),
+                'index_in_epoch': np.asarray(self._index_in_epoch, np.int64),
+                'epochs_completed': np.asarray(self.epochs_completed, np.int64)}
+
+    def load_state_dict(self, state):
+        """Take over a state_dict() of an index over the same number of samples; a ValueError changes nothing."""
+        num_samples = int(state['num_samples'])
+        sample_list = np.asarray(state['sample_list'], np.int64).reshape(-1)
+        index_in_epoch, epochs_completed = int(state['index_in_epoch']), int(state['epochs_completed'])
+        if num_samples != self.num_samples:
+            raise ValueError('the state is of %d samples, this index of %d' % (num_samples, self.num_samples))
+        if not np.array_equal(np.sort(sample_list), np.arange(self.num_samples)):
+            raise ValueError('sample_list of the state is not a permutation of the %d samples' % self.num_samples)
+        if not 0 <= index_in_epoch <= self.num_samples or epochs_completed < 0:
+            raise ValueError('the state stands at sample %d of epoch %d' % (index_in_epoch, epochs_completed))
+        rng_state = json.loads(str(np.asarray(state['bit_generator_state'])[()]))
+        if rng_state.get('bit_generator') != type(self._rng.bit_generator).__name__:
+            raise ValueError('the state is of a %s bit generator, this index draws from %s' % (
+                rng_state.get('bit_generator'), type(self._rng.bit_generator).__name__))
+        self._rng.bit_generator.state = rng_state
+        self.sample_list = sample_list.copy()
+        self._index_in_epoch, self.epochs_completed = index_in_epoch, epochs_completed
 
 
 class _Group:
@@ -512,6 +542,28 @@ class KittiDataset:
         for frames, epoch in self._epochs.next(batch_size, shuffle):
             samples.extend(self._build(frames, epoch))
         return samples
+
+    def state_dict(self):
+        """The position in the split: EpochIndex.state_dict plus the seed and what identifies the split (its name and
+        the names of the frames that keep a label).  A sample depends on (seed, epoch, frame) only, so a dataset that
+        loads this continues with the batches this one would have built."""
+        state = self._epochs.state_dict()
+        state.update(seed=np.asarray(self.seed, np.int64), data_split=np.asarray(self.data_split),
+                     sample_names=np.asarray(self.sample_names))
+        return state
+
+    def load_state_dict(self, state):
+        """Continue where a state_dict() of a dataset over the same split stood (its seed included); a state whose
+        num_samples or split names differ is a ValueError and changes nothing."""
+        if int(state['num_samples']) != self.num_samples:
+            raise ValueError('the state is of %d samples, this split holds %d' % (int(state['num_samples']),
+                                                                                 self.num_samples))
+        names = [str(n) for n in np.asarray(state['sample_names']).reshape(-1)]
+        if str(np.asarray(state['data_split'])[()]) != self.data_split or names != self.sample_names:
+            raise ValueError("the state is of split '%s' (%d frames), not of this '%s' split's frames" % (
+                str(np.asarray(state['data_split'])[()]), len(names), self.data_split))
+        self._epochs.load_state_dict(state)
+        self.seed = int(state['seed'])
 
     def get_sample_dict(self, indices, epoch=None):
         """The samples of sample_list[indices] as they are in `epoch` (default: the current one); the bookkeeping of
