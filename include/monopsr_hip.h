@@ -384,13 +384,19 @@ int mpsr_crop_and_resize_grad(const float *grad_out, int nimg, int H, int W, int
  * statistics over (N,H,W) per channel, no scale, epsilon 1e-3, then ReLU).  z is the (M, C) convolution output,
  * M = N*H*W, C % 4 == 0, C <= 1024.  Statistics are accumulated in fp64 around the first row for conditioning:
  *   sum[c] = sum_m (z[m][c] - z[0][c]),  sumsq_shifted[c] = sum_m (z[m][c] - z[0][c])^2
- * so mean = z[0] + sum/M and the (biased) variance = sumsq_shifted/M - (sum/M)^2. */
+ * so mean = z[0] + sum/M and the (biased) variance = sumsq_shifted/M - (sum/M)^2.
+ * Alignment: every (M, C) tensor and every per-channel float vector of the entry points below that stream them (_stats,
+ * _apply, _grad_sums[_z], _grad[_z]) is accessed 16 bytes at a time; a pointer that is not a multiple of 16 is refused
+ * (status 1) before anything is launched.  The fp64 sums and the operands of the two _finalize calls need only their
+ * natural alignment.
+ * NaN: a NaN anywhere in a channel of z makes that channel's sums, mean, variance, inv_std and BOTH moving statistics
+ * NaN (the variance is clamped at 0 from below only; a NaN is not clamped away); other channels are unaffected. */
 int mpsr_batch_norm_stats(const float *z, long long M, int C, double *sum, double *sumsq_shifted,
                           mpsr_stream_t stream);
 /* ABI 6: the per-channel arithmetic between the passes as one launch each (they were ~16 and ~4 tiny tensor operations
  * per layer and step on the host framework's side).  Forward: d = sum / M, mean = z_row0 + d (z_row0 = the first row of
- * z, the shift of the sums), var = max(sumsq_shifted / M - d^2, 0) in fp64; mean and inv_std = 1 / sqrt(var + eps) as
- * floats; moving_mean = moving_mean * decay + (1 - decay) * mean and moving_variance likewise with the UNBIASED
+ * z, the shift of the sums), var = max(sumsq_shifted / M - d^2, 0) (a NaN stays NaN) in fp64; mean and
+ * inv_std = 1 / sqrt(var + eps) as floats; moving_mean = moving_mean * decay + (1 - decay) * mean and moving_variance likewise with the UNBIASED
  * variance var * M / max(M - 1, 1), as TensorFlow's fused kernel feeds its moving average (either may be NULL: not
  * updated).  Backward: dbeta += sum_g (NULL: not deposited), mean_g = sum_g / count, mean_gz = sum_gz / count (count =
  * the rows the statistics were taken over).  A caller that pools the sums over ranks does this arithmetic itself. */

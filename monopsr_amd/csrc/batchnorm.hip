@@ -182,6 +182,9 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_apply_kernel(const float *__r
     }
 }
 
+// every pointer the kernels read or write as float4 (NULL passes: optional operands are checked for presence separately)
+template <typename... P> inline bool aligned16(const P *...p) { return (((uintptr_t)p | ...) & 15) == 0; }
+
 int check_mc(const char *op, long long M, int C)
 {
     MPSR_REQUIRE(M >= 1 && C >= 4 && C % 4 == 0 && C <= 1024, "%s: M=%lld C=%d (C must be a multiple of 4, <= 1024)", op,
@@ -219,7 +222,10 @@ __global__ void bn_finalize_kernel(const double *__restrict__ sum, const double 
     if (c >= C) return;
     const double d = sum[c] * inv_m;
     const double mu = (double)z0[c] + d;
-    const double var = fmax(sumsq[c] * inv_m - d * d, 0.0);
+    // (negative from cancellation -> 0; a NaN stays NaN, so a poisoned channel shows in inv_std and moving_variance as
+    // it does in the mean -- fmax would return the 0)
+    const double v0 = sumsq[c] * inv_m - d * d;
+    const double var = (v0 > 0.0 || v0 != v0) ? v0 : 0.0;
     mean[c] = (float)mu;
     inv_std[c] = (float)(1.0 / sqrt(var + eps));
     if (moving_mean) moving_mean[c] = moving_mean[c] * decay + (1.f - decay) * (float)mu;
@@ -261,6 +267,7 @@ extern "C" int mpsr_batch_norm_apply(const float *z, long long M, int C, const f
 {
     if (int rc = check_mc("batch_norm_apply", M, C)) return rc;
     MPSR_REQUIRE(z && mean && inv_std && beta && y, "batch_norm_apply: null pointer");
+    MPSR_REQUIRE(aligned16(z, mean, inv_std, beta, y), "batch_norm_apply: misaligned pointer (16 bytes)");
     const long long n4 = M * (C / 4);
     hipLaunchKernelGGL(bn_apply_kernel, dim3(stream_grid(n4)), dim3(kThreads), 0, mpsr::as_stream(stream), z, n4, C / 4,
                        mean, inv_std, beta, relu, y);
@@ -274,6 +281,7 @@ extern "C" int mpsr_batch_norm_grad_sums(const float *dy, const float *y, const 
 {
     if (int rc = check_mc("batch_norm_grad_sums", M, C)) return rc;
     MPSR_REQUIRE(dy && z && mean && inv_std && sum_g && sum_gz, "batch_norm_grad_sums: null pointer");
+    MPSR_REQUIRE(aligned16(dy, y, z, mean, inv_std), "batch_norm_grad_sums: misaligned pointer (16 bytes)");
     hipStream_t s = mpsr::as_stream(stream);
     MPSR_CHECK_HIP(zero_pair(sum_g, sum_gz, C, s));
     int blocks;
@@ -291,6 +299,8 @@ extern "C" int mpsr_batch_norm_grad(const float *dy, const float *y, const float
 {
     if (int rc = check_mc("batch_norm_grad", M, C)) return rc;
     MPSR_REQUIRE(dy && z && mean && inv_std && mean_g && mean_gz && dz, "batch_norm_grad: null pointer");
+    MPSR_REQUIRE(aligned16(dy, y, z, mean, inv_std, mean_g, mean_gz, dz),
+                 "batch_norm_grad: misaligned pointer (16 bytes)");
     const long long n4 = M * (C / 4);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_grid(n4)), dim3(kThreads), 0, mpsr::as_stream(stream), dy, y, z,
                        n4, C / 4, mean, inv_std, mean_g, mean_gz, (const float *)nullptr, dz);
@@ -332,6 +342,7 @@ extern "C" int mpsr_batch_norm_grad_sums_z(const float *dy, const float *z, long
 {
     if (int rc = check_mc("batch_norm_grad_sums_z", M, C)) return rc;
     MPSR_REQUIRE(dy && z && mean && inv_std && beta && sum_g && sum_gz, "batch_norm_grad_sums_z: null pointer");
+    MPSR_REQUIRE(aligned16(dy, z, mean, inv_std, beta), "batch_norm_grad_sums_z: misaligned pointer (16 bytes)");
     hipStream_t s = mpsr::as_stream(stream);
     MPSR_CHECK_HIP(zero_pair(sum_g, sum_gz, C, s));
     int blocks;
@@ -349,6 +360,8 @@ extern "C" int mpsr_batch_norm_grad_z(const float *dy, const float *z, long long
 {
     if (int rc = check_mc("batch_norm_grad_z", M, C)) return rc;
     MPSR_REQUIRE(dy && z && mean && inv_std && beta && mean_g && mean_gz && dz, "batch_norm_grad_z: null pointer");
+    MPSR_REQUIRE(aligned16(dy, z, mean, inv_std, beta, mean_g, mean_gz, dz),
+                 "batch_norm_grad_z: misaligned pointer (16 bytes)");
     const long long n4 = M * (C / 4);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_grid(n4)), dim3(kThreads), 0, mpsr::as_stream(stream), dy,
                        (const float *)nullptr, z, n4, C / 4, mean, inv_std, mean_g, mean_gz, beta, dz);
