@@ -990,6 +990,55 @@ int mpsr_train_log_append(mpsr_train_log_terms terms, int n_terms, const float *
                           float lr, long long step, float *rows, long long *steps, int n_rows, int n_cols, int row,
                           mpsr_stream_t stream);
 
+/* ---- Scene reconstruction (additive to ABI 13): instance clouds, z-buffer depth maps and instance images ----
+ * A chunk of n_frames frames, frame f of frame_hw[f] = (h, w) pixels, its pixels at pixel_offset[f] ..
+ * pixel_offset[f + 1] of every per-pixel array (pixel_offset[0] = 0, pixel_offset[n_frames] = total_pixels); n_boxes
+ * boxes of points_per_box points each, box b of frame box_frame[b], box_frame never decreasing.  Arrays named *_host
+ * are host copies of the device array of the same name, checked before anything is launched.  The three calls share
+ * one caller-owned workspace and run in this order on one stream: project, then resolve and / or compact.
+ * Empty sizes (n_frames, n_boxes or points_per_box 0) are no-ops that return MPSR_OK; negative sizes, null pointers
+ * with non-empty sizes, n_boxes * points_per_box >= 2^32 and a frame of more than 2^30 pixels are
+ * MPSR_ERR_INVALID_ARG.  DESIGN.md section 7.7. */
+
+/* Bytes of the workspace: one uint64 key per pixel, one int32 pixel index per point, n_frames + 1 first-box indices
+ * and n_boxes + 1 int64 box offsets.  0 for empty or refused sizes. */
+size_t mpsr_scene_workspace_bytes(int n_frames, long long total_pixels, int n_boxes, int points_per_box);
+
+/* xyz_global (n_boxes, points_per_box, 3) float32 in the camera frame; valid_mask (n_boxes, points_per_box) float32 or
+ * null (all valid); box_keep (n_boxes) int32 or null (all kept); cam_p (n_frames, 3, 4) fp64.  Per point, in fp64
+ * without contraction: u_k = ((P[k][0] x + P[k][1] y) + P[k][2] z) + P[k][3], col = rint(u0 / u2), row = rint(u1 / u2)
+ * (half to even).  A point is KEPT when its box is kept, its mask is > 0, x, y and z are finite, z > 0, u2 > 0,
+ * 0 <= col < w and 0 <= row < h.  A kept point stores its pixel index row * w + col in the workspace (a dropped one -1)
+ * and lowers its pixel's key, ((uint64) float_bits(z) << 32) | (b * points_per_box + p), with an unsigned 64-bit
+ * atomicMin: the nearer point wins, on equal float32 depth the lower point index.  (mpsr_lidar_project_depths keeps the
+ * LAST duplicate of a pixel instead.) */
+int mpsr_scene_project(const float *xyz_global, const float *valid_mask, const int *box_frame,
+                       const int *box_frame_host, const int *box_keep, const double *cam_p, const int *frame_hw,
+                       const int *frame_hw_host, const long long *pixel_offset, const long long *pixel_offset_host,
+                       int n_frames, int n_boxes, int points_per_box, void *workspace, size_t workspace_bytes,
+                       mpsr_stream_t stream);
+
+/* depth (total_pixels) float32: the winner's z bit for bit, 0 for a pixel no kept point fell on; instance
+ * (total_pixels) uint8: the winner box's ordinal within its frame, 255 for such a pixel (the ground-truth instance
+ * images' convention).  A frame of more than MPSR_INSTANCE_MAX_BOXES boxes is MPSR_ERR_INVALID_ARG. */
+int mpsr_scene_resolve(const int *box_frame, const int *box_frame_host, int n_frames, long long total_pixels,
+                       int n_boxes, int points_per_box, const void *workspace, size_t workspace_bytes, float *depth,
+                       unsigned char *instance, mpsr_stream_t stream);
+
+/* The kept points (visible_only: the pixels' winners only) in box order and, within a box, point order.  kept_per_box
+ * and visible_per_box (n_boxes) int32 are both written whatever visible_only says.  Of the M selected points: xyz
+ * (M, 3) float32 the input values copied; rgb (M, 3) float32 = images[f][3 * pixel + c], images a device table of
+ * n_frames pointers to (h, w, 3) float32 images (nearest pixel; images and rgb both null: no colours); box (M) int32;
+ * pixel (M) int32 = row * w + col; frame_offset (n_frames + 1) int64: frame f owns rows frame_offset[f] ..
+ * frame_offset[f + 1], frame_offset[n_frames] = M.  The output buffers hold n_boxes * points_per_box rows; rows from M
+ * on are not written.  Counts, a one-workgroup scan and ranks from wave ballots: no atomics, and two calls return the
+ * same bytes. */
+int mpsr_scene_compact(const float *xyz_global, const int *box_frame, const float *const *images,
+                       const long long *pixel_offset, int n_frames, long long total_pixels, int n_boxes,
+                       int points_per_box, int visible_only, void *workspace, size_t workspace_bytes, float *xyz,
+                       float *rgb, int *box, int *pixel, long long *frame_offset, int *kept_per_box,
+                       int *visible_per_box, mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,12 @@ SIGNATURES = {
     "mpsr_metric_stats": (c_i, [c_f, c_f, c_i, c_i, ctypes.POINTER(c_i), c_i, c_i, c_i, c_f, c_f, c_f]),
     "mpsr_train_log_append": (c_i, [TrainLogTerms, c_i, c_f, c_i, ctypes.c_float, ctypes.c_float, ctypes.c_longlong, c_f,
                                     c_f, c_i, c_i, c_i, c_f]),
+    "mpsr_scene_workspace_bytes": (c_sz, [c_i, ctypes.c_longlong, c_i, c_i]),
+    "mpsr_scene_project": (c_i, [c_f, c_f, c_f, ctypes.c_void_p, c_f, c_f, c_f, ctypes.c_void_p, c_f, ctypes.c_void_p,
+                                 c_i, c_i, c_i, c_f, c_sz, c_f]),
+    "mpsr_scene_resolve": (c_i, [c_f, ctypes.c_void_p, c_i, ctypes.c_longlong, c_i, c_i, c_f, c_sz, c_f, c_f, c_f]),
+    "mpsr_scene_compact": (c_i, [c_f, c_f, c_f, c_f, c_i, ctypes.c_longlong, c_i, c_i, c_i, c_f, c_sz, c_f, c_f, c_f,
+                                 c_f, c_f, c_f, c_f, c_f]),
 }
 
 

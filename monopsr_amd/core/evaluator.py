@@ -25,6 +25,10 @@ in <predictions_base_dir>/evaluated_<split>.txt and every report in kitti_report
 are sweep_checkpoints / repeated_sweep, plain functions of a checkpoint list, the evaluated set and a callable.
 python -m monopsr_amd.experiments.run_evaluation is the command line of a sweep.
 
+chunk_hook: a callable that sees every chunk's (rows, samples, outs) during the pass, so that one network pass serves
+the label files and whatever else is made of the predictions (experiments/run_inference.py: the scenes of
+core/scene_reconstruction.py).
+
 Not built: TF summaries and metrics_to_show, both IoU settings in one pass.
 """
 import argparse
@@ -102,7 +106,7 @@ class Evaluator:
 
     def __init__(self, model, dataset, score_threshold=0.1, predictions_base_dir=None, batch_size=8,
                  project_3d_box=False, iou='standard', compute_metrics=True, compute_losses=True, metric_stats=False,
-                 skip_evaluated_checkpoints=True):
+                 skip_evaluated_checkpoints=True, chunk_hook=None):
         if iou not in kitti_eval.MIN_OVERLAP:
             raise ValueError('iou must be one of %s' % sorted(kitti_eval.MIN_OVERLAP))
         if int(batch_size) < 1:
@@ -115,6 +119,10 @@ class Evaluator:
         self.compute_losses = bool(compute_losses)
         self.metric_stats = bool(metric_stats)
         self.skip_evaluated_checkpoints = bool(skip_evaluated_checkpoints)
+        # chunk_hook(rows, samples, outs), called after each build_batch of the pass: rows = the chunk's frames as rows
+        # of the dataset's frame tables (sample_names), samples / outs what get_sample_dict / build_batch returned
+        # (experiments/run_inference.py writes the scenes through it); None: nothing is called
+        self.chunk_hook = chunk_hook
         # after a run_once with metric_stats: (values (n,10) float32, frame (n,) int32) on the device
         self.metric_table = None
         self._loss_model = None
@@ -154,6 +162,8 @@ class Evaluator:
                 rows = np.arange(a, min(a + self.batch_size, ds.num_samples))
                 samples = ds.get_sample_dict(position[rows], epoch=0)
                 outs = model.build_batch(samples)
+                if self.chunk_hook is not None:
+                    self.chunk_hook(rows, samples, outs)
                 for r, s, o in zip(rows, samples, outs):
                     n = int(s['num_objs'])
                     b3, b2 = instance_utils.format_boxes(
@@ -282,9 +292,9 @@ class Evaluator:
             result['report'] = kitti_eval.format_report(result['kitti'], global_step)
         return result
 
-    def run_checkpoint_once(self, path, width_div=1):
+    def restore_checkpoint(self, path, width_div=1):
         """Restores the model's weights from a checkpoint (a TensorFlow V2 prefix, its directory, or an .npz) through
-        checkpoint_utils, then run_once at the checkpoint's global step."""
+        checkpoint_utils.  -> the checkpoint's global step, or None."""
         from monopsr_amd.core import checkpoint_utils, device_net
         from monopsr_amd.core import weights as W
         checkpoint = checkpoint_utils.load_checkpoint(path)
@@ -296,7 +306,11 @@ class Evaluator:
         self.model.device_net = device_net.DeviceNet(weights, device=self.dataset.device, width_div=width_div,
                                                      full_trunk=True)
         step = checkpoint.get('global_step')
-        return self.run_once(None if step is None else int(np.asarray(step)))
+        return None if step is None else int(np.asarray(step))
+
+    def run_checkpoint_once(self, path, width_div=1):
+        """restore_checkpoint, then run_once at the checkpoint's global step."""
+        return self.run_once(self.restore_checkpoint(path, width_div=width_div))
 
     # ---- sweeps over a checkpoint directory
 

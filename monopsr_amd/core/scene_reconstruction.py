@@ -1,0 +1,309 @@
+"""The output side of the reconstruction: the predicted instance clouds of a chunk of frames in the camera frame,
+coloured from the image, and the same clouds rendered back into the image as a depth map and an instance image
+(csrc/scene.hip).
+
+    scene = reconstruct_frames(model, samples, outs, min_score=0.1)     # samples / outs of one Evaluator chunk
+    for f, s in enumerate(samples):
+        save_frame(scene_output_dirs(base), s['sample_name'], scene.frame(f))
+
+writes <name>.ply (binary little-endian: float x y z, uchar red green blue, int box), the depth map as
+depth_map_utils.save_depth_map writes a LiDAR one and the instance image as instance_utils.save_instance_image writes a
+ground-truth one (255 background, k the k-th box of the frame).
+
+The rendering is a z-buffer: the nearest point of a pixel wins, on equal float32 depth the lower point index.  (The
+LiDAR projection of depth_map_utils keeps the last duplicate of a pixel, as the reference does with a LiDAR cloud.)
+Colours are the image's value at the point's pixel (nearest pixel, exact).  Everything stays on the device; one copy of
+n_frames + 1 offsets to the host per call tells where each frame's points are.
+"""
+import ctypes
+import os
+
+import numpy as np
+
+from monopsr_amd import _lib
+
+MAX_BOXES = 255  # per frame: 255 of an instance image is the background
+
+_PLY_DTYPE = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('green', 'u1'), ('blue', 'u1'),
+                       ('box', '<i4')])
+_PLY_HEADER = ('ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n'
+               'property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nproperty int box\n'
+               'end_header\n')
+
+
+def _empty(shape, dtype, device):
+    """Every device buffer of this module comes from here (tests/test_scene_reconstruction_gpu.py poisons them)."""
+    import torch
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+class FrameScene(object):
+    """One frame of a SceneResult: xyz (m,3), rgb (m,3) or None, box (m,) int32 = the ordinal within the frame (the
+    value of the instance image), pixel (m,) int32 = row * w + col, depth_map (h,w) float32, instance_map (h,w) uint8;
+    kept_per_box / visible_per_box (n,) int32 of the frame's boxes."""
+    __slots__ = ('xyz', 'rgb', 'box', 'pixel', 'depth_map', 'instance_map', 'kept_per_box', 'visible_per_box')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+class SceneResult(object):
+    """What project_instance_points returns, device tensors: xyz (M,3) float32, rgb (M,3) float32 or None, box (M,)
+    int32 (index into the call's boxes), pixel (M,) int32, frame_offset (F+1,) int64 (frame f owns rows
+    frame_offset[f] .. frame_offset[f+1]), depth_maps / instance_maps: lists of (H_f, W_f) float32 / uint8,
+    kept_per_box / visible_per_box (B,) int32.  frame_offset_host and box_frame_host are their host copies."""
+    __slots__ = ('xyz', 'rgb', 'box', 'pixel', 'frame_offset', 'depth_maps', 'instance_maps', 'kept_per_box',
+                 'visible_per_box', 'frame_offset_host', 'box_frame_host')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    @property
+    def num_frames(self):
+        return len(self.depth_maps)
+
+    def frame(self, f):
+        a, b = int(self.frame_offset_host[f]), int(self.frame_offset_host[f + 1])
+        b0, b1 = (int(v) for v in np.searchsorted(self.box_frame_host, [f, f + 1]))
+        return FrameScene(xyz=self.xyz[a:b], rgb=None if self.rgb is None else self.rgb[a:b], box=self.box[a:b] - b0,
+                          pixel=self.pixel[a:b], depth_map=self.depth_maps[f], instance_map=self.instance_maps[f],
+                          kept_per_box=self.kept_per_box[b0:b1], visible_per_box=self.visible_per_box[b0:b1])
+
+
+def _host_ints(v):
+    import torch
+    if torch.is_tensor(v):
+        v = v.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(v).astype(np.int32))
+
+
+def project_instance_points(xyz_global, box_frame, cam_p, frame_shapes, images=None, valid_mask=None, keep=None,
+                            visible_only=False):
+    """The direct wrapper of mpsr_scene_project / _resolve / _compact.
+
+    xyz_global (B,P,3) or (B,H,W,3) float32 CUDA tensor in the camera frame; box_frame (B,) the frame of each box,
+    never decreasing (a host sequence: a tensor is copied to the host); cam_p (F,3,4), a tensor, an array or a list of
+    (3,4), used in float64; frame_shapes F x (h, w[, ...]); images None or F CUDA tensors (h_f, w_f, 3) float32;
+    valid_mask None or (B,P) / (B,H,W[,1]) float32, a point counts where it is > 0; keep None or (B,) (bool or int): a
+    box with 0 takes no part.  visible_only: the cloud holds each pixel's winner only.  -> SceneResult."""
+    import torch
+    if not torch.is_tensor(xyz_global) or not xyz_global.is_cuda:
+        raise _lib.MpsrError('expected xyz_global on the GPU; monopsr_amd has no CPU path')
+    if xyz_global.dim() not in (3, 4) or xyz_global.shape[-1] != 3:
+        raise _lib.InvalidArgumentError('xyz_global must be (B, P, 3) or (B, H, W, 3), got %s'
+                                        % (tuple(xyz_global.shape),))
+    dev = xyz_global.device
+    nb = int(xyz_global.shape[0])
+    npts = int(np.prod(xyz_global.shape[1:-1]))
+    nf = len(frame_shapes)
+    hw = np.ascontiguousarray(np.asarray([[int(s[0]), int(s[1])] for s in frame_shapes], np.int32).reshape(nf, 2))
+    if nf and int(hw.min()) <= 0:
+        raise _lib.InvalidArgumentError('frame_shapes must be positive, got %s' % (hw.tolist(),))
+    bf = _host_ints(box_frame).reshape(-1)
+    if len(bf) != nb:
+        raise _lib.InvalidArgumentError('box_frame has %d entries for %d boxes' % (len(bf), nb))
+    if nb and (int(bf.min()) < 0 or int(bf.max()) >= nf or bool(np.any(np.diff(bf) < 0))):
+        raise _lib.InvalidArgumentError('box_frame must lie in [0, %d) and never decrease' % nf)
+    if nb and int(np.bincount(bf).max()) > MAX_BOXES:
+        raise _lib.InvalidArgumentError('a frame has %d boxes, more than %d (255 of an instance image is the '
+                                        'background)' % (int(np.bincount(bf).max()), MAX_BOXES))
+    if nb * npts >= 2 ** 32:
+        raise _lib.InvalidArgumentError('%d boxes of %d points: the point index does not fit 32 bits' % (nb, npts))
+    if images is not None and len(images) != nf:
+        raise _lib.InvalidArgumentError('%d images for %d frames' % (len(images), nf))
+    offs = np.zeros(nf + 1, np.int64)
+    offs[1:] = np.cumsum(hw[:, 0].astype(np.int64) * hw[:, 1])
+    total = int(offs[-1])
+    lib = _lib.lib()
+    i32, i64, f32 = torch.int32, torch.int64, torch.float32
+    with torch.cuda.device(dev):
+        if torch.is_tensor(cam_p):
+            cam = cam_p.to(dev).double().reshape(-1, 3, 4).contiguous()
+        else:
+            cam = torch.from_numpy(np.ascontiguousarray(np.stack(
+                [(c.detach().cpu().numpy() if torch.is_tensor(c) else np.asarray(c)).astype(np.float64).reshape(3, 4)
+                 for c in cam_p] or [np.zeros((3, 4))]))).to(dev)
+        if nf and cam.shape[0] != nf:
+            raise _lib.InvalidArgumentError('%d cameras for %d frames' % (cam.shape[0], nf))
+        xyz_in = xyz_global.detach().to(f32).reshape(nb, npts, 3).contiguous()
+        mask = None
+        if valid_mask is not None:
+            if valid_mask.numel() != nb * npts:
+                raise _lib.InvalidArgumentError('valid_mask %s does not match %d boxes of %d points'
+                                                % (tuple(valid_mask.shape), nb, npts))
+            mask = valid_mask.detach().to(dev).to(f32).reshape(nb, npts).contiguous()
+        keep_d = None
+        if keep is not None:
+            keep_d = torch.as_tensor(keep, device=dev).reshape(-1).ne(0).to(i32).contiguous()
+            if keep_d.numel() != nb:
+                raise _lib.InvalidArgumentError('keep has %d entries for %d boxes' % (keep_d.numel(), nb))
+        table = rgb = None
+        imgs = []
+        if images is not None:
+            for f, im in enumerate(images):
+                if not torch.is_tensor(im) or tuple(im.shape) != (int(hw[f, 0]), int(hw[f, 1]), 3):
+                    raise _lib.InvalidArgumentError('image %d must be a (%d, %d, 3) tensor' % (f, hw[f, 0], hw[f, 1]))
+                imgs.append(im.detach().to(dev).to(f32).contiguous())  # (kept alive until the launches are queued)
+            table = torch.from_numpy(np.asarray([_lib.ptr(im) for im in imgs] or [0], np.uint64).view(np.int64)).to(dev)
+        cap = nb * npts
+        depth = _empty((total,), f32, dev)
+        inst = _empty((total,), torch.uint8, dev)
+        xyz = _empty((cap, 3), f32, dev)
+        if images is not None:
+            rgb = _empty((cap, 3), f32, dev)
+        box, pixel = _empty((cap,), i32, dev), _empty((cap,), i32, dev)
+        kept, visible = _empty((nb,), i32, dev), _empty((nb,), i32, dev)
+        frame_offset = _empty((nf + 1,), i64, dev)
+        if nf == 0 or cap == 0 or total == 0:  # nothing to launch: empty maps, an empty cloud
+            depth.zero_()
+            inst.fill_(255)
+            kept.zero_()
+            visible.zero_()
+            frame_offset.zero_()
+            fo_host = np.zeros(nf + 1, np.int64)
+        else:
+            bf_d, hw_d, offs_d = torch.from_numpy(bf).to(dev), torch.from_numpy(hw).to(dev), torch.from_numpy(offs).to(dev)
+            ws = _empty((lib.mpsr_scene_workspace_bytes(nf, total, nb, npts),), torch.uint8, dev)
+            stream = _lib.stream()
+            host = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+            _lib.check(lib.mpsr_scene_project(
+                _lib.ptr(xyz_in), _lib.ptr(mask), _lib.ptr(bf_d), host(bf), _lib.ptr(keep_d), _lib.ptr(cam),
+                _lib.ptr(hw_d), host(hw), _lib.ptr(offs_d), host(offs), nf, nb, npts, _lib.ptr(ws), ws.numel(), stream))
+            _lib.check(lib.mpsr_scene_resolve(_lib.ptr(bf_d), host(bf), nf, total, nb, npts, _lib.ptr(ws), ws.numel(),
+                                              _lib.ptr(depth), _lib.ptr(inst), stream))
+            _lib.check(lib.mpsr_scene_compact(
+                _lib.ptr(xyz_in), _lib.ptr(bf_d), _lib.ptr(table), _lib.ptr(offs_d), nf, total, nb, npts,
+                int(bool(visible_only)), _lib.ptr(ws), ws.numel(), _lib.ptr(xyz), _lib.ptr(rgb), _lib.ptr(box),
+                _lib.ptr(pixel), _lib.ptr(frame_offset), _lib.ptr(kept), _lib.ptr(visible), stream))
+            fo_host = frame_offset.cpu().numpy()  # the one copy to the host: M and where each frame's points are
+        m = int(fo_host[-1])
+    return SceneResult(
+        xyz=xyz[:m], rgb=None if rgb is None else rgb[:m], box=box[:m], pixel=pixel[:m], frame_offset=frame_offset,
+        depth_maps=[depth[int(offs[f]):int(offs[f + 1])].view(int(hw[f, 0]), int(hw[f, 1])) for f in range(nf)],
+        instance_maps=[inst[int(offs[f]):int(offs[f + 1])].view(int(hw[f, 0]), int(hw[f, 1])) for f in range(nf)],
+        kept_per_box=kept, visible_per_box=visible, frame_offset_host=fo_host, box_frame_host=bf)
+
+
+def reconstruct_frames(model, samples, outs, min_score=None, visible_only=False):
+    """The scene of a chunk: `samples` as dataset.get_sample_dict returns them, `outs` as model.build_batch returns
+    them.  The first num_objs rows of each frame: KEY_INST_XYZ_MAP_LOCAL placed with KEY_VIEW_ANG and KEY_CENTROIDS
+    (instance_utils.tf_inst_xyz_map_local_to_global), masked by gt_valid_mask_maps where the sample carries them, kept
+    where label_scores >= min_score (None: all), coloured from rgb_image, projected with cam_p.  -> SceneResult."""
+    import torch
+    from monopsr_amd.core import constants
+    from monopsr_amd.datasets.kitti import instance_utils
+    if len(samples) != len(outs):
+        raise ValueError('%d samples, %d outputs' % (len(samples), len(outs)))
+    if len(samples) == 0:
+        raise ValueError('reconstruct_frames needs at least one frame')
+    roi = tuple(model.map_roi_size)
+    dev = samples[0]['rgb_image'].device
+    counts = [int(s['num_objs']) for s in samples]
+    with_mask = all(s.get('gt_valid_mask_maps') is not None for s in samples)
+    with torch.cuda.device(dev), torch.no_grad():
+        cat = lambda ts, tail: torch.cat([t.reshape((n,) + tail) for t, n in zip(ts, counts)], 0)
+        local = cat([o[constants.KEY_INST_XYZ_MAP_LOCAL][0:n] for o, n in zip(outs, counts)], roi + (3,))
+        view = cat([o[constants.KEY_VIEW_ANG][0:n] for o, n in zip(outs, counts)], (1,))
+        cen = cat([o[constants.KEY_CENTROIDS][0:n] for o, n in zip(outs, counts)], (3,))
+        glob = instance_utils.tf_inst_xyz_map_local_to_global(local, roi, view, cen)
+        mask = cat([s['gt_valid_mask_maps'][0:n] for s, n in zip(samples, counts)], roi) if with_mask else None
+        keep = None
+        if min_score is not None:
+            keep = cat([s['label_scores'][0:n] for s, n in zip(samples, counts)], ()) >= float(min_score)
+        cam_p = torch.stack([s['cam_p'].reshape(3, 4) for s in samples], 0)
+        box_frame = np.repeat(np.arange(len(samples)), counts)
+        return project_instance_points(glob, box_frame, cam_p, [tuple(s['rgb_image'].shape) for s in samples],
+                                       images=[s['rgb_image'] for s in samples], valid_mask=mask, keep=keep,
+                                       visible_only=visible_only)
+
+
+# ---- files
+
+
+def colours_to_uint8(rgb):
+    """float colours -> uchar: clipped to [0, 255], then rounded half to even (254.5 -> 254, 255.5 -> 255, -0.5 -> 0,
+    300 -> 255); NaN -> 0."""
+    c = np.nan_to_num(np.asarray(rgb, np.float64), nan=0.0)
+    return np.rint(np.clip(c, 0.0, 255.0)).astype(np.uint8)
+
+
+def write_ply(path, xyz, rgb=None, box=None):
+    """Binary little-endian PLY of n vertices: float x y z, uchar red green blue, int box.  xyz (n,3); rgb (n,3) float
+    (colours_to_uint8) or uint8, None: 0; box (n,) int, None: 0.  n may be 0."""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    n = len(xyz)
+    v = np.zeros(n, _PLY_DTYPE)
+    v['x'], v['y'], v['z'] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if rgb is not None:
+        rgb = np.asarray(rgb)
+        c = (rgb if rgb.dtype == np.uint8 else colours_to_uint8(rgb)).reshape(n, 3)
+        v['red'], v['green'], v['blue'] = c[:, 0], c[:, 1], c[:, 2]
+    if box is not None:
+        v['box'] = np.asarray(box).reshape(n)
+    with open(path, 'wb') as f:
+        f.write((_PLY_HEADER % n).encode('ascii'))
+        f.write(v.tobytes())
+
+
+def read_ply(path):
+    """A file of write_ply -> (xyz (n,3) float32, rgb (n,3) uint8, box (n,) int32)."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    end = data.find(b'end_header\n')
+    if end < 0 or not data.startswith(b'ply\n'):
+        raise ValueError('%s is not a PLY file' % path)
+    header = data[:end + len(b'end_header\n')].decode('ascii')
+    n = None
+    for line in header.splitlines():
+        if line.startswith('element vertex '):
+            n = int(line.split()[2])
+    if n is None or header != _PLY_HEADER % n:
+        raise ValueError('%s: not the header write_ply writes' % path)
+    body = data[len(header):]
+    if len(body) != n * _PLY_DTYPE.itemsize:
+        raise ValueError('%s: %d bytes of vertices, expected %d' % (path, len(body), n * _PLY_DTYPE.itemsize))
+    v = np.frombuffer(body, _PLY_DTYPE)
+    return (np.stack([v['x'], v['y'], v['z']], 1).astype(np.float32).reshape(n, 3),
+            np.stack([v['red'], v['green'], v['blue']], 1).reshape(n, 3), v['box'].astype(np.int32))
+
+
+SCENE_DIRS = ('points', 'depth', 'instances')
+
+
+def scene_output_dirs(base):
+    """{'points' | 'depth' | 'instances': <base>/<kind>}, created."""
+    dirs = {k: os.path.join(base, k) for k in SCENE_DIRS}
+    for d in dirs.values():
+        os.makedirs(d, exist_ok=True)
+    return dirs
+
+
+def save_frame(out_dirs, name, frame_result):
+    """points/<name>.ply, depth/<name>.png (depth_map_utils.save_depth_map: uint16, 1/256 m) and instances/<name>.png
+    (instance_utils.save_instance_image) of a FrameScene.  -> the three paths."""
+    from monopsr_amd.datasets.kitti import depth_map_utils, instance_utils
+    fr = frame_result
+    host = lambda t: None if t is None else t.detach().cpu().numpy()
+    paths = (os.path.join(out_dirs['points'], name + '.ply'), os.path.join(out_dirs['depth'], name + '.png'),
+             os.path.join(out_dirs['instances'], name + '.png'))
+    write_ply(paths[0], host(fr.xyz), host(fr.rgb), host(fr.box))
+    # (a depth beyond the PNG's 16 bits, 256 m, has no place in the format: stored as 0, "no depth")
+    depth = host(fr.depth_map)
+    depth_map_utils.save_depth_map(paths[1], np.where(depth < 256.0, depth, np.float32(0.0)))
+    instance_utils.save_instance_image(paths[2], host(fr.instance_map))
+    return paths
+
+
+def save_empty_frame(out_dirs, name, image_shape):
+    """The three files of a frame without a box (the Evaluator writes an empty label file for it): no vertex, depth 0,
+    instance 255 everywhere.  -> the three paths."""
+    from monopsr_amd.datasets.kitti import depth_map_utils, instance_utils
+    h, w = int(image_shape[0]), int(image_shape[1])
+    paths = (os.path.join(out_dirs['points'], name + '.ply'), os.path.join(out_dirs['depth'], name + '.png'),
+             os.path.join(out_dirs['instances'], name + '.png'))
+    write_ply(paths[0], np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8), np.zeros(0, np.int32))
+    depth_map_utils.save_depth_map(paths[1], np.zeros((h, w), np.float32))
+    instance_utils.save_instance_image(paths[2], np.full((h, w), 255, np.uint8))
+    return paths

@@ -1,0 +1,406 @@
+// Scene reconstruction on the device: the predicted instance clouds of a chunk of frames (B boxes of P points each, in
+// the camera frame: what instance_utils.tf_inst_xyz_map_local_to_global returns) projected into their images, rendered
+// as a depth map and an instance image per frame, and compacted into one coloured cloud.
+//
+// mpsr_scene_project: one thread per point computes, in fp64 without contraction (rows3 and rint as in depth_fill.hip),
+//   pixel = rint(u0 / u2), rint(u1 / u2) of cam_p . [x y z 1], stores the pixel index of a kept point (-1 of a dropped
+//   one) and lowers the pixel's 64-bit key ((uint64) float_bits(z) << 32 | point index) with an unsigned atomicMin: the
+//   one atomic of this file.  A kept point has z > 0, so its float bits order as its value: the NEARER point wins, and
+//   on equal float32 depth the LOWER point index, in whatever order the waves run.  This is a true z-buffer.  The LiDAR
+//   projection of depth_fill.hip is not: it keeps the LAST duplicate of a pixel, near or far, because that is what the
+//   reference's fancy assignment does with a LiDAR cloud.
+// mpsr_scene_resolve: one thread per pixel turns the key into depth (the key's upper half, the winner's z bit for bit;
+//   0 where no point fell) and instance (the winner box's ordinal within its frame; 255 where no point fell).
+// mpsr_scene_compact: per-box counts of kept and of visible points (a visible point is its pixel's winner), a one-block
+//   exclusive scan over the boxes, and a write pass of one workgroup per box that places a point at its box's offset
+//   plus its rank within the box: __ballot / __popcll prefix counts within a wave, wave offsets through LDS, a running
+//   base from one 256-point slice of the box to the next.  No atomics: the write position does not depend on scheduling.
+#include "common.h"
+
+#include <algorithm>
+#include <climits>
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr unsigned long long kEmptyKey = ~0ULL;  // the memset's 0xff bytes; no kept point has it (its z is finite)
+
+__device__ __forceinline__ void rows3(const double *m, double x, double y, double z, double *o)
+{
+    for (int r = 0; r < 3; ++r) o[r] = ((m[4 * r] * x + m[4 * r + 1] * y) + m[4 * r + 2] * z) + m[4 * r + 3];
+}
+
+// frame_box[f] = the first box of frame f (box_frame is sorted), frame_box[n_frames] = n_boxes
+__global__ void __launch_bounds__(kThreads) frame_box_kernel(const int *__restrict__ box_frame, int n_boxes,
+                                                             int n_frames, int *__restrict__ frame_box)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f > n_frames) return;
+    int lo = 0, hi = n_boxes;  // lower bound of f
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (box_frame[mid] < f)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    frame_box[f] = lo;
+}
+
+__global__ void __launch_bounds__(kThreads) project_kernel(const float *__restrict__ xyz,
+                                                           const float *__restrict__ valid_mask,
+                                                           const int *__restrict__ box_frame,
+                                                           const int *__restrict__ box_keep,
+                                                           const double *__restrict__ cam_p,
+                                                           const int *__restrict__ frame_hw,
+                                                           const long long *__restrict__ pixel_offset, long long n,
+                                                           int points_per_box, unsigned long long *__restrict__ keys,
+                                                           int *__restrict__ pix)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / points_per_box);
+        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+        int at = -1;
+        const bool on = (box_keep == nullptr || box_keep[b] != 0) && (valid_mask == nullptr || valid_mask[i] > 0.0f) &&
+                        isfinite(x) && isfinite(y) && isfinite(z) && z > 0.0f;
+        if (on) {
+            const int f = box_frame[b];
+            const int h = frame_hw[2 * f], w = frame_hw[2 * f + 1];
+            double u[3];
+            rows3(cam_p + 12 * f, (double)x, (double)y, (double)z, u);
+            const double col = rint(u[0] / u[2]), row = rint(u[1] / u[2]);
+            // NaN fails every comparison; +-inf fails the range test; -0.0 is inside
+            if (u[2] > 0.0 && col >= 0.0 && col < (double)w && row >= 0.0 && row < (double)h) {
+                at = (int)row * w + (int)col;
+                const unsigned long long key =
+                    ((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)(unsigned)i;
+                atomicMin(keys + pixel_offset[f] + at, key);
+            }
+        }
+        pix[i] = at;
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) resolve_kernel(const unsigned long long *__restrict__ keys,
+                                                           long long total_pixels, const int *__restrict__ box_frame,
+                                                           const int *__restrict__ frame_box, int points_per_box,
+                                                           float *__restrict__ depth,
+                                                           unsigned char *__restrict__ instance)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total_pixels;
+         i += (long long)gridDim.x * blockDim.x) {
+        const unsigned long long key = keys[i];
+        float d = 0.0f;
+        unsigned char id = 255;
+        if (key != kEmptyKey) {
+            d = __uint_as_float((unsigned)(key >> 32));
+            const int b = (int)((unsigned)key / (unsigned)points_per_box);
+            id = (unsigned char)(b - frame_box[box_frame[b]]);
+        }
+        depth[i] = d;
+        instance[i] = id;
+    }
+}
+
+// is point i (pixel `at` of its frame, whose keys start at fkeys) its pixel's winner?
+__device__ __forceinline__ bool wins(const unsigned long long *fkeys, int at, long long i)
+{
+    return (unsigned)fkeys[at] == (unsigned)i;
+}
+
+// one workgroup per box: kept[b] and visible[b]
+__global__ void __launch_bounds__(kThreads) count_kernel(const unsigned long long *__restrict__ keys,
+                                                         const int *__restrict__ pix,
+                                                         const int *__restrict__ box_frame,
+                                                         const long long *__restrict__ pixel_offset,
+                                                         int points_per_box, int *__restrict__ kept,
+                                                         int *__restrict__ visible)
+{
+    __shared__ int part[2][kWaves];
+    const int b = blockIdx.x;
+    const unsigned long long *fkeys = keys + pixel_offset[box_frame[b]];
+    const long long i0 = (long long)b * points_per_box;
+    int nk = 0, nv = 0;  // per wave: every lane holds its wave's sums
+    for (int p0 = 0; p0 < points_per_box; p0 += kThreads) {
+        const int p = p0 + threadIdx.x;
+        const int at = p < points_per_box ? pix[i0 + p] : -1;
+        nk += __popcll(__ballot(at >= 0));
+        nv += __popcll(__ballot(at >= 0 && wins(fkeys, at, i0 + p)));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        part[0][threadIdx.x >> 6] = nk;
+        part[1][threadIdx.x >> 6] = nv;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int sk = 0, sv = 0;
+        for (int v = 0; v < kWaves; ++v) {
+            sk += part[0][v];
+            sv += part[1][v];
+        }
+        kept[b] = sk;
+        visible[b] = sv;
+    }
+}
+
+// One workgroup: box_offset (n_boxes + 1) = the exclusive scan of the boxes' counts (int64), and frame_offset
+// (n_frames + 1) = box_offset at each frame's first box (n_boxes past the last box): the thread of box b writes the
+// entries of the frames that start at b, i.e. box_frame[b] and the frames without a box in front of it.
+__global__ void __launch_bounds__(kThreads) scan_kernel(const int *__restrict__ counts, int n_boxes,
+                                                        const int *__restrict__ box_frame, int n_frames,
+                                                        long long *__restrict__ box_offset,
+                                                        long long *__restrict__ frame_offset)
+{
+    __shared__ long long wave_sum[kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long base = 0;
+    for (int b0 = 0; b0 < n_boxes; b0 += kThreads) {
+        const int b = b0 + threadIdx.x;
+        const long long c = b < n_boxes ? counts[b] : 0;
+        long long incl = c;  // inclusive scan within the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long up = __shfl_up(incl, o);
+            if (lane >= o) incl += up;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        long long before = 0, all = 0;
+        for (int v = 0; v < kWaves; ++v) {
+            before += v < wave ? wave_sum[v] : 0;
+            all += wave_sum[v];
+        }
+        if (b < n_boxes) {
+            const long long excl = base + before + incl - c;
+            box_offset[b] = excl;
+            for (int f = b ? box_frame[b - 1] + 1 : 0; f <= box_frame[b]; ++f) frame_offset[f] = excl;
+        }
+        base += all;
+        __syncthreads();  // wave_sum is rewritten by the next slice
+    }
+    if (threadIdx.x == 0) {
+        box_offset[n_boxes] = base;
+        for (int f = box_frame[n_boxes - 1] + 1; f <= n_frames; ++f) frame_offset[f] = base;
+    }
+}
+
+// one workgroup per box: its selected points, in point order, to box_offset[b] + rank
+__global__ void __launch_bounds__(kThreads) write_kernel(const float *__restrict__ xyz_in,
+                                                         const unsigned long long *__restrict__ keys,
+                                                         const int *__restrict__ pix,
+                                                         const int *__restrict__ box_frame,
+                                                         const long long *__restrict__ pixel_offset,
+                                                         const float *const *__restrict__ images,
+                                                         const long long *__restrict__ box_offset,
+                                                         int points_per_box, int visible_only,
+                                                         float *__restrict__ xyz, float *__restrict__ rgb,
+                                                         int *__restrict__ box, int *__restrict__ pixel)
+{
+    __shared__ int wave_n[kWaves];
+    const int b = blockIdx.x, f = box_frame[b];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long *fkeys = keys + pixel_offset[f];
+    const float *image = images ? images[f] : nullptr;
+    const long long i0 = (long long)b * points_per_box;
+    long long base = box_offset[b];
+    for (int p0 = 0; p0 < points_per_box; p0 += kThreads) {
+        const int p = p0 + threadIdx.x;
+        const int at = p < points_per_box ? pix[i0 + p] : -1;
+        const bool take = at >= 0 && (!visible_only || wins(fkeys, at, i0 + p));
+        const unsigned long long mask = __ballot(take);
+        if (lane == 0) wave_n[wave] = __popcll(mask);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int v = 0; v < kWaves; ++v) {
+            before += v < wave ? wave_n[v] : 0;
+            all += wave_n[v];
+        }
+        if (take) {
+            const long long o = base + before + __popcll(mask & ((1ULL << lane) - 1ULL));
+            const float *q = xyz_in + 3 * (i0 + p);
+            xyz[3 * o] = q[0];
+            xyz[3 * o + 1] = q[1];
+            xyz[3 * o + 2] = q[2];
+            if (image) {
+                const float *c = image + 3 * (long long)at;
+                rgb[3 * o] = c[0];
+                rgb[3 * o + 1] = c[1];
+                rgb[3 * o + 2] = c[2];
+            }
+            box[o] = b;
+            pixel[o] = at;
+        }
+        base += all;
+        __syncthreads();  // wave_n is rewritten by the next slice
+    }
+}
+
+// workspace: [keys: one uint64 per pixel] [pix: one int per point] [frame_box: n_frames + 1 ints]
+// [box_offset: n_boxes + 1 int64]
+struct SceneLayout {
+    size_t keys, pix, frame_box, box_offset, total;
+};
+
+SceneLayout scene_layout(int n_frames, long long total_pixels, int n_boxes, int points_per_box)
+{
+    SceneLayout L;
+    size_t o = 0;
+    L.keys = o;
+    o += mpsr::align_up((size_t)total_pixels * sizeof(unsigned long long), 256);
+    L.pix = o;
+    o += mpsr::align_up((size_t)n_boxes * points_per_box * sizeof(int), 256);
+    L.frame_box = o;
+    o += mpsr::align_up(((size_t)n_frames + 1) * sizeof(int), 256);
+    L.box_offset = o;
+    o += mpsr::align_up(((size_t)n_boxes + 1) * sizeof(long long), 256);
+    L.total = o;
+    return L;
+}
+
+// the sizes every entry point takes; *empty: nothing to do
+int check_sizes(const char *who, int n_frames, long long total_pixels, int n_boxes, int points_per_box, bool *empty)
+{
+    MPSR_REQUIRE(n_frames >= 0 && total_pixels >= 0 && n_boxes >= 0 && points_per_box >= 0,
+                 "%s: negative size (n_frames %d, total_pixels %lld, n_boxes %d, points_per_box %d)", who, n_frames,
+                 total_pixels, n_boxes, points_per_box);
+    MPSR_REQUIRE((long long)n_boxes * points_per_box < (1LL << 32),
+                 "%s: %d boxes of %d points: the point index does not fit the key's 32 bits", who, n_boxes,
+                 points_per_box);
+    MPSR_REQUIRE(total_pixels <= (1LL << 40), "%s: %lld pixels are too many", who, total_pixels);
+    *empty = n_frames == 0 || n_boxes == 0 || points_per_box == 0;
+    return MPSR_OK;
+}
+
+int check_workspace(const char *who, const void *workspace, size_t workspace_bytes, const SceneLayout &L)
+{
+    if (!workspace || workspace_bytes < L.total)
+        return mpsr::fail(MPSR_ERR_WORKSPACE, "%s: workspace %zu bytes < %zu", who, workspace_bytes, L.total);
+    return MPSR_OK;
+}
+
+// box_frame (host): in [0, n_frames) and never decreasing; at most max_per_frame boxes in a frame (0: any number)
+int check_box_frames(const char *who, const int *box_frame_host, int n_boxes, int n_frames, int max_per_frame)
+{
+    int run = 0;
+    for (int b = 0; b < n_boxes; ++b) {
+        const int f = box_frame_host[b];
+        MPSR_REQUIRE(f >= 0 && f < n_frames, "%s: box %d is of frame %d (0..%d)", who, b, f, n_frames - 1);
+        MPSR_REQUIRE(b == 0 || f >= box_frame_host[b - 1], "%s: box_frame decreases at box %d (%d after %d)", who, b,
+                     f, b ? box_frame_host[b - 1] : 0);
+        run = (b > 0 && f == box_frame_host[b - 1]) ? run + 1 : 1;
+        MPSR_REQUIRE(max_per_frame == 0 || run <= max_per_frame,
+                     "%s: frame %d has more than %d boxes (255 of an instance image is the background)", who, f,
+                     max_per_frame);
+    }
+    return MPSR_OK;
+}
+
+unsigned grid_for(long long n) { return (unsigned)std::min<long long>((n + kThreads - 1) / kThreads, 1 << 16); }
+
+}  // namespace
+
+extern "C" size_t mpsr_scene_workspace_bytes(int n_frames, long long total_pixels, int n_boxes, int points_per_box)
+{
+    if (n_frames <= 0 || total_pixels <= 0 || n_boxes <= 0 || points_per_box <= 0) return 0;
+    if ((long long)n_boxes * points_per_box >= (1LL << 32) || total_pixels > (1LL << 40)) return 0;
+    return scene_layout(n_frames, total_pixels, n_boxes, points_per_box).total;
+}
+
+extern "C" int mpsr_scene_project(const float *xyz_global, const float *valid_mask, const int *box_frame,
+                                  const int *box_frame_host, const int *box_keep, const double *cam_p,
+                                  const int *frame_hw, const int *frame_hw_host, const long long *pixel_offset,
+                                  const long long *pixel_offset_host, int n_frames, int n_boxes, int points_per_box,
+                                  void *workspace, size_t workspace_bytes, mpsr_stream_t stream)
+{
+    bool empty;
+    // (total_pixels is pixel_offset_host[n_frames]: read below, once the pointer is known to be there)
+    int st = check_sizes("scene_project", n_frames, 0, n_boxes, points_per_box, &empty);
+    if (st) return st;
+    if (empty) return MPSR_OK;
+    MPSR_REQUIRE(xyz_global && box_frame && box_frame_host, "scene_project: points or box_frame is null");
+    MPSR_REQUIRE(cam_p && frame_hw && frame_hw_host && pixel_offset && pixel_offset_host,
+                 "scene_project: cameras, frame sizes or pixel offsets are null");
+    MPSR_REQUIRE(pixel_offset_host[0] == 0, "scene_project: pixel_offset[0] = %lld, expected 0", pixel_offset_host[0]);
+    for (int f = 0; f < n_frames; ++f) {
+        const int h = frame_hw_host[2 * f], w = frame_hw_host[2 * f + 1];
+        MPSR_REQUIRE(h > 0 && w > 0 && (long long)h * w <= (1LL << 30), "scene_project: frame %d is %d x %d", f, h, w);
+        MPSR_REQUIRE(pixel_offset_host[f + 1] - pixel_offset_host[f] == (long long)h * w,
+                     "scene_project: pixel_offset of frame %d spans %lld pixels, its image has %lld", f,
+                     pixel_offset_host[f + 1] - pixel_offset_host[f], (long long)h * w);
+    }
+    const long long total_pixels = pixel_offset_host[n_frames];
+    st = check_sizes("scene_project", n_frames, total_pixels, n_boxes, points_per_box, &empty);
+    if (st) return st;
+    st = check_box_frames("scene_project", box_frame_host, n_boxes, n_frames, 0);
+    if (st) return st;
+    const SceneLayout L = scene_layout(n_frames, total_pixels, n_boxes, points_per_box);
+    st = check_workspace("scene_project", workspace, workspace_bytes, L);
+    if (st) return st;
+
+    char *ws = static_cast<char *>(workspace);
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws + L.keys);
+    int *pix = reinterpret_cast<int *>(ws + L.pix), *frame_box = reinterpret_cast<int *>(ws + L.frame_box);
+    hipStream_t s = mpsr::as_stream(stream);
+    MPSR_CHECK_HIP(hipMemsetAsync(keys, 0xff, (size_t)total_pixels * sizeof(unsigned long long), s));  // kEmptyKey
+    hipLaunchKernelGGL(frame_box_kernel, dim3((n_frames + 1 + kThreads - 1) / kThreads), dim3(kThreads), 0, s,
+                       box_frame, n_boxes, n_frames, frame_box);
+    const long long n = (long long)n_boxes * points_per_box;
+    hipLaunchKernelGGL(project_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, xyz_global, valid_mask, box_frame,
+                       box_keep, cam_p, frame_hw, pixel_offset, n, points_per_box, keys, pix);
+    MPSR_CHECK_LAUNCH("scene_project");
+    return MPSR_OK;
+}
+
+extern "C" int mpsr_scene_resolve(const int *box_frame, const int *box_frame_host, int n_frames,
+                                  long long total_pixels, int n_boxes, int points_per_box, const void *workspace,
+                                  size_t workspace_bytes, float *depth, unsigned char *instance, mpsr_stream_t stream)
+{
+    bool empty;
+    int st = check_sizes("scene_resolve", n_frames, total_pixels, n_boxes, points_per_box, &empty);
+    if (st) return st;
+    if (empty || total_pixels == 0) return MPSR_OK;
+    MPSR_REQUIRE(box_frame && box_frame_host && depth && instance, "scene_resolve: box_frame or an output is null");
+    st = check_box_frames("scene_resolve", box_frame_host, n_boxes, n_frames, MPSR_INSTANCE_MAX_BOXES);
+    if (st) return st;
+    const SceneLayout L = scene_layout(n_frames, total_pixels, n_boxes, points_per_box);
+    st = check_workspace("scene_resolve", workspace, workspace_bytes, L);
+    if (st) return st;
+    const char *ws = static_cast<const char *>(workspace);
+    hipLaunchKernelGGL(resolve_kernel, dim3(grid_for(total_pixels)), dim3(kThreads), 0, mpsr::as_stream(stream),
+                       reinterpret_cast<const unsigned long long *>(ws + L.keys), total_pixels, box_frame,
+                       reinterpret_cast<const int *>(ws + L.frame_box), points_per_box, depth, instance);
+    MPSR_CHECK_LAUNCH("scene_resolve");
+    return MPSR_OK;
+}
+
+extern "C" int mpsr_scene_compact(const float *xyz_global, const int *box_frame, const float *const *images,
+                                  const long long *pixel_offset, int n_frames, long long total_pixels, int n_boxes,
+                                  int points_per_box, int visible_only, void *workspace, size_t workspace_bytes,
+                                  float *xyz, float *rgb, int *box, int *pixel, long long *frame_offset,
+                                  int *kept_per_box, int *visible_per_box, mpsr_stream_t stream)
+{
+    bool empty;
+    int st = check_sizes("scene_compact", n_frames, total_pixels, n_boxes, points_per_box, &empty);
+    if (st) return st;
+    if (empty || total_pixels == 0) return MPSR_OK;
+    MPSR_REQUIRE(xyz_global && box_frame && pixel_offset, "scene_compact: points, box_frame or pixel_offset is null");
+    MPSR_REQUIRE(xyz && box && pixel && frame_offset && kept_per_box && visible_per_box,
+                 "scene_compact: an output is null");
+    MPSR_REQUIRE((images == nullptr) == (rgb == nullptr), "scene_compact: images and rgb go together (both or neither)");
+    const SceneLayout L = scene_layout(n_frames, total_pixels, n_boxes, points_per_box);
+    st = check_workspace("scene_compact", workspace, workspace_bytes, L);
+    if (st) return st;
+    char *ws = static_cast<char *>(workspace);
+    const unsigned long long *keys = reinterpret_cast<const unsigned long long *>(ws + L.keys);
+    const int *pix = reinterpret_cast<const int *>(ws + L.pix);
+    long long *box_offset = reinterpret_cast<long long *>(ws + L.box_offset);
+    hipStream_t s = mpsr::as_stream(stream);
+    hipLaunchKernelGGL(count_kernel, dim3(n_boxes), dim3(kThreads), 0, s, keys, pix, box_frame, pixel_offset,
+                       points_per_box, kept_per_box, visible_per_box);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kThreads), 0, s, visible_only ? visible_per_box : kept_per_box,
+                       n_boxes, box_frame, n_frames, box_offset, frame_offset);
+    hipLaunchKernelGGL(write_kernel, dim3(n_boxes), dim3(kThreads), 0, s, xyz_global, keys, pix, box_frame,
+                       pixel_offset, images, box_offset, points_per_box, visible_only, xyz, rgb, box, pixel);
+    MPSR_CHECK_LAUNCH("scene_compact");
+    return MPSR_OK;
+}

@@ -1,0 +1,110 @@
+"""Runs one checkpoint over a split of MSCNN 2-D detections in 'test' mode and writes what it predicts: the KITTI label
+files and, per frame, the reconstructed scene (the reference's experiments/run_inference.py; the scenes are
+core/scene_reconstruction.py).
+
+    python -m monopsr_amd.experiments.run_inference CONFIG CHECKPOINT --mscnn-dir DIR --output-dir DIR
+        [--data-split val|test] [--width-div N] [--no-scenes] [--min-score S] [--visible-only]
+
+Under --output-dir: kitti_predictions_3d/<split>/<threshold>/<step>/data/<name>.txt as run_evaluation writes them, and
+scenes/<split>/<step>/points/<name>.ply, depth/<name>.png, instances/<name>.png.  One network pass serves both: the
+scenes are written from the Evaluator's chunks through its chunk_hook.  Split 'test' reads <dataset_dir>/testing and has
+no labels; any other split reads the config's data_split_dir, and the AP report is printed when it has a label_2.
+"""
+import argparse
+import os
+import sys
+
+from monopsr_amd.core import evaluator, scene_reconstruction
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description='KITTI label files and reconstructed scenes of one checkpoint on a split')
+    ap.add_argument('config', help='experiment config (yaml)')
+    ap.add_argument('checkpoint', help='checkpoint prefix, directory or .npz')
+    ap.add_argument('--mscnn-dir', required=True, help='MSCNN detections in KITTI label format, one file per frame')
+    ap.add_argument('--output-dir', required=True, help='where the label files and the scenes are written')
+    ap.add_argument('--data-split', default='val', help="'test' reads <dataset_dir>/testing and has no labels")
+    ap.add_argument('--width-div', type=int, default=1, help='channel divisor of the net the checkpoint was saved from')
+    ap.add_argument('--no-scenes', action='store_true', help='write the label files only')
+    ap.add_argument('--min-score', type=float, default=None,
+                    help='2-D detection score a box needs to enter the scene (default: the label files\' threshold)')
+    ap.add_argument('--visible-only', action='store_true',
+                    help='keep only the points that win their pixel (drop what another point hides)')
+    return ap
+
+
+def scene_dir(output_dir, data_split, global_step):
+    return os.path.join(output_dir, 'scenes', data_split, str(global_step))
+
+
+class SceneWriter(object):
+    """An Evaluator chunk_hook: reconstruct_frames of every chunk, save_frame of every frame.  `base` is the directory
+    that takes points/, depth/ and instances/; names collects the frames written."""
+
+    def __init__(self, model, base, min_score=None, visible_only=False):
+        self.model, self.base, self.min_score, self.visible_only = model, base, min_score, bool(visible_only)
+        self.names = []
+        self._dirs = None
+
+    def __call__(self, rows, samples, outs):
+        if self._dirs is None:
+            self._dirs = scene_reconstruction.scene_output_dirs(self.base)
+        scene = scene_reconstruction.reconstruct_frames(self.model, samples, outs, self.min_score, self.visible_only)
+        for f, s in enumerate(samples):
+            scene_reconstruction.save_frame(self._dirs, s['sample_name'], scene.frame(f))
+            self.names.append(s['sample_name'])
+
+    def finish(self, dataset):
+        """The frames of the split that keep no detection are no sample of the dataset: an empty scene for each, as the
+        Evaluator writes an empty label file for them."""
+        from monopsr_amd.datasets.kitti import depth_map_utils
+        if self._dirs is None:
+            self._dirs = scene_reconstruction.scene_output_dirs(self.base)
+        done = set(self.names)
+        for name in dataset.split_sample_names:
+            if name not in done:
+                shape = depth_map_utils.image_shape(os.path.join(dataset.rgb_image_dir, name + '.png'))
+                scene_reconstruction.save_empty_frame(self._dirs, name, shape)
+                self.names.append(name)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    from monopsr_amd.core import config_utils
+    from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
+    from monopsr_amd.datasets.kitti.kitti_dataset import KittiDataset
+    cfg = config_utils.parse_yaml_config(args.config)
+    dcfg = cfg.dataset_config
+    dcfg.data_split = args.data_split
+    dcfg.use_mscnn_detections = True
+    if args.data_split == 'test':
+        dcfg.data_split_dir = 'testing'
+        dcfg.has_kitti_labels = False
+    else:
+        split_dir = os.path.join(os.path.expanduser(dcfg.dataset_dir), getattr(dcfg, 'data_split_dir', 'training'))
+        dcfg.has_kitti_labels = os.path.isdir(os.path.join(split_dir, 'label_2'))
+    dataset = KittiDataset(dcfg, 'test', mscnn_label_dir=args.mscnn_dir)
+    model = MonoPSRModel(cfg.model_config, dcfg, None, 'test')
+    threshold = getattr(cfg.get('train_config'), 'kitti_score_threshold', 0.1)
+    ev = evaluator.Evaluator(model, dataset, score_threshold=threshold, predictions_base_dir=args.output_dir)
+    step = ev.restore_checkpoint(args.checkpoint, width_div=args.width_div)
+    writer = None
+    if not args.no_scenes:
+        writer = SceneWriter(model, scene_dir(args.output_dir, dataset.data_split, step),
+                             ev.score_threshold if args.min_score is None else args.min_score, args.visible_only)
+        ev.chunk_hook = writer
+    result = ev.run_once(step)
+    if writer is not None:
+        writer.finish(dataset)
+    if result['report'] is not None:
+        sys.stdout.write(result['report'])
+    sys.stdout.write('%d detections in %d of %d frames: %s\n' % (
+        result['num_detections'], result['num_frames_with_detections'], result['num_frames'],
+        result['kitti_predictions_dir']))
+    if writer is not None:
+        sys.stdout.write('%d scenes: %s\n' % (len(writer.names), writer.base))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
