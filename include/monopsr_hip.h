@@ -1039,6 +1039,39 @@ int mpsr_scene_compact(const float *xyz_global, const int *box_frame, const floa
                        float *rgb, int *box, int *pixel, long long *frame_offset, int *kept_per_box,
                        int *visible_per_box, mpsr_stream_t stream);
 
+/* ---- Scoring a reconstruction against ground truth (additive to ABI 13) ----
+ * Runs after mpsr_scene_project on the same stream and workspace (which holds the keys and the per-point pixel
+ * indices), independent of resolve and compact, in any order.  gt_depth / gt_instance: device tables of n_frames
+ * pointers to the frames' (h, w) float32 LiDAR depth maps and uint8 instance images (no alignment is asked of the
+ * images: the histogram pass peels to 16 bytes).  box_gt_id (n_boxes) int32: the value box b has in its frame's
+ * instance image; anything outside [0, 254] means "no ground truth for this box".  xyz_global is the array project
+ * took; it is checked and not read (a winner's z is its key's upper half).
+ * With f = box_frame[b], g = box_gt_id[b], a KEPT point and its pixel `at` as project stored them, a VISIBLE point its
+ * pixel's winner ((key & 0xffffffff) == b * points_per_box + p), counts (n_boxes, 6) int32, all exact:
+ *   0 kept       kept points (= kept_per_box of compact)
+ *   1 on_points  kept points with gt_instance[f][at] == g (0 when g is "none")
+ *   2 pred_px    visible points: the pixels the box wins (= visible_per_box)
+ *   3 inter_px   visible points with gt_instance[f][at] == g
+ *   4 gt_px      pixels of frame f whose instance value is g (0 when g is "none")
+ *   5 depth_n    the points of inter_px whose d = gt_depth[f][at] is finite and > 0
+ * sums (n_boxes, 3) fp64 over the depth_n points, e = (double)z - (double)d with z the point's float32 z: the sums of
+ * e, |e| and e * e (the square rounded before it is added).
+ * scratch: mpsr_scene_score_scratch_bytes(n_frames) bytes, the (n_frames, 256) int32 value counts of the instance
+ * images; the call zeroes it and fills it with integer atomics (LDS and global), whose result does not depend on
+ * order.  The per-box part is one launch of one workgroup per box: counts from wave ballots, the fp64 sums per thread
+ * in slice order, then a lane-ordered wave reduction, wave partials through LDS and a combine in wave order.  No
+ * floating-point atomics: two calls on the same inputs return the same bytes.
+ * Checked on the host before any launch: empty sizes (and total_pixels 0) are no-ops that return MPSR_OK and write
+ * nothing; negative sizes, null pointers with non-empty sizes, n_boxes * points_per_box >= 2^32 and a box_frame_host
+ * out of [0, n_frames) or decreasing are MPSR_ERR_INVALID_ARG; a workspace smaller than mpsr_scene_workspace_bytes or
+ * a scratch smaller than mpsr_scene_score_scratch_bytes is MPSR_ERR_WORKSPACE. */
+size_t mpsr_scene_score_scratch_bytes(int n_frames); /* 256 int32 per frame; 0 for n_frames <= 0 */
+int mpsr_scene_score(const float *xyz_global, const int *box_frame, const int *box_frame_host, const int *box_gt_id,
+                     const float *const *gt_depth, const unsigned char *const *gt_instance,
+                     const long long *pixel_offset, int n_frames, long long total_pixels, int n_boxes,
+                     int points_per_box, const void *workspace, size_t workspace_bytes, void *scratch,
+                     size_t scratch_bytes, int *counts, double *sums, mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

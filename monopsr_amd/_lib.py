@@ -228,6 +228,9 @@ SIGNATURES = {
     "mpsr_scene_resolve": (c_i, [c_f, ctypes.c_void_p, c_i, ctypes.c_longlong, c_i, c_i, c_f, c_sz, c_f, c_f, c_f]),
     "mpsr_scene_compact": (c_i, [c_f, c_f, c_f, c_f, c_i, ctypes.c_longlong, c_i, c_i, c_i, c_f, c_sz, c_f, c_f, c_f,
                                  c_f, c_f, c_f, c_f, c_f]),
+    "mpsr_scene_score_scratch_bytes": (c_sz, [c_i]),
+    "mpsr_scene_score": (c_i, [c_f, c_f, ctypes.c_void_p, c_f, c_f, c_f, c_f, c_i, ctypes.c_longlong, c_i, c_i, c_f,
+                               c_sz, c_f, c_sz, c_f, c_f, c_f]),
 }
 
 

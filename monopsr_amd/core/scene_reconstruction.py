@@ -14,6 +14,13 @@ The rendering is a z-buffer: the nearest point of a pixel wins, on equal float32
 LiDAR projection of depth_map_utils keeps the last duplicate of a pixel, as the reference does with a LiDAR cloud.)
 Colours are the image's value at the point's pixel (nearest pixel, exact).  Everything stays on the device; one copy of
 n_frames + 1 offsets to the host per call tells where each frame's points are.
+
+With ground truth (the LiDAR depth maps, the instance images and each box's instance id: what
+KittiDataset.frame_ground_truth returns) the same call also scores the reconstruction per box (mpsr_scene_score, DESIGN.md
+section 7.8): SceneResult.scores, a SceneScores of six exact counts and three fp64 sums per box, and its table() of
+SCENE_METRIC_NAMES.  One limit: a box has 48 x 48 points, so a box larger than 48 x 48 pixels cannot fill its mask, and
+scene_mask_iou is bounded by pred_px / gt_px for near objects.  That is why the two precisions and the raw counts are
+reported next to it.
 """
 import ctypes
 import os
@@ -23,6 +30,12 @@ import numpy as np
 from monopsr_amd import _lib
 
 MAX_BOXES = 255  # per frame: 255 of an instance image is the background
+
+# the columns of SceneScores.counts and .sums (mpsr_scene_score) and of SceneScores.table()
+SCENE_COUNT_NAMES = ('kept', 'on_points', 'pred_px', 'inter_px', 'gt_px', 'depth_n')
+SCENE_SUM_NAMES = ('sum_e', 'sum_abs_e', 'sum_e2')
+SCENE_METRIC_NAMES = ('scene_mask_iou', 'scene_mask_precision', 'scene_point_precision', 'scene_depth_bias',
+                      'scene_depth_mae', 'scene_depth_rmse')
 
 _PLY_DTYPE = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('green', 'u1'), ('blue', 'u1'),
                        ('box', '<i4')])
@@ -48,15 +61,52 @@ class FrameScene(object):
             setattr(self, k, kw[k])
 
 
+def score_table(counts, sums, box_gt_id):
+    """The (B, 6) float32 per-box metric table in SCENE_METRIC_NAMES order from counts (B, 6) int, sums (B, 3) float64
+    and box_gt_id (B,) int, tensors of one device: computed in fp64, rounded once.
+        scene_mask_iou         inter_px / (pred_px + gt_px - inter_px): the IoU of the mask the box renders and the true
+                               one; NaN when the box has no ground truth (id outside [0, 254]) or the union is 0
+        scene_mask_precision   inter_px / pred_px; NaN when pred_px == 0
+        scene_point_precision  on_points / kept; NaN when kept == 0
+        scene_depth_bias       sum e / depth_n          (e = z - LiDAR depth over the depth_n points)
+        scene_depth_mae        sum |e| / depth_n
+        scene_depth_rmse       sqrt(sum e^2 / depth_n); all three NaN when depth_n == 0"""
+    import torch
+    c = counts.to(torch.float64)
+    kept, on_points, pred_px, inter_px, gt_px, depth_n = (c[:, k] for k in range(6))
+    has_gt = (box_gt_id >= 0) & (box_gt_id <= 254)
+    nan = torch.full_like(kept, float('nan'))
+    ratio = lambda num, den, ok: torch.where(ok & (den > 0), num / torch.where(den > 0, den, torch.ones_like(den)), nan)
+    every = torch.ones_like(has_gt)
+    return torch.stack([ratio(inter_px, pred_px + gt_px - inter_px, has_gt), ratio(inter_px, pred_px, every),
+                        ratio(on_points, kept, every), ratio(sums[:, 0], depth_n, every),
+                        ratio(sums[:, 1], depth_n, every), torch.sqrt(ratio(sums[:, 2], depth_n, every))],
+                       1).to(torch.float32)
+
+
+class SceneScores(object):
+    """A reconstruction against its ground truth, per box, device tensors: counts (B, 6) int32 (SCENE_COUNT_NAMES),
+    sums (B, 3) float64 (SCENE_SUM_NAMES), box_gt_id (B,) int32 as given.  table(): score_table of them."""
+    __slots__ = ('counts', 'sums', 'box_gt_id')
+
+    def __init__(self, counts, sums, box_gt_id):
+        self.counts, self.sums, self.box_gt_id = counts, sums, box_gt_id
+
+    def table(self):
+        return score_table(self.counts, self.sums, self.box_gt_id)
+
+
 class SceneResult(object):
     """What project_instance_points returns, device tensors: xyz (M,3) float32, rgb (M,3) float32 or None, box (M,)
     int32 (index into the call's boxes), pixel (M,) int32, frame_offset (F+1,) int64 (frame f owns rows
     frame_offset[f] .. frame_offset[f+1]), depth_maps / instance_maps: lists of (H_f, W_f) float32 / uint8,
-    kept_per_box / visible_per_box (B,) int32.  frame_offset_host and box_frame_host are their host copies."""
+    kept_per_box / visible_per_box (B,) int32.  frame_offset_host and box_frame_host are their host copies.  scores: a
+    SceneScores when the call was given ground truth, else None."""
     __slots__ = ('xyz', 'rgb', 'box', 'pixel', 'frame_offset', 'depth_maps', 'instance_maps', 'kept_per_box',
-                 'visible_per_box', 'frame_offset_host', 'box_frame_host')
+                 'visible_per_box', 'frame_offset_host', 'box_frame_host', 'scores')
 
     def __init__(self, **kw):
+        kw.setdefault('scores', None)
         for k in self.__slots__:
             setattr(self, k, kw[k])
 
@@ -79,15 +129,49 @@ def _host_ints(v):
     return np.ascontiguousarray(np.asarray(v).astype(np.int32))
 
 
+def _ground_truth_tables(ground_truth, hw, nb, dev):
+    """-> (the F depth maps, the F instance images, box_gt_id (B,) int32 on the device), checked against the frames."""
+    import torch
+    nf = len(hw)
+    try:
+        depths, insts, ids = ground_truth['depth_maps'], ground_truth['instance_images'], ground_truth['box_gt_id']
+    except (KeyError, TypeError):
+        raise _lib.InvalidArgumentError("ground_truth must be a dict of 'depth_maps', 'instance_images' and 'box_gt_id'")
+    if len(depths) != nf or len(insts) != nf:
+        raise _lib.InvalidArgumentError('%d depth maps and %d instance images for %d frames'
+                                        % (len(depths), len(insts), nf))
+    out_d, out_i = [], []
+    for f in range(nf):
+        shape = (int(hw[f, 0]), int(hw[f, 1]))
+        for what, t, dtype in (('depth map', depths[f], torch.float32), ('instance image', insts[f], torch.uint8)):
+            if not torch.is_tensor(t) or not t.is_cuda or tuple(t.shape) != shape or t.dtype != dtype:
+                raise _lib.InvalidArgumentError('ground truth: %s %d must be a (%d, %d) %s CUDA tensor'
+                                                % (what, f, shape[0], shape[1], str(dtype).split('.')[-1]))
+        out_d.append(depths[f].detach().to(dev).contiguous())  # (a view of a resident stack is taken as it is)
+        out_i.append(insts[f].detach().to(dev).contiguous())
+    if not torch.is_tensor(ids):
+        ids = np.asarray(ids)
+        ids = torch.from_numpy(np.ascontiguousarray(ids.astype(np.int64) if ids.size == 0 or ids.dtype.kind in 'iu'
+                                                    else ids.astype(np.float64)))
+    ids = ids.to(dev)
+    if ids.dim() != 1 or ids.numel() != nb or ids.is_floating_point():
+        raise _lib.InvalidArgumentError('ground truth: box_gt_id must be %d ints, got %s %s'
+                                        % (nb, tuple(ids.shape), ids.dtype))
+    return out_d, out_i, ids.clamp(-1, 255).to(torch.int32).contiguous()
+
+
 def project_instance_points(xyz_global, box_frame, cam_p, frame_shapes, images=None, valid_mask=None, keep=None,
-                            visible_only=False):
-    """The direct wrapper of mpsr_scene_project / _resolve / _compact.
+                            visible_only=False, ground_truth=None):
+    """The direct wrapper of mpsr_scene_project / _resolve / _compact (and, with ground_truth, mpsr_scene_score).
 
     xyz_global (B,P,3) or (B,H,W,3) float32 CUDA tensor in the camera frame; box_frame (B,) the frame of each box,
     never decreasing (a host sequence: a tensor is copied to the host); cam_p (F,3,4), a tensor, an array or a list of
     (3,4), used in float64; frame_shapes F x (h, w[, ...]); images None or F CUDA tensors (h_f, w_f, 3) float32;
     valid_mask None or (B,P) / (B,H,W[,1]) float32, a point counts where it is > 0; keep None or (B,) (bool or int): a
-    box with 0 takes no part.  visible_only: the cloud holds each pixel's winner only.  -> SceneResult."""
+    box with 0 takes no part.  visible_only: the cloud holds each pixel's winner only.  ground_truth: None or a dict of
+    depth_maps (F CUDA tensors (h_f, w_f) float32), instance_images (F CUDA tensors (h_f, w_f) uint8) and box_gt_id
+    ((B,) ints, a tensor or a sequence: the value of each box in its frame's instance image, outside [0, 254] for a box
+    without ground truth); with it the result carries .scores (SceneScores).  -> SceneResult."""
     import torch
     if not torch.is_tensor(xyz_global) or not xyz_global.is_cuda:
         raise _lib.MpsrError('expected xyz_global on the GPU; monopsr_amd has no CPU path')
@@ -147,6 +231,10 @@ def project_instance_points(xyz_global, box_frame, cam_p, frame_shapes, images=N
                     raise _lib.InvalidArgumentError('image %d must be a (%d, %d, 3) tensor' % (f, hw[f, 0], hw[f, 1]))
                 imgs.append(im.detach().to(dev).to(f32).contiguous())  # (kept alive until the launches are queued)
             table = torch.from_numpy(np.asarray([_lib.ptr(im) for im in imgs] or [0], np.uint64).view(np.int64)).to(dev)
+        scores = gt = None
+        if ground_truth is not None:
+            gt = _ground_truth_tables(ground_truth, hw, nb, dev)
+            scores = SceneScores(_empty((nb, 6), i32, dev), _empty((nb, 3), torch.float64, dev), gt[2])
         cap = nb * npts
         depth = _empty((total,), f32, dev)
         inst = _empty((total,), torch.uint8, dev)
@@ -163,6 +251,9 @@ def project_instance_points(xyz_global, box_frame, cam_p, frame_shapes, images=N
             visible.zero_()
             frame_offset.zero_()
             fo_host = np.zeros(nf + 1, np.int64)
+            if scores is not None:  # (no point: no count; gt_px is not counted either)
+                scores.counts.zero_()
+                scores.sums.zero_()
         else:
             bf_d, hw_d, offs_d = torch.from_numpy(bf).to(dev), torch.from_numpy(hw).to(dev), torch.from_numpy(offs).to(dev)
             ws = _empty((lib.mpsr_scene_workspace_bytes(nf, total, nb, npts),), torch.uint8, dev)
@@ -177,20 +268,30 @@ def project_instance_points(xyz_global, box_frame, cam_p, frame_shapes, images=N
                 _lib.ptr(xyz_in), _lib.ptr(bf_d), _lib.ptr(table), _lib.ptr(offs_d), nf, total, nb, npts,
                 int(bool(visible_only)), _lib.ptr(ws), ws.numel(), _lib.ptr(xyz), _lib.ptr(rgb), _lib.ptr(box),
                 _lib.ptr(pixel), _lib.ptr(frame_offset), _lib.ptr(kept), _lib.ptr(visible), stream))
+            if scores is not None:
+                tables = torch.from_numpy(np.asarray([[_lib.ptr(t) for t in gt[0]], [_lib.ptr(t) for t in gt[1]]],
+                                                     np.uint64).view(np.int64)).to(dev)
+                scratch = _empty((lib.mpsr_scene_score_scratch_bytes(nf),), torch.uint8, dev)
+                _lib.check(lib.mpsr_scene_score(
+                    _lib.ptr(xyz_in), _lib.ptr(bf_d), host(bf), _lib.ptr(scores.box_gt_id), _lib.ptr(tables[0]),
+                    _lib.ptr(tables[1]), _lib.ptr(offs_d), nf, total, nb, npts, _lib.ptr(ws), ws.numel(),
+                    _lib.ptr(scratch), scratch.numel(), _lib.ptr(scores.counts), _lib.ptr(scores.sums), stream))
             fo_host = frame_offset.cpu().numpy()  # the one copy to the host: M and where each frame's points are
         m = int(fo_host[-1])
     return SceneResult(
         xyz=xyz[:m], rgb=None if rgb is None else rgb[:m], box=box[:m], pixel=pixel[:m], frame_offset=frame_offset,
         depth_maps=[depth[int(offs[f]):int(offs[f + 1])].view(int(hw[f, 0]), int(hw[f, 1])) for f in range(nf)],
         instance_maps=[inst[int(offs[f]):int(offs[f + 1])].view(int(hw[f, 0]), int(hw[f, 1])) for f in range(nf)],
-        kept_per_box=kept, visible_per_box=visible, frame_offset_host=fo_host, box_frame_host=bf)
+        kept_per_box=kept, visible_per_box=visible, frame_offset_host=fo_host, box_frame_host=bf, scores=scores)
 
 
-def reconstruct_frames(model, samples, outs, min_score=None, visible_only=False):
+def reconstruct_frames(model, samples, outs, min_score=None, visible_only=False, ground_truth=None):
     """The scene of a chunk: `samples` as dataset.get_sample_dict returns them, `outs` as model.build_batch returns
     them.  The first num_objs rows of each frame: KEY_INST_XYZ_MAP_LOCAL placed with KEY_VIEW_ANG and KEY_CENTROIDS
     (instance_utils.tf_inst_xyz_map_local_to_global), masked by gt_valid_mask_maps where the sample carries them, kept
-    where label_scores >= min_score (None: all), coloured from rgb_image, projected with cam_p.  -> SceneResult."""
+    where label_scores >= min_score (None: all), coloured from rgb_image, projected with cam_p.  ground_truth: as
+    project_instance_points takes it (box_gt_id over the frames' first num_objs rows, frame after frame).
+    -> SceneResult."""
     import torch
     from monopsr_amd.core import constants
     from monopsr_amd.datasets.kitti import instance_utils
@@ -216,7 +317,7 @@ def reconstruct_frames(model, samples, outs, min_score=None, visible_only=False)
         box_frame = np.repeat(np.arange(len(samples)), counts)
         return project_instance_points(glob, box_frame, cam_p, [tuple(s['rgb_image'].shape) for s in samples],
                                        images=[s['rgb_image'] for s in samples], valid_mask=mask, keep=keep,
-                                       visible_only=visible_only)
+                                       visible_only=visible_only, ground_truth=ground_truth)
 
 
 # ---- files

@@ -15,6 +15,15 @@
 //   exclusive scan over the boxes, and a write pass of one workgroup per box that places a point at its box's offset
 //   plus its rank within the box: __ballot / __popcll prefix counts within a wave, wave offsets through LDS, a running
 //   base from one 256-point slice of the box to the next.  No atomics: the write position does not depend on scheduling.
+// mpsr_scene_score: the reconstruction against ground truth, after project, independent of
+//   resolve and compact.  hist_kernel counts the values of every ground-truth instance image into a (n_frames, 256)
+//   int32 table: a 256-bin histogram per workgroup in LDS, flushed with integer atomics, whose result does not depend
+//   on order.  The frame pointers are NOT aligned (frame k of a stack of 5 x 7 images starts at byte 35 k): the pass
+//   PEELS to alignment -- the bytes in front of the first 16-byte boundary and behind the last one are read one by
+//   one, the body in 16-byte loads.  score_kernel, one workgroup per box, walks the box's points in slices of 256 as
+//   count_kernel does: the six counts from ballots and popcounts, the three fp64 sums per thread in slice order, then
+//   a lane-ordered wave reduction, wave partials through LDS and a combine in wave order.  No floating-point atomics:
+//   two calls return the same bytes.
 #include "common.h"
 
 #include <algorithm>
@@ -235,6 +244,119 @@ __global__ void __launch_bounds__(kThreads) write_kernel(const float *__restrict
     }
 }
 
+// value counts of frame blockIdx.y's ground-truth instance image, added into hist[frame][256] (zeroed by the caller).
+// 255, the background, is most of an image: it is counted in a register, not in LDS.
+__global__ void __launch_bounds__(kThreads) hist_kernel(const unsigned char *const *__restrict__ gt_instance,
+                                                        const long long *__restrict__ pixel_offset,
+                                                        int *__restrict__ hist)
+{
+    __shared__ int bins[256];
+    const int f = blockIdx.y;
+    const unsigned char *img = gt_instance[f];
+    const long long n = pixel_offset[f + 1] - pixel_offset[f];
+    bins[threadIdx.x] = 0;
+    __syncthreads();
+    int background = 0;
+    auto count = [&](unsigned v) {
+        if (v == 255u)
+            ++background;
+        else
+            atomicAdd(&bins[v], 1);
+    };
+    // [0, head): bytes in front of the first 16-byte boundary; [head, head + 16 body): aligned vectors; the rest: bytes
+    const long long to_boundary = (long long)((16 - ((unsigned long long)img & 15)) & 15);
+    const long long head = to_boundary < n ? to_boundary : n;
+    const long long body = (n - head) / 16;
+    const uint4 *vec = reinterpret_cast<const uint4 *>(img + head);
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < body; i += (long long)gridDim.x * kThreads) {
+        const uint4 q = vec[i];
+        const unsigned w[4] = {q.x, q.y, q.z, q.w};
+        for (int k = 0; k < 4; ++k)
+            for (int s = 0; s < 32; s += 8) count((w[k] >> s) & 255u);
+    }
+    if (blockIdx.x == 0) {
+        const long long tail = head + 16 * body;  // n - tail < 16, head < 16: one thread each
+        if (threadIdx.x < head) count(img[threadIdx.x]);
+        if (tail + threadIdx.x < n) count(img[tail + threadIdx.x]);
+    }
+    for (int o = 32; o > 0; o >>= 1) background += __shfl_down(background, o);
+    if ((threadIdx.x & 63) == 0 && background) atomicAdd(&bins[255], background);
+    __syncthreads();
+    if (bins[threadIdx.x]) atomicAdd(hist + 256 * (long long)f + threadIdx.x, bins[threadIdx.x]);
+}
+
+// one workgroup per box: counts[b][6] = kept, on_points, pred_px, inter_px, gt_px, depth_n and sums[b][3] = the sums of
+// e, |e| and e * e over the depth_n points, e = (double)z - (double)gt depth
+__global__ void __launch_bounds__(kThreads) score_kernel(const unsigned long long *__restrict__ keys,
+                                                         const int *__restrict__ pix,
+                                                         const int *__restrict__ box_frame,
+                                                         const int *__restrict__ box_gt_id,
+                                                         const float *const *__restrict__ gt_depth,
+                                                         const unsigned char *const *__restrict__ gt_instance,
+                                                         const long long *__restrict__ pixel_offset,
+                                                         const int *__restrict__ hist, int points_per_box,
+                                                         int *__restrict__ counts, double *__restrict__ sums)
+{
+    __shared__ int part[5][kWaves];
+    __shared__ double dpart[3][kWaves];
+    const int b = blockIdx.x, f = box_frame[b], g = box_gt_id[b];
+    const bool has_gt = g >= 0 && g <= 254;
+    const unsigned long long *fkeys = keys + pixel_offset[f];
+    const unsigned char *inst = gt_instance[f];
+    const float *depth = gt_depth[f];
+    const long long i0 = (long long)b * points_per_box;
+    int n[5] = {0, 0, 0, 0, 0};          // per wave: every lane holds its wave's counts
+    double s[3] = {0.0, 0.0, 0.0};       // per thread, in slice order
+    for (int p0 = 0; p0 < points_per_box; p0 += kThreads) {
+        const int p = p0 + threadIdx.x;
+        const int at = p < points_per_box ? pix[i0 + p] : -1;
+        const bool kept = at >= 0;
+        const bool on = kept && has_gt && (int)inst[at] == g;
+        const unsigned long long key = kept ? fkeys[at] : kEmptyKey;
+        const bool visible = kept && (unsigned)key == (unsigned)(i0 + p);
+        const bool inter = visible && on;
+        bool measured = false;
+        if (inter) {
+            const float d = depth[at];
+            if (isfinite(d) && d > 0.0f) {
+                measured = true;
+                const double e = (double)__uint_as_float((unsigned)(key >> 32)) - (double)d;
+                s[0] += e;
+                s[1] += fabs(e);
+                s[2] += e * e;
+            }
+        }
+        n[0] += __popcll(__ballot(kept));
+        n[1] += __popcll(__ballot(on));
+        n[2] += __popcll(__ballot(visible));
+        n[3] += __popcll(__ballot(inter));
+        n[4] += __popcll(__ballot(measured));
+    }
+    for (int k = 0; k < 3; ++k)
+        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_down(s[k], o);  // lane l += lane l + o: a fixed tree
+    if ((threadIdx.x & 63) == 0) {
+        for (int k = 0; k < 5; ++k) part[k][threadIdx.x >> 6] = n[k];
+        for (int k = 0; k < 3; ++k) dpart[k][threadIdx.x >> 6] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c[5] = {0, 0, 0, 0, 0};
+        double t[3] = {0.0, 0.0, 0.0};
+        for (int v = 0; v < kWaves; ++v) {  // in wave order
+            for (int k = 0; k < 5; ++k) c[k] += part[k][v];
+            for (int k = 0; k < 3; ++k) t[k] += dpart[k][v];
+        }
+        int *out = counts + 6 * (long long)b;
+        out[0] = c[0];
+        out[1] = c[1];
+        out[2] = c[2];
+        out[3] = c[3];
+        out[4] = has_gt ? hist[256 * (long long)f + g] : 0;
+        out[5] = c[4];
+        for (int k = 0; k < 3; ++k) sums[3 * (long long)b + k] = t[k];
+    }
+}
+
 // workspace: [keys: one uint64 per pixel] [pix: one int per point] [frame_box: n_frames + 1 ints]
 // [box_offset: n_boxes + 1 int64]
 struct SceneLayout {
@@ -402,5 +524,53 @@ extern "C" int mpsr_scene_compact(const float *xyz_global, const int *box_frame,
     hipLaunchKernelGGL(write_kernel, dim3(n_boxes), dim3(kThreads), 0, s, xyz_global, keys, pix, box_frame,
                        pixel_offset, images, box_offset, points_per_box, visible_only, xyz, rgb, box, pixel);
     MPSR_CHECK_LAUNCH("scene_compact");
+    return MPSR_OK;
+}
+
+extern "C" size_t mpsr_scene_score_scratch_bytes(int n_frames)
+{
+    return n_frames <= 0 ? 0 : (size_t)n_frames * 256 * sizeof(int);
+}
+
+extern "C" int mpsr_scene_score(const float *xyz_global, const int *box_frame, const int *box_frame_host,
+                                const int *box_gt_id, const float *const *gt_depth,
+                                const unsigned char *const *gt_instance, const long long *pixel_offset, int n_frames,
+                                long long total_pixels, int n_boxes, int points_per_box, const void *workspace,
+                                size_t workspace_bytes, void *scratch, size_t scratch_bytes, int *counts, double *sums,
+                                mpsr_stream_t stream)
+{
+    bool empty;
+    int st = check_sizes("scene_score", n_frames, total_pixels, n_boxes, points_per_box, &empty);
+    if (st) return st;
+    if (empty || total_pixels == 0) return MPSR_OK;
+    MPSR_REQUIRE(xyz_global && box_frame && box_frame_host && box_gt_id && pixel_offset,
+                 "scene_score: points, box_frame, box_gt_id or pixel_offset is null");
+    MPSR_REQUIRE(gt_depth && gt_instance, "scene_score: a ground-truth table is null");
+    MPSR_REQUIRE(counts && sums, "scene_score: an output is null");
+    st = check_box_frames("scene_score", box_frame_host, n_boxes, n_frames, 0);
+    if (st) return st;
+    const SceneLayout L = scene_layout(n_frames, total_pixels, n_boxes, points_per_box);
+    st = check_workspace("scene_score", workspace, workspace_bytes, L);
+    if (st) return st;
+    const size_t need = mpsr_scene_score_scratch_bytes(n_frames);
+    if (!scratch || scratch_bytes < need)
+        return mpsr::fail(MPSR_ERR_WORKSPACE, "scene_score: scratch %zu bytes < %zu", scratch_bytes, need);
+    const char *ws = static_cast<const char *>(workspace);
+    const unsigned long long *keys = reinterpret_cast<const unsigned long long *>(ws + L.keys);
+    const int *pix = reinterpret_cast<const int *>(ws + L.pix);
+    int *hist = static_cast<int *>(scratch);
+    hipStream_t s = mpsr::as_stream(stream);
+    MPSR_CHECK_HIP(hipMemsetAsync(hist, 0, need, s));
+    // workgroups per frame: one per 64 KiB of an average frame (a frame of any size is walked with the grid's stride)
+    const long long per_frame = (total_pixels + n_frames - 1) / n_frames;
+    const unsigned gx = (unsigned)std::min<long long>(std::max<long long>((per_frame + 65535) / 65536, 1), 64);
+    for (int f0 = 0; f0 < n_frames; f0 += 65535) {  // (gridDim.y holds 65535)
+        const int nf = std::min(n_frames - f0, 65535);
+        hipLaunchKernelGGL(hist_kernel, dim3(gx, nf), dim3(kThreads), 0, s, gt_instance + f0, pixel_offset + f0,
+                           hist + 256 * (size_t)f0);
+    }
+    hipLaunchKernelGGL(score_kernel, dim3(n_boxes), dim3(kThreads), 0, s, keys, pix, box_frame, box_gt_id, gt_depth,
+                       gt_instance, pixel_offset, hist, points_per_box, counts, sums);
+    MPSR_CHECK_LAUNCH("scene_score");
     return MPSR_OK;
 }

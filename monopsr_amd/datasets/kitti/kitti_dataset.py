@@ -586,6 +586,34 @@ class KittiDataset:
                                             '1 frame, 2 instance id, 4 not finite, 8 empty or outside the image)'
                                             % (count, flags))
 
+    # ---- ground truth of whole frames
+
+    def _label_instance_ids(self, label_row):
+        """The value each label row (int64, on the device) has in its frame's instance image: what the crop kernel is
+        given for a slot (_build) and what a reconstruction is scored against (frame_ground_truth)."""
+        return self._instance_id.index_select(0, label_row)
+
+    def frame_ground_truth(self, rows):
+        """The ground truth of whole frames, for rows of the frame tables (indices into sample_names: the `rows` an
+        Evaluator chunk hook receives).  -> one dict per frame: depth_map (h, w) float32 and instance_image (h, w)
+        uint8, views of the resident stacks (no copy), and instance_ids (num_objs,) int32 on the device: the value of
+        the frame's k-th object in instance_image, i.e. the id _build hands to the crop kernel for the frame's slot k
+        (k < num_objs: the slots that are not oversampled).  'test' mode has no ground truth: ValueError."""
+        if self.is_test:
+            raise ValueError("frame_ground_truth: a 'test'-mode dataset reads no depth map or instance image")
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        if len(rows) and (rows.min() < 0 or rows.max() >= self.num_samples):
+            raise IndexError('frame index out of range [0, %d)' % self.num_samples)
+        starts = np.concatenate([[0], np.cumsum(self._num_objs_host)]).astype(np.int64)
+        out = []
+        with torch.cuda.device(self.device):
+            for r in rows:
+                g, local = self._groups[self._group_host[r]], int(self._local_host[r])
+                label_row = torch.arange(int(starts[r]), int(starts[r + 1]), dtype=torch.int64, device=self.device)
+                out.append(dict(depth_map=g.depth[local], instance_image=g.inst[local],
+                                instance_ids=self._label_instance_ids(label_row)))
+        return out
+
     # ---- one batch
 
     def _build(self, frames, epoch):
@@ -629,7 +657,7 @@ class KittiDataset:
                 _lib.ptr(flag), _lib.ptr(boxes_xyxy), _lib.ptr(slot_hw), _lib.ptr(slot_p), _lib.ptr(slot_split),
                 _lib.ptr(slot_local), stream))
             rows = {k: t.index_select(0, label_row) for k, t in self._rows.items()}
-            instance_id = self._instance_id.index_select(0, label_row)
+            instance_id = self._label_instance_ids(label_row)
             if self.jitter_mode:
                 trials = torch.empty(n, dtype=i32, device=dev)
                 out_xyxy = torch.empty((n, 4), dtype=torch.float64, device=dev)

@@ -6,6 +6,9 @@ repeated_checkpoint_run).
 
 Under --predictions-dir: kitti_predictions_3d/ (the label files), metrics/<split>/metrics_{avg,std,avg_abs,std_abs}_<split>.csv,
 kitti_reports/<split>/<step>_<iou>.txt and evaluated_<split>.txt, which a later run reads to skip what is done.
+With --scene-metrics every checkpoint's reconstructed scenes are also scored against the LiDAR depth maps and the
+instance images (mask IoU, precisions, depth error: DESIGN.md section 7.8): six more lines per checkpoint and
+metrics/<split>/scene_metrics_<split>.csv.
 """
 import argparse
 import sys
@@ -28,13 +31,19 @@ def build_parser():
                     help='stop after this many seconds without a new checkpoint (--repeat; default: never)')
     ap.add_argument('--width-div', type=int, default=1, help='channel divisor of the net the checkpoints were saved from')
     ap.add_argument('--low-iou', action='store_true', help='MIN_OVERLAP 0.5 / 0.25 / 0.25')
+    ap.add_argument('--scene-metrics', action='store_true',
+                    help='also score the reconstructed scenes against ground truth: mask IoU and depth error per box')
     return ap
 
 
 def format_result(result):
-    """The report of one checkpoint and a line of its four statistics per metric."""
+    """The report of one checkpoint and a line of its four statistics per metric (the scene metrics, where the result
+    has them, in their own order after the others)."""
     lines = [result['report'] or '']
     for name, st in sorted(result.get('metric_stats', {}).items()):
+        lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
+            name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
+    for name, st in result.get('scene_stats', {}).items():
         lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
             name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
     return ''.join(lines)
@@ -53,7 +62,8 @@ def main(argv=None):
     train_config = cfg.get('train_config')
     threshold = getattr(train_config, 'kitti_score_threshold', 0.1)
     ev = evaluator.Evaluator(model, dataset, score_threshold=threshold, predictions_base_dir=args.predictions_dir,
-                             iou='low' if args.low_iou else 'standard', metric_stats=True)
+                             iou='low' if args.low_iou else 'standard', metric_stats=True,
+                             scene_metrics=args.scene_metrics)
     if args.repeat:
         max_iterations = getattr(train_config, 'max_iterations', None)
         if max_iterations is None and args.max_idle is None:
