@@ -127,8 +127,9 @@ __device__ __forceinline__ double sqdist_d(float ax, float ay, float az, float b
 // budget is 1e-3; tests hold the culled loss to 2e-5 of the plain one).
 constexpr int kSortMax = 4096;    // points per cloud the in-LDS sort takes; larger clouds run without culling
 constexpr int kChunk = 32;        // staged opposite points per bounding box
-constexpr float kCullExp = -150.f;  // exp2 of anything below is +0 in fp32 (denormals kept or flushed)
-constexpr int kNeverCull = 0x100;  // flag bit (`skip` / `flags` kernel arguments): chunk tests always fail (mpsr_debug_set_emd_cull(2))
+// exp2 of anything below is +0 in fp32 (denormals kept or flushed).  The culling kernels take their cut-off as the argument
+// `cull_exp`: this, or -inf (sorted clouds, every chunk test failing: mpsr_debug_set_emd_cull(2), the tests' reference)
+constexpr float kCullExp = -150.f;
 
 __device__ __forceinline__ unsigned spread3(unsigned v)  // 5 bits -> every third bit
 {
@@ -273,6 +274,42 @@ __device__ __forceinline__ float box_gap2(const float *cb, const float wlo[3], c
     return g2;
 }
 
+// Bounding box of a wave's own points: every lane includes its live points, then reduce() leaves the wave's box in every
+// lane.  Empty (lo = +inf, hi = -inf) when no lane had a live point.
+struct WaveBox {
+    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    __device__ __forceinline__ void include(float x, float y, float z)
+    {
+        const bool ok = x == x && y == y && z == z;  // (a NaN point: box = everything)
+        lo[0] = ok ? fminf(lo[0], x) : -__builtin_inff(); hi[0] = ok ? fmaxf(hi[0], x) : __builtin_inff();
+        lo[1] = ok ? fminf(lo[1], y) : -__builtin_inff(); hi[1] = ok ? fmaxf(hi[1], y) : __builtin_inff();
+        lo[2] = ok ? fminf(lo[2], z) : -__builtin_inff(); hi[2] = ok ? fmaxf(hi[2], z) : __builtin_inff();
+    }
+    __device__ __forceinline__ void reduce()
+    {
+        // the reduced value is the same in every lane; read as such it lives in scalar registers (the culling passes sit
+        // at the VGPR edge of their occupancy: with the box in VGPRs the receiver pass loses a wave per SIMD)
+        auto uniform = [](float v) {
+            return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+        };
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            lo[d] = uniform(wave_min_f(lo[d]));
+            hi[d] = uniform(wave_max_f(hi[d]));
+        }
+    }
+};
+
+// Index of own point u of thread `tid` in the kThreads * kPT-point block of a pass that starts at `base`.  CULL: a wave's
+// own points are consecutive (wave w owns base + 128 w .. + 127), so that they have a small box; otherwise interleaved.
+template <bool CULL>
+__device__ __forceinline__ int own_index(int base, int tid, int u)
+{
+    // (u's term last: point u sits at a constant offset from point 0, which the loads then share an address with)
+    return CULL ? base + (tid >> 6) * (64 * kPT) + (tid & 63) + u * 64 : base + tid + u * kThreads;
+}
+
 // ---------------------------------------------------------------------------------------------------- state
 // Per cloud, in words of S: remL[n] remR[m] ratL[slots][n] ratR[slots][m]; slots = levels (ratios of every level
 // kept for the emit / loss kernels) or 1 (compact path).
@@ -297,16 +334,15 @@ struct State {
 // Own points = givers k.  MODE 0: sweep 1 of level `lev` only (the first launch); 1: sweep 3 of level lev-1 and sweep
 // 1 of level lev; 2: sweep 3 of level lev-1 only (the last launch).  grid (ceil(n / 512), b).
 // CULL (DEVICE only; the clouds are in Morton order: "spatial order" above): a wave's own points are 128 CONSECUTIVE
-// points, chunks of the staged tile farther from their box than the level's cut-off are skipped.
+// points, chunks of the staged tile farther from their box than the level's cut-off (`cull_exp`) are skipped.
+// `skip`: the exhausted-receiver mode (g_emd_skip below).
 template <bool HOST, int MODE, bool CULL = false>
 __global__ __launch_bounds__(kThreads) void emd_giver_kernel(int n, int m, const float *__restrict__ xyz1,
                                                             const float *__restrict__ xyz2, void *temp, int lev,
-                                                            int slots, size_t cstride, int skip)
+                                                            int slots, size_t cstride, int skip, float cull_exp)
 {
     using S = typename Sem<HOST>::S;
     static_assert(!(HOST && CULL), "culling is a DEVICE-semantics path");
-    const float cull_exp = (skip & kNeverCull) ? -__builtin_inff() : kCullExp;  // (test mode: sorted clouds, nothing skipped)
-    skip &= 0xff;
     constexpr bool kDo3 = MODE != 0, kDo1 = MODE != 2;
     __shared__ float4 tile[kTile];  // x, y, z, (DEVICE) weight of sweep 3
     __shared__ float cbox[CULL ? kTile / kChunk : 1][6];
@@ -325,34 +361,18 @@ __global__ __launch_bounds__(kThreads) void emd_giver_kernel(int n, int m, const
     const float lv_cur = kDo1 ? level_value<HOST>(lev) : 0.f, lv_prev = kDo3 ? level_value<HOST>(lev - 1) : 0.f;
 
     const int base = blockIdx.x * (kThreads * kPT);
-    // own point u of this thread (CULL: the wave's points are consecutive: wave w owns base + 128 w .. + 127)
-    auto own_index = [&](int u) __attribute__((always_inline)) {
-        return CULL ? base + (tid >> 6) * (64 * kPT) + u * 64 + (tid & 63) : base + u * kThreads + tid;
-    };
     float ox[kPT], oy[kPT], oz[kPT];
-    float wlo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float whi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    WaveBox wbox;
 #pragma unroll
     for (int u = 0; u < kPT; ++u) {
-        const int i = own_index(u);
+        const int i = own_index<CULL>(base, tid, u);
         const bool live = i < n;
         ox[u] = live ? p1[3 * i] : 0.f;
         oy[u] = live ? p1[3 * i + 1] : 0.f;
         oz[u] = live ? p1[3 * i + 2] : 0.f;
-        if (CULL && live) {
-            const bool ok = ox[u] == ox[u] && oy[u] == oy[u] && oz[u] == oz[u];  // (a NaN point: box = everything)
-            wlo[0] = ok ? fminf(wlo[0], ox[u]) : -__builtin_inff(); whi[0] = ok ? fmaxf(whi[0], ox[u]) : __builtin_inff();
-            wlo[1] = ok ? fminf(wlo[1], oy[u]) : -__builtin_inff(); whi[1] = ok ? fmaxf(whi[1], oy[u]) : __builtin_inff();
-            wlo[2] = ok ? fminf(wlo[2], oz[u]) : -__builtin_inff(); whi[2] = ok ? fmaxf(whi[2], oz[u]) : __builtin_inff();
-        }
+        if (CULL && live) wbox.include(ox[u], oy[u], oz[u]);
     }
-    if constexpr (CULL) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            wlo[d] = wave_min_f(wlo[d]);
-            whi[d] = wave_max_f(whi[d]);
-        }
-    }
+    if constexpr (CULL) wbox.reduce();
     S s1[kPT], s3[kPT];
 #pragma unroll
     for (int u = 0; u < kPT; ++u) {
@@ -459,7 +479,7 @@ __global__ __launch_bounds__(kThreads) void emd_giver_kernel(int n, int m, const
                 if constexpr (CULL) {
                     // the SMALLER level of the pass decides (the steeper one's term vanishes with it): c_small < 0.
                     // (never at the zero level, whose sweep-1 term does not depend on the distance)
-                    if (!kZero && c_small * box_gap2(cbox[c0 / kChunk], wlo, whi) < cull_exp) continue;  // wave-uniform
+                    if (!kZero && c_small * box_gap2(cbox[c0 / kChunk], wbox.lo, wbox.hi) < cull_exp) continue;  // wave-uniform
                     c1 = min(c0 + kChunk, cnt);
                 }
 #pragma unroll 4
@@ -504,7 +524,7 @@ __global__ __launch_bounds__(kThreads) void emd_giver_kernel(int n, int m, const
     }
 #pragma unroll
     for (int u = 0; u < kPT; ++u) {
-        const int i = own_index(u);
+        const int i = own_index<CULL>(base, tid, u);
         if (i >= n) continue;
         S rem = first ? multiL : (first3 ? multiL : st.remL[i]);
         if (kDo3) {
@@ -519,16 +539,15 @@ __global__ __launch_bounds__(kThreads) void emd_giver_kernel(int n, int m, const
 }
 
 // ---------------------------------------------------------------------------------------------------- receiver pass
-// Own points = receivers l: sweep 2 of level `lev`.  grid (ceil(m / 512), b).
+// Own points = receivers l: sweep 2 of level `lev`.  grid (ceil(m / 512), b).  `skip`, CULL and `cull_exp` as in the
+// giver pass.
 template <bool HOST, bool CULL = false>
 __global__ __launch_bounds__(kThreads) void emd_receiver_kernel(int n, int m, const float *__restrict__ xyz1,
                                                                const float *__restrict__ xyz2, void *temp, int lev,
-                                                               int slots, size_t cstride, int skip)
+                                                               int slots, size_t cstride, int skip, float cull_exp)
 {
     using S = typename Sem<HOST>::S;
     static_assert(!(HOST && CULL), "culling is a DEVICE-semantics path");
-    const float cull_exp = (skip & kNeverCull) ? -__builtin_inff() : kCullExp;  // (test mode: sorted clouds, nothing skipped)
-    skip &= 0xff;
     __shared__ float4 tile[kTile];
     __shared__ float cbox[CULL ? kTile / kChunk : 1][6];
     __shared__ S ws[HOST ? kTile : 1];
@@ -572,7 +591,7 @@ __global__ __launch_bounds__(kThreads) void emd_receiver_kernel(int n, int m, co
 #pragma unroll
         for (int u = 0; u < kPT; ++u) {
             // (CULL: a wave's own receivers are consecutive, as in the compacted form below)
-            const int i = CULL ? base + (tid >> 6) * (64 * kPT) + u * 64 + (tid & 63) : base + u * kThreads + tid;
+            const int i = own_index<CULL>(base, tid, u);
             oi[u] = i < m ? i : -1;
         }
     } else {
@@ -624,6 +643,7 @@ __global__ __launch_bounds__(kThreads) void emd_receiver_kernel(int n, int m, co
         }
     }
     float ox[kPT], oy[kPT], oz[kPT];
+    WaveBox wbox;
 #pragma unroll
     for (int u = 0; u < kPT; ++u) {
         const bool live = oi[u] >= 0;
@@ -631,24 +651,9 @@ __global__ __launch_bounds__(kThreads) void emd_receiver_kernel(int n, int m, co
         ox[u] = live ? p2[3 * i] : 0.f;
         oy[u] = live ? p2[3 * i + 1] : 0.f;
         oz[u] = live ? p2[3 * i + 2] : 0.f;
+        if (CULL && live) wbox.include(ox[u], oy[u], oz[u]);
     }
-    float wlo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float whi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    if constexpr (CULL) {
-#pragma unroll
-        for (int u = 0; u < kPT; ++u)
-            if (oi[u] >= 0) {
-                const bool ok = ox[u] == ox[u] && oy[u] == oy[u] && oz[u] == oz[u];  // (a NaN point: box = everything)
-                wlo[0] = ok ? fminf(wlo[0], ox[u]) : -__builtin_inff(); whi[0] = ok ? fmaxf(whi[0], ox[u]) : __builtin_inff();
-                wlo[1] = ok ? fminf(wlo[1], oy[u]) : -__builtin_inff(); whi[1] = ok ? fmaxf(whi[1], oy[u]) : __builtin_inff();
-                wlo[2] = ok ? fminf(wlo[2], oz[u]) : -__builtin_inff(); whi[2] = ok ? fmaxf(whi[2], oz[u]) : __builtin_inff();
-            }
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            wlo[d] = wave_min_f(wlo[d]);
-            whi[d] = wave_max_f(whi[d]);
-        }
-    }
+    if constexpr (CULL) wbox.reduce();
     S t_[kPT];
     f32x2 vx[kPV], vy[kPV], vz[kPV], acc[kPV];
 #pragma unroll
@@ -688,7 +693,7 @@ __global__ __launch_bounds__(kThreads) void emd_receiver_kernel(int n, int m, co
                 int c1 = o_end;
                 if constexpr (CULL) {
                     c1 = min((c0 / kChunk + 1) * kChunk, o_end);  // up to the end of c0's chunk
-                    if (c * box_gap2(cbox[c0 / kChunk], wlo, whi) < cull_exp) {  // wave-uniform; c < 0 (never the zero level)
+                    if (c * box_gap2(cbox[c0 / kChunk], wbox.lo, wbox.hi) < cull_exp) {  // wave-uniform; c < 0 (never the zero level)
                         c0 = c1;
                         continue;
                     }
@@ -898,13 +903,27 @@ __device__ __forceinline__ double wave_sum_d(double v)
 // and read three times.  grid (ceil(own / 256), b).
 constexpr int kLossTile = 256;
 
-template <bool HOST, int ROLE>
+// Last step of a ROLE-0 loss kernel (256 threads): the workgroup's partial cost, summed in double from every thread's
+// `csum`, goes as float32 into word blockIdx.x of the cloud's remL (S = the state's word type).
+template <typename S>
+__device__ __forceinline__ void store_partial_cost(double csum, double (&part)[4], S *remL, int tid)
+{
+    const double v = wave_sum_d(csum);
+    __syncthreads();
+    if ((tid & 63) == 0) part[tid >> 6] = v;
+    __syncthreads();
+    // (remL is dead once the passes are done: it now carries the workgroups' partial costs to emd_cost_finish_kernel)
+    if (tid == 0) remL[blockIdx.x] = (float)(part[0] + part[1] + part[2] + part[3]);
+}
+
+// HOST semantics only (the DEVICE semantics run emd_loss_pk_kernel below); one own point per thread.
+template <int ROLE>
 __global__ __launch_bounds__(256) void emd_loss_kernel(int n, int m, const float *__restrict__ xyz1,
                                                       const float *__restrict__ xyz2, void *temp,
                                                       float *__restrict__ cost, float *__restrict__ grad)
 {
-    using S = typename Sem<HOST>::S;
-    constexpr int L = Sem<HOST>::levels;
+    using S = Sem<true>::S;
+    constexpr int L = Sem<true>::levels;
     __shared__ float4 tp[kLossTile];
     __shared__ S tr[kLossTile][L + 1];
     __shared__ double part[4];
@@ -912,7 +931,7 @@ __global__ __launch_bounds__(256) void emd_loss_kernel(int n, int m, const float
     const int nown = ROLE == 0 ? n : m, nother = ROLE == 0 ? m : n;
     const float *own = (ROLE == 0 ? xyz1 : xyz2) + (size_t)cloud * nown * 3;
     const float *other = (ROLE == 0 ? xyz2 : xyz1) + (size_t)cloud * nother * 3;
-    const State<HOST> st(temp, cloud, n, m, L);
+    const State<true> st(temp, cloud, n, m, L);
     const S *ratOwn = ROLE == 0 ? st.ratL : st.ratR, *ratOther = ROLE == 0 ? st.ratR : st.ratL;
     const int i = blockIdx.x * 256 + tid;
     const bool live = i < nown;
@@ -935,25 +954,16 @@ __global__ __launch_bounds__(256) void emd_loss_kernel(int n, int m, const float
         for (int o = 0; o < cnt; ++o) {
             const float4 t = tp[o];
             // giver first, receiver second, whatever the role
-            const float mv = ROLE == 0 ? pair_match<HOST>(x, y, z, t.x, t.y, t.z, ro, tr[o])
-                                       : pair_match<HOST>(t.x, t.y, t.z, x, y, z, tr[o], ro);
+            const float mv = ROLE == 0 ? pair_match<true>(x, y, z, t.x, t.y, t.z, ro, tr[o])
+                                       : pair_match<true>(t.x, t.y, t.z, x, y, z, tr[o], ro);
             const float dx = x - t.x, dy = y - t.y, dz = z - t.z;  // own - other
             const float d2 = dx * dx + dy * dy + dz * dz;
-            if constexpr (HOST) {
-                // tf_approxmatch.cpp:85-140: unit vector by a division, distance floored at 1e-20
-                const float d = fmaxf(sqrtf(d2), 1e-20f);
-                gx += mv * (dx / d);
-                gy += mv * (dy / d);
-                gz += mv * (dz / d);
-                if (ROLE == 0) csum += (double)(sqrtf(d2) * mv);
-            } else {
-                // tf_approxmatch_g.cu:183-291: rsqrt of the squared distance floored at 1e-20
-                const float s = mv * rsqrtf(fmaxf(d2, 1e-20f));
-                gx += dx * s;
-                gy += dy * s;
-                gz += dz * s;
-                if (ROLE == 0) csum += sqrtf(d2) * mv;
-            }
+            // tf_approxmatch.cpp:85-140: unit vector by a division, distance floored at 1e-20
+            const float d = fmaxf(sqrtf(d2), 1e-20f);
+            gx += mv * (dx / d);
+            gy += mv * (dy / d);
+            gz += mv * (dz / d);
+            if (ROLE == 0) csum += (double)(sqrtf(d2) * mv);
         }
     }
     if (live && grad) {
@@ -962,14 +972,7 @@ __global__ __launch_bounds__(256) void emd_loss_kernel(int n, int m, const float
         g[1] = gy;
         g[2] = gz;
     }
-    if (ROLE == 0) {
-        double v = wave_sum_d((double)csum);
-        __syncthreads();
-        if ((tid & 63) == 0) part[tid >> 6] = v;
-        __syncthreads();
-        // (remL is dead once the passes are done: it now carries the workgroups' partial costs to emd_cost_finish_kernel)
-        if (tid == 0) st.remL[blockIdx.x] = (float)(part[0] + part[1] + part[2] + part[3]);
-    }
+    if (ROLE == 0) store_partial_cost(csum, part, st.remL, tid);
 }
 
 // cost[cloud] = the cloud's `parts` partial costs added in float32 in workgroup order, starting from 0: one thread per
@@ -989,7 +992,8 @@ __global__ __launch_bounds__(64) void emd_cost_finish_kernel(int b, int n, int m
 // DEVICE semantics, two own points per thread in the halves of 2-wide vectors: the ~45 full-rate instructions a pair
 // costs (distance, fourth powers, the ten level terms, gradient) issue as packed fp32, which leaves the five
 // transcendentals per pair (3 exp2, rsqrt; sqrt(d2) is taken as d2 * rsqrt) as the larger share.  Same terms in the
-// same order as pair_match<false> / emd_loss_kernel<false, ROLE>.  grid (ceil(own / 512), b).
+// same order as pair_match<false>; the gradient as tf_approxmatch_g.cu:183-291 (rsqrt of the squared distance floored at
+// 1e-20).  grid (ceil(own / 512), b).
 // CULL: the clouds are in Morton order ("spatial order" above), a wave's own points are 128 consecutive ones, and for a
 // chunk of the tile farther than 0.32 from the wave's box the three steepest levels (e[0..2] = exp(-16384 / -4096 /
 // -1024 d^2), one of the three exponentials and four of the twelve squarings) are exactly zero and are left out; perm =
@@ -998,10 +1002,10 @@ template <int ROLE, bool CULL = false>
 __global__ __launch_bounds__(256) void emd_loss_pk_kernel(int n, int m, const float *__restrict__ xyz1,
                                                          const float *__restrict__ xyz2, void *temp,
                                                          float *__restrict__ cost, float *__restrict__ grad,
-                                                         const int *__restrict__ perm, int flags)
+                                                         const int *__restrict__ perm, float cull_exp)
 {
     constexpr int L = Sem<false>::levels;
-    const float cull_exp = (flags & kNeverCull) ? -__builtin_inff() : kCullExp;  // (test mode: sorted clouds, nothing skipped)
+    static_assert(kThreads == 256 && kPT == 2, "own_index's block is this kernel's 512 points");
     __shared__ float4 tp[kLossTile];
     __shared__ float tr[kLossTile][L + 2];
     __shared__ float cbox[CULL ? kLossTile / kChunk : 1][6];
@@ -1012,29 +1016,16 @@ __global__ __launch_bounds__(256) void emd_loss_pk_kernel(int n, int m, const fl
     const float *other = (ROLE == 0 ? xyz2 : xyz1) + (size_t)cloud * nother * 3;
     const State<false> st(temp, cloud, n, m, L);
     const float *ratOwn = ROLE == 0 ? st.ratL : st.ratR, *ratOther = ROLE == 0 ? st.ratR : st.ratL;
-    const int i0 = CULL ? blockIdx.x * 512 + (tid >> 6) * 128 + (tid & 63) : blockIdx.x * 512 + tid;
-    const int i1 = CULL ? i0 + 64 : i0 + 256;
+    const int i0 = own_index<CULL>(blockIdx.x * 512, tid, 0), i1 = own_index<CULL>(blockIdx.x * 512, tid, 1);
     const bool live0 = i0 < nown, live1 = i1 < nown;
     const f32x2 vx = {live0 ? own[3 * i0] : 0.f, live1 ? own[3 * i1] : 0.f};
     const f32x2 vy = {live0 ? own[3 * i0 + 1] : 0.f, live1 ? own[3 * i1 + 1] : 0.f};
     const f32x2 vz = {live0 ? own[3 * i0 + 2] : 0.f, live1 ? own[3 * i1 + 2] : 0.f};
-    float wlo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float whi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    WaveBox wbox;
     if constexpr (CULL) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-            if (h == 0 ? live0 : live1) {
-                const float px = vx[h], py = vy[h], pz = vz[h];
-                const bool ok = px == px && py == py && pz == pz;  // (a NaN point: box = everything)
-                wlo[0] = ok ? fminf(wlo[0], px) : -__builtin_inff(); whi[0] = ok ? fmaxf(whi[0], px) : __builtin_inff();
-                wlo[1] = ok ? fminf(wlo[1], py) : -__builtin_inff(); whi[1] = ok ? fmaxf(whi[1], py) : __builtin_inff();
-                wlo[2] = ok ? fminf(wlo[2], pz) : -__builtin_inff(); whi[2] = ok ? fmaxf(whi[2], pz) : __builtin_inff();
-            }
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            wlo[d] = wave_min_f(wlo[d]);
-            whi[d] = wave_max_f(whi[d]);
-        }
+        if (live0) wbox.include(vx[0], vy[0], vz[0]);
+        if (live1) wbox.include(vx[1], vy[1], vz[1]);
+        wbox.reduce();
     }
     f32x2 ro[L];
 #pragma unroll
@@ -1101,7 +1092,7 @@ __global__ __launch_bounds__(256) void emd_loss_pk_kernel(int n, int m, const fl
         if constexpr (CULL) {
             for (int c0 = 0; c0 < cnt; c0 += kChunk) {
                 const int c1 = min(c0 + kChunk, cnt);
-                const float g2 = box_gap2(cbox[c0 / kChunk], wlo, whi);
+                const float g2 = box_gap2(cbox[c0 / kChunk], wbox.lo, wbox.hi);
                 if (!(g2 < __builtin_inff())) continue;  // an empty box on either side: nothing to pair
                 if ((-1024.f * kLog2e) * g2 < cull_exp) {  // wave-uniform
                     for (int o = c0; o < c1; ++o) pair(o, std::false_type{});
@@ -1127,14 +1118,7 @@ __global__ __launch_bounds__(256) void emd_loss_pk_kernel(int n, int m, const fl
             g[2] = gz[1];
         }
     }
-    if (ROLE == 0) {
-        double v = wave_sum_d((double)csum[0] + (double)csum[1]);
-        __syncthreads();
-        if ((tid & 63) == 0) part[tid >> 6] = v;
-        __syncthreads();
-        // (remL is dead once the passes are done: it now carries the workgroups' partial costs to emd_cost_finish_kernel)
-        if (tid == 0) st.remL[blockIdx.x] = (float)(part[0] + part[1] + part[2] + part[3]);
-    }
+    if (ROLE == 0) store_partial_cost((double)csum[0] + (double)csum[1], part, st.remL, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------- cost / grad of
@@ -1287,57 +1271,87 @@ size_t state_floats(int b, int n, int m, int levels, bool host)
     return (size_t)b * ((size_t)(n + m) * (1 + levels)) * (host ? 2 : 1);
 }
 
+// the culling kernels' cut-off argument
+float cull_exp_arg() { return g_emd_cull.load() == 2 ? -__builtin_inff() : kCullExp; }
+
+// One pass launch, in its chunk-culling form where `cull` is set (DEVICE semantics only); args = the kernel's.
+template <bool HOST, int MODE, typename... A>
+void launch_giver(bool cull, dim3 grid, hipStream_t s, A... args)
+{
+    if constexpr (!HOST) {
+        if (cull) {
+            hipLaunchKernelGGL((emd_giver_kernel<false, MODE, true>), grid, dim3(kThreads), 0, s, args...);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((emd_giver_kernel<HOST, MODE>), grid, dim3(kThreads), 0, s, args...);
+}
+template <bool HOST, typename... A>
+void launch_receiver(bool cull, dim3 grid, hipStream_t s, A... args)
+{
+    if constexpr (!HOST) {
+        if (cull) {
+            hipLaunchKernelGGL((emd_receiver_kernel<false, true>), grid, dim3(kThreads), 0, s, args...);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((emd_receiver_kernel<HOST>), grid, dim3(kThreads), 0, s, args...);
+}
+
+struct NothingBetween {
+    int operator()(int) const { return 0; }
+};
+
 // the 2L + 1 passes; `slots` = levels (ratios of every level kept) or 1; `between` runs after the receiver pass of
 // each level (the compact path accumulates match there)
 // cull_levels > 0 (DEVICE semantics, clouds in Morton order): the passes of the first `cull_levels` levels run in their
 // chunk-culling form -- a pass culls by the SMALLER of its levels, so giver pass `lev` (sweep 3 of lev - 1, sweep 1 of lev)
 // qualifies with lev < cull_levels like receiver pass `lev`.
-template <bool HOST, typename F>
+template <bool HOST, typename F = NothingBetween>
 int run_passes(int b, int n, int m, const float *xyz1, const float *xyz2, void *temp, int slots, hipStream_t s,
-               F between, size_t cstride = 0, int cull_levels = 0)
+               size_t cstride = 0, int cull_levels = 0, F between = F())
 {
     constexpr int L = Sem<HOST>::levels;
     const dim3 gl(mpsr::ceil_div(n, kThreads * kPT), b), gr(mpsr::ceil_div(m, kThreads * kPT), b);
-    int skip = g_emd_skip.load();  // 1: leave exhausted receivers out (exact), 2: and split short receiver passes
-    if (g_emd_cull.load() == 2) skip |= kNeverCull;
-    if constexpr (HOST) cull_levels = 0;
-    if constexpr (!HOST) {
-        if (cull_levels > 0)
-            hipLaunchKernelGGL((emd_giver_kernel<false, 0, true>), gl, dim3(kThreads), 0, s, n, m, xyz1, xyz2, temp, 0, slots,
-                               cstride, skip);
-    }
-    if (cull_levels <= 0)
-        hipLaunchKernelGGL((emd_giver_kernel<HOST, 0>), gl, dim3(kThreads), 0, s, n, m, xyz1, xyz2, temp, 0, slots,
-                           cstride, skip);
+    const int skip = g_emd_skip.load();  // 1: leave exhausted receivers out (exact), 2: and split short receiver passes
+    const float cull_exp = cull_exp_arg();
+    launch_giver<HOST, 0>(0 < cull_levels, gl, s, n, m, xyz1, xyz2, temp, 0, slots, cstride, skip, cull_exp);
     for (int lev = 0; lev < L; ++lev) {
-        bool done = false;
-        if constexpr (!HOST) {
-            if (lev < cull_levels) {
-                hipLaunchKernelGGL((emd_receiver_kernel<false, true>), gr, dim3(kThreads), 0, s, n, m, xyz1, xyz2, temp, lev,
-                                   slots, cstride, skip);
-                done = true;
-            }
-        }
-        if (!done)
-            hipLaunchKernelGGL((emd_receiver_kernel<HOST>), gr, dim3(kThreads), 0, s, n, m, xyz1, xyz2, temp, lev, slots,
-                               cstride, skip);
+        launch_receiver<HOST>(lev < cull_levels, gr, s, n, m, xyz1, xyz2, temp, lev, slots, cstride, skip, cull_exp);
         if (int rc = between(lev)) return rc;
-        if (lev + 1 < L) {
-            done = false;
-            if constexpr (!HOST) {
-                if (lev + 1 < cull_levels) {
-                    hipLaunchKernelGGL((emd_giver_kernel<false, 1, true>), gl, dim3(kThreads), 0, s, n, m, xyz1, xyz2, temp,
-                                       lev + 1, slots, cstride, skip);
-                    done = true;
-                }
-            }
-            if (!done)
-                hipLaunchKernelGGL((emd_giver_kernel<HOST, 1>), gl, dim3(kThreads), 0, s, n, m, xyz1, xyz2, temp, lev + 1,
-                                   slots, cstride, skip);
-        }
         // the giver capacity after the last level is never read: no trailing sweep 3
+        if (lev + 1 < L)
+            launch_giver<HOST, 1>(lev + 1 < cull_levels, gl, s, n, m, xyz1, xyz2, temp, lev + 1, slots, cstride, skip,
+                                  cull_exp);
     }
     MPSR_CHECK_LAUNCH("emd passes");
+    return MPSR_OK;
+}
+
+// match from the ratios of every level in `temp`; grid, cstride and row_limit as at emd_emit_kernel
+template <bool HOST>
+int launch_emit(dim3 grid, hipStream_t s, int n, int m, const float *xyz1, const float *xyz2, void *temp, float *match,
+                size_t cstride = 0, int row_limit = 0x7fffffff)
+{
+    hipLaunchKernelGGL(emd_emit_kernel<HOST>, grid, dim3(256), 0, s, n, m, xyz1, xyz2, temp, match, cstride, row_limit);
+    MPSR_CHECK_LAUNCH("emd_emit_kernel");
+    return MPSR_OK;
+}
+
+// The DEVICE-semantics fused loss on clouds x1 / x2: the passes, then both roles of the packed loss kernel.  CULL: the clouds
+// are in Morton order, perm1 / perm2 lead the gradients back to the caller's order (unused without CULL).
+template <bool CULL>
+int device_loss(int b, int n, int m, const float *x1, const float *x2, const int *perm1, const int *perm2, float *cost,
+                float *grad1, float *grad2, void *temp, hipStream_t s)
+{
+    const dim3 p1(mpsr::ceil_div(n, 512), b), p2(mpsr::ceil_div(m, 512), b), gf(mpsr::ceil_div(b, 64));
+    const float cull_exp = cull_exp_arg();
+    if (int rc = run_passes<false>(b, n, m, x1, x2, temp, Sem<false>::levels, s, 0, CULL ? kCullLevels : 0)) return rc;
+    hipLaunchKernelGGL((emd_loss_pk_kernel<0, CULL>), p1, dim3(256), 0, s, n, m, x1, x2, temp, cost, grad1, perm1, cull_exp);
+    hipLaunchKernelGGL(emd_cost_finish_kernel<false>, gf, dim3(64), 0, s, b, n, m, temp, (int)p1.x, cost);
+    if (grad2)
+        hipLaunchKernelGGL((emd_loss_pk_kernel<1, CULL>), p2, dim3(256), 0, s, n, m, x1, x2, temp, cost, grad2, perm2,
+                           cull_exp);
     return MPSR_OK;
 }
 
@@ -1379,23 +1393,16 @@ extern "C" int mpsr_approx_match_ex(int b, int n, int m, const float *xyz1, cons
         if (temp_floats < full)
             return mpsr::fail(MPSR_ERR_WORKSPACE, "approx_match (host semantics): temp holds %zu floats, needs %zu",
                               temp_floats, full);
-        if (int rc = run_passes<true>(b, n, m, xyz1, xyz2, temp, Sem<true>::levels, s, [](int) { return 0; })) return rc;
+        if (int rc = run_passes<true>(b, n, m, xyz1, xyz2, temp, Sem<true>::levels, s)) return rc;
         dim3 grid(mpsr::ceil_div(m, 256), mpsr::ceil_div(n, kEmitRows), b);
         MPSR_REQUIRE(grid.y <= 65535, "approx_match: n=%d too large", n);
-        hipLaunchKernelGGL(emd_emit_kernel<true>, grid, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, match, (size_t)0,
-                           0x7fffffff);
-        MPSR_CHECK_LAUNCH("emd_emit_kernel");
-        return MPSR_OK;
+        return launch_emit<true>(grid, s, n, m, xyz1, xyz2, temp, match);
     }
     dim3 grid(mpsr::ceil_div(n, 256), mpsr::ceil_div(m, kEmitRows), b);
     MPSR_REQUIRE(grid.y <= 65535, "approx_match: m=%d too large", m);
     if (temp_floats >= full) {
-        if (int rc = run_passes<false>(b, n, m, xyz1, xyz2, temp, Sem<false>::levels, s, [](int) { return 0; }))
-            return rc;
-        hipLaunchKernelGGL(emd_emit_kernel<false>, grid, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, match, (size_t)0,
-                           0x7fffffff);
-        MPSR_CHECK_LAUNCH("emd_emit_kernel");
-        return MPSR_OK;
+        if (int rc = run_passes<false>(b, n, m, xyz1, xyz2, temp, Sem<false>::levels, s)) return rc;
+        return launch_emit<false>(grid, s, n, m, xyz1, xyz2, temp, match);
     }
     if (temp_floats < compact)
         return mpsr::fail(MPSR_ERR_WORKSPACE,
@@ -1417,10 +1424,8 @@ extern "C" int mpsr_approx_match_ex(int b, int n, int m, const float *xyz1, cons
             const size_t lds = (size_t)L * n * sizeof(float);
             if (m - row0 <= kEmitRows && lds <= 128 * 1024) {
                 float *state = match + (block - S);  // cloud 0's state; cloud c's is c * block words further
-                if (int rc = run_passes<false>(b, n, m, xyz1, xyz2, state, L, s, [](int) { return 0; }, block)) return rc;
-                hipLaunchKernelGGL(emd_emit_kernel<false>, grid, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)state, match,
-                                   block, row0);
-                MPSR_CHECK_LAUNCH("emd_emit_kernel");
+                if (int rc = run_passes<false>(b, n, m, xyz1, xyz2, state, L, s, block)) return rc;
+                if (int rc = launch_emit<false>(grid, s, n, m, xyz1, xyz2, state, match, block, row0)) return rc;
                 MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(emd_emit_tail_kernel),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 hipLaunchKernelGGL(emd_emit_tail_kernel, dim3(b), dim3(256), lds, s, n, m, xyz1, xyz2, (void *)state,
@@ -1431,7 +1436,7 @@ extern "C" int mpsr_approx_match_ex(int b, int n, int m, const float *xyz1, cons
         }
     }
     // small or very ragged clouds: one ratio slot in the caller's scratch, match accumulated level by level
-    return run_passes<false>(b, n, m, xyz1, xyz2, temp, 1, s, [&](int lev) {
+    return run_passes<false>(b, n, m, xyz1, xyz2, temp, 1, s, 0, 0, [&](int lev) {
         hipLaunchKernelGGL(emd_accumulate_kernel, grid, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, match, lev);
         return 0;
     });
@@ -1455,44 +1460,25 @@ extern "C" int mpsr_emd_loss(int b, int n, int m, const float *xyz1, const float
         return mpsr::fail(MPSR_ERR_WORKSPACE, "emd_loss: temp holds %zu floats, needs %zu (mpsr_emd_temp_floats)",
                           temp_floats, full);
     hipStream_t s = mpsr::as_stream(stream);
-    const dim3 g1(mpsr::ceil_div(n, 256), b), g2(mpsr::ceil_div(m, 256), b);
-    const dim3 gf(mpsr::ceil_div(b, 64));
     if (semantics == MPSR_EMD_HOST) {
+        const dim3 g1(mpsr::ceil_div(n, 256), b), g2(mpsr::ceil_div(m, 256), b), gf(mpsr::ceil_div(b, 64));
         MPSR_REQUIRE(((uintptr_t)temp & 7) == 0, "emd_loss: temp must be 8-byte aligned for the host semantics");
-        if (int rc = run_passes<true>(b, n, m, xyz1, xyz2, temp, Sem<true>::levels, s, [](int) { return 0; })) return rc;
-        hipLaunchKernelGGL((emd_loss_kernel<true, 0>), g1, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, cost, grad1);
+        if (int rc = run_passes<true>(b, n, m, xyz1, xyz2, temp, Sem<true>::levels, s)) return rc;
+        hipLaunchKernelGGL(emd_loss_kernel<0>, g1, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, cost, grad1);
         hipLaunchKernelGGL(emd_cost_finish_kernel<true>, gf, dim3(64), 0, s, b, n, m, (void *)temp, (int)g1.x, cost);
         if (grad2)
-            hipLaunchKernelGGL((emd_loss_kernel<true, 1>), g2, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, cost,
-                               grad2);
+            hipLaunchKernelGGL(emd_loss_kernel<1>, g2, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, cost, grad2);
+    } else if (g_emd_cull.load() && n <= kSortMax && m <= kSortMax &&
+               temp_floats >= full + emd_cull_extra_floats(b, n, m)) {
+        // level culling (r06): both clouds into Morton order behind the state, every pass and both loss kernels on
+        // the sorted clouds, the four steepest levels' passes and the loss kernels in their chunk-culling form
+        float *s1 = temp + full, *s2 = s1 + (size_t)b * n * 3;
+        int *perm1 = reinterpret_cast<int *>(s2 + (size_t)b * m * 3), *perm2 = perm1 + (size_t)b * n;
+        hipLaunchKernelGGL(emd_sort_kernel, dim3(b, 2), dim3(256), 0, s, n, m, xyz1, xyz2, s1, s2, perm1, perm2);
+        MPSR_CHECK_LAUNCH("emd_sort_kernel");
+        if (int rc = device_loss<true>(b, n, m, s1, s2, perm1, perm2, cost, grad1, grad2, temp, s)) return rc;
     } else {
-        const dim3 p1(mpsr::ceil_div(n, 512), b), p2(mpsr::ceil_div(m, 512), b);
-        if (g_emd_cull.load() && n <= kSortMax && m <= kSortMax && temp_floats >= full + emd_cull_extra_floats(b, n, m)) {
-            // level culling (r06): both clouds into Morton order behind the state, every pass and both loss kernels on
-            // the sorted clouds, the four steepest levels' passes and the loss kernels in their chunk-culling form
-            float *s1 = temp + full, *s2 = s1 + (size_t)b * n * 3;
-            int *perm1 = reinterpret_cast<int *>(s2 + (size_t)b * m * 3), *perm2 = perm1 + (size_t)b * n;
-            hipLaunchKernelGGL(emd_sort_kernel, dim3(b, 2), dim3(256), 0, s, n, m, xyz1, xyz2, s1, s2, perm1, perm2);
-            MPSR_CHECK_LAUNCH("emd_sort_kernel");
-            if (int rc = run_passes<false>(b, n, m, s1, s2, temp, Sem<false>::levels, s, [](int) { return 0; }, 0, kCullLevels))
-                return rc;
-            const int flags = g_emd_cull.load() == 2 ? kNeverCull : 0;
-            hipLaunchKernelGGL((emd_loss_pk_kernel<0, true>), p1, dim3(256), 0, s, n, m, s1, s2, (void *)temp, cost, grad1,
-                               (const int *)perm1, flags);
-            hipLaunchKernelGGL(emd_cost_finish_kernel<false>, gf, dim3(64), 0, s, b, n, m, (void *)temp, (int)p1.x, cost);
-            if (grad2)
-                hipLaunchKernelGGL((emd_loss_pk_kernel<1, true>), p2, dim3(256), 0, s, n, m, s1, s2, (void *)temp, cost,
-                                   grad2, (const int *)perm2, flags);
-        } else {
-            if (int rc = run_passes<false>(b, n, m, xyz1, xyz2, temp, Sem<false>::levels, s, [](int) { return 0; }))
-                return rc;
-            hipLaunchKernelGGL(emd_loss_pk_kernel<0>, p1, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, cost, grad1,
-                               (const int *)nullptr, 0);
-            hipLaunchKernelGGL(emd_cost_finish_kernel<false>, gf, dim3(64), 0, s, b, n, m, (void *)temp, (int)p1.x, cost);
-            if (grad2)
-                hipLaunchKernelGGL(emd_loss_pk_kernel<1>, p2, dim3(256), 0, s, n, m, xyz1, xyz2, (void *)temp, cost, grad2,
-                                   (const int *)nullptr, 0);
-        }
+        if (int rc = device_loss<false>(b, n, m, xyz1, xyz2, nullptr, nullptr, cost, grad1, grad2, temp, s)) return rc;
     }
     MPSR_CHECK_LAUNCH("emd_loss_kernel");
     return MPSR_OK;

@@ -201,7 +201,7 @@ def test_emd_vs_oracle(b, n, m):
 
 
 @pytest.mark.parametrize("b,n,m", [(1, 1, 1), (2, 3, 3), (2, 40, 40), (2, 12, 4), (2, 4, 12), (2, 7, 5), (2, 300, 300),
-                                   (1, 700, 450)])
+                                   (1, 700, 450), (1, 1100, 1030)])
 def test_emd_host_semantics_vs_pinned_cpu_oracle(b, n, m):
     """semantics="host" (11 levels from j = 8, double state, (b,n,m) layout: tf_approxmatch.cpp:23-140) against the
     oracle's restatement of the reference's CPU kernel -- the one pinned by the reference's known-answer tests."""
