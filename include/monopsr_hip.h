@@ -1072,6 +1072,69 @@ int mpsr_scene_score(const float *xyz_global, const int *box_frame, const int *b
                      int points_per_box, const void *workspace, size_t workspace_bytes, void *scratch,
                      size_t scratch_bytes, int *counts, double *sums, mpsr_stream_t stream);
 
+/* ---- Instance maps rendered as surfaces (additive to ABI 13) ----
+ * The same chunk as above, but a box's points are a (map_h, map_w) grid (points_per_box = map_h * map_w, row-major)
+ * whose cells are joined into triangles and rasterised through a 64-bit z-buffer of their own.  Cell (i, j),
+ * 0 <= i < map_h - 1, 0 <= j < map_w - 1, has the corners v00 = (i, j), v01 = (i, j + 1), v10 = (i + 1, j),
+ * v11 = (i + 1, j + 1) and gives triangle k = 0: (v00, v01, v10) and k = 1: (v11, v10, v01); the triangle id is
+ * t = ((b (map_h - 1) + i) (map_w - 1) + j) 2 + k.  The workspace is separate from mpsr_scene_workspace_bytes': both
+ * renderings of a chunk can coexist.  render, then resolve and / or score, on one stream.
+ * Checked on the host before any launch, by every entry point: map_h or map_w < 2 and
+ * n_boxes (map_h - 1) (map_w - 1) 2 >= 2^32 are MPSR_ERR_INVALID_ARG, like negative sizes, null pointers with
+ * non-empty sizes and a box_frame_host out of range or decreasing; n_frames or n_boxes 0 is a no-op; a workspace
+ * smaller than mpsr_scene_surface_workspace_bytes is MPSR_ERR_WORKSPACE. */
+
+/* Bytes of the workspace: one uint64 key per pixel, one (int32, int32) vertex per map point, n_frames + 1 first-box
+ * indices, and per box a triangle count and a pixel rectangle.  0 for empty or refused sizes. */
+size_t mpsr_scene_surface_workspace_bytes(int n_frames, long long total_pixels, int n_boxes, int map_h, int map_w);
+
+/* The arguments of mpsr_scene_project, and max_edge_dz (float32, > 0, +inf allowed; NaN or <= 0 is
+ * MPSR_ERR_INVALID_ARG) and max_span_px (1..1024, else MPSR_ERR_INVALID_ARG).
+ * Vertices: u as in mpsr_scene_project.  A vertex is VALID when its box is kept, its mask is > 0, x, y and z are
+ * finite, z > 0, u2 > 0, |u0 / u2| < 2^20 and |u1 / u2| < 2^20 (it need not be inside the image).  A valid vertex has
+ * the fixed-point screen coordinates X = (int) rint((u0 / u2) 256.0), Y = (int) rint((u1 / u2) 256.0) (half to even):
+ * the centre of pixel (col, row) is (256 col, 256 row).
+ * A triangle (a, b, c) is DROPPED when a vertex is invalid; when max(z) - min(z) of its three float32 depths, taken in
+ * float32, is > max_edge_dz; when its doubled area A = (bX - aX)(cY - aY) - (bY - aY)(cX - aX) (int64) is 0; or when
+ * its pixel extent in columns or rows, floor(max / 256) - ceil(min / 256) + 1 (unclamped), exceeds max_span_px.  Every
+ * other triangle is DRAWN (an extent <= 0 covers no pixel centre and draws nothing).  With A < 0, b and c are swapped.
+ * Coverage of the pixel centre s, over the extent clamped to the image: E(p, q, s) = (qX - pX)(sY - pY) -
+ * (qY - pY)(sX - pX), e0 = E(b, c, s), e1 = E(c, a, s), e2 = E(a, b, s), all exact; covered when every e_k > 0, or
+ * e_k == 0 and the edge p -> q owns its boundary: qY - pY > 0, or qY - pY == 0 and qX - pX < 0.
+ * Depth, fp64 without contraction: q = (e0 (1.0 / za) + e1 (1.0 / zb)) + e2 (1.0 / zc), zf = (float)(A / q).  The key
+ * ((uint64) float_bits(zf) << 32) | t is lowered with an unsigned 64-bit atomicMin: the nearer surface wins, on equal
+ * float32 depth the lower triangle id.  Per box, by integer atomics: the number of drawn triangles and the rectangle
+ * (min / max column and row) of their clamped extents.  Two calls return the same bytes. */
+int mpsr_scene_surface_render(const float *xyz_global, const float *valid_mask, const int *box_frame,
+                              const int *box_frame_host, const int *box_keep, const double *cam_p, const int *frame_hw,
+                              const int *frame_hw_host, const long long *pixel_offset,
+                              const long long *pixel_offset_host, int n_frames, int n_boxes, int map_h, int map_w,
+                              float max_edge_dz, int max_span_px, void *workspace, size_t workspace_bytes,
+                              mpsr_stream_t stream);
+
+/* depth (total_pixels) float32: the key's upper half, 0 for an empty pixel; instance (total_pixels) uint8: the winner
+ * box's ordinal within its frame, 255 for an empty pixel; tri (total_pixels) int32 or null: the winner's t, -1 for an
+ * empty pixel.  A frame of more than MPSR_INSTANCE_MAX_BOXES boxes is MPSR_ERR_INVALID_ARG. */
+int mpsr_scene_surface_resolve(const int *box_frame, const int *box_frame_host, int n_frames, long long total_pixels,
+                               int n_boxes, int map_h, int map_w, const void *workspace, size_t workspace_bytes,
+                               float *depth, unsigned char *instance, int *tri, mpsr_stream_t stream);
+
+/* The surfaces against ground truth: gt_depth, gt_instance, box_gt_id and scratch (mpsr_scene_score_scratch_bytes) as
+ * mpsr_scene_score takes them.  counts (n_boxes, 5) int32, exact: 0 tris (drawn triangles), 1 pred_px (pixels the box
+ * wins), 2 inter_px (won pixels whose instance value is g), 3 gt_px (pixels of the frame whose value is g; 0 when g is
+ * outside [0, 254]), 4 depth_n (inter_px pixels whose ground-truth depth d is finite and > 0).  sums (n_boxes, 3)
+ * fp64 over the depth_n pixels, e = (double)zf - (double)d: the sums of e, |e| and e * e (the square rounded first).
+ * One workgroup per box walks the box's rectangle row-major in slices of 256 pixels; each thread adds in slice order,
+ * then a lane-ordered wave reduction and a combine in wave order: no floating-point atomics, two calls return the
+ * same bytes.  A scratch that is too small is MPSR_ERR_WORKSPACE.  box_gt_id, gt_depth and gt_instance all null: no
+ * ground truth (tris and pred_px alone, the other counts and the sums 0, no scratch needed); one or two of them null
+ * is MPSR_ERR_INVALID_ARG. */
+int mpsr_scene_surface_score(const int *box_frame, const int *box_frame_host, const int *box_gt_id,
+                             const float *const *gt_depth, const unsigned char *const *gt_instance,
+                             const int *frame_hw, const long long *pixel_offset, int n_frames, long long total_pixels,
+                             int n_boxes, int map_h, int map_w, const void *workspace, size_t workspace_bytes,
+                             void *scratch, size_t scratch_bytes, int *counts, double *sums, mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,6 +231,13 @@ SIGNATURES = {
     "mpsr_scene_score_scratch_bytes": (c_sz, [c_i]),
     "mpsr_scene_score": (c_i, [c_f, c_f, ctypes.c_void_p, c_f, c_f, c_f, c_f, c_i, ctypes.c_longlong, c_i, c_i, c_f,
                                c_sz, c_f, c_sz, c_f, c_f, c_f]),
+    "mpsr_scene_surface_workspace_bytes": (c_sz, [c_i, ctypes.c_longlong, c_i, c_i, c_i]),
+    "mpsr_scene_surface_render": (c_i, [c_f, c_f, c_f, ctypes.c_void_p, c_f, c_f, c_f, ctypes.c_void_p, c_f,
+                                        ctypes.c_void_p, c_i, c_i, c_i, c_i, ctypes.c_float, c_i, c_f, c_sz, c_f]),
+    "mpsr_scene_surface_resolve": (c_i, [c_f, ctypes.c_void_p, c_i, ctypes.c_longlong, c_i, c_i, c_i, c_f, c_sz, c_f,
+                                         c_f, c_f, c_f]),
+    "mpsr_scene_surface_score": (c_i, [c_f, ctypes.c_void_p, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_longlong, c_i, c_i,
+                                       c_i, c_f, c_sz, c_f, c_sz, c_f, c_f, c_f]),
 }
 
 

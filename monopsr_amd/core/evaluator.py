@@ -36,6 +36,11 @@ takes their statistics with NAN_RULE_ENTRY (a box without overlap drops its own 
 result['scene_stats'], and with predictions_base_dir one line in metrics/<split>/scene_metrics_<split>.csv
 (evaluator_utils.save_scene_stats).  DESIGN.md section 7.8.
 
+scene_metrics='surface' does what True does and also renders every chunk's maps as surfaces (DESIGN.md section 7.9:
+scene_reconstruction.render_instance_surfaces with its default max_edge_dz and max_span_px) and scores them against the
+same ground truth: result['surface_stats'] over scene_reconstruction.SURFACE_METRIC_NAMES, and with predictions_base_dir
+one line in metrics/<split>/surface_metrics_<split>.csv (evaluator_utils.save_surface_stats).
+
 Not built: TF summaries and metrics_to_show, both IoU settings in one pass.
 """
 import argparse
@@ -124,8 +129,14 @@ class Evaluator:
         if scene_metrics and getattr(dataset, 'train_val_test', None) != 'val':
             raise ValueError("scene_metrics scores the reconstruction against ground truth: it needs a 'val'-mode "
                              "dataset, got %r" % (getattr(dataset, 'train_val_test', None),))
+        if isinstance(scene_metrics, str) and scene_metrics != 'surface':
+            raise ValueError("scene_metrics must be False, True or 'surface', got %r" % (scene_metrics,))
         self.model = model
         self.scene_metrics = bool(scene_metrics)
+        self.surface_metrics = scene_metrics == 'surface'
+        # after a run_once with scene_metrics='surface': (table (n,6) float32 in SURFACE_METRIC_NAMES order, counts
+        # (n,5) int32, sums (n,3) float64, frame (n,) int32) on the device, in the order of the pass
+        self.surface_table = None
         # after a run_once with scene_metrics: (table (n,6) float32 in SCENE_METRIC_NAMES order, counts (n,6) int32,
         # sums (n,3) float64, frame (n,) int32) on the device, one row per object in the order of the pass
         self.scene_table = None
@@ -153,7 +164,8 @@ class Evaluator:
         """-> (box_3d (N,9), box_2d (N,7), frame (N,) int32: rows of the dataset's frame tables; metric sums (2,2):
         [emd, chamfer] x [sum of the entries that are not NaN, their number]; loss names and their sums (n,2) in the
         same form; the metric table (N, 10) float32 in METRIC_COLUMNS' order, or None; with scene_metrics the scene
-        scores (table (N,6) float32, counts (N,6) int32, sums (N,3) float64), else None), all on the device."""
+        scores (table (N,6) float32, counts (N,6) int32, sums (N,3) float64), else None; with scene_metrics='surface'
+        the surface scores in the same form (counts (N,5)), else None), all on the device."""
         ds, model = self.dataset, self.model
         dev = ds.device
         # the frames in split order, whatever the epoch's shuffle made of sample_list
@@ -165,7 +177,7 @@ class Evaluator:
         with_table = ds.train_val_test == 'val' and self.metric_stats
         loss_names, loss_sums = [], None
         table = []
-        scene_parts = []
+        scene_parts, surface_parts = [], []
         if with_losses or with_table:
             # the 'val'-mode graph of the same net: method by method, with the ground truth and the offsets
             from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
@@ -185,9 +197,13 @@ class Evaluator:
                     gt = ds.frame_ground_truth(rows)
                     gt = dict(depth_maps=[g['depth_map'] for g in gt], instance_images=[g['instance_image'] for g in gt],
                               box_gt_id=torch.cat([g['instance_ids'] for g in gt]))
-                    scores = scene_reconstruction.reconstruct_frames(model, samples, outs, min_score=None,
-                                                                     ground_truth=gt).scores
+                    scene = scene_reconstruction.reconstruct_frames(model, samples, outs, min_score=None, ground_truth=gt,
+                                                                    surfaces={} if self.surface_metrics else None)
+                    scores = scene.scores
                     scene_parts.append((scores.table(), scores.counts, scores.sums))
+                    if self.surface_metrics:
+                        scores = scene.surfaces.scores
+                        surface_parts.append((scores.table(), scores.counts, scores.sums))
                 for r, s, o in zip(rows, samples, outs):
                     n = int(s['num_objs'])
                     b3, b2 = instance_utils.format_boxes(
@@ -232,7 +248,8 @@ class Evaluator:
                         loss_sums[:, 1] += ok
         return (torch.cat(b3s), torch.cat(b2s), torch.cat(frames), sums, loss_names, loss_sums,
                 torch.cat(table).contiguous() if with_table else None,
-                tuple(torch.cat(part).contiguous() for part in zip(*scene_parts)) if self.scene_metrics else None)
+                tuple(torch.cat(part).contiguous() for part in zip(*scene_parts)) if self.scene_metrics else None,
+                tuple(torch.cat(part).contiguous() for part in zip(*surface_parts)) if self.surface_metrics else None)
 
     def _rows_to_host(self, b3, b2, frame):
         """One launch, one compaction, one copy: -> (rows (m,14) float64, class index (m,), frame (m,)) of the kept
@@ -256,7 +273,7 @@ class Evaluator:
 
     def run_once(self, global_step=None):
         ds = self.dataset
-        b3, b2, frame, sums, loss_names, loss_sums, table, scene = self._predict()
+        b3, b2, frame, sums, loss_names, loss_sums, table, scene, surface = self._predict()
         rows, cls, frame_h = self._rows_to_host(b3, b2, frame)
         names = ds.sample_names
         per_frame = {}
@@ -297,6 +314,17 @@ class Evaluator:
             if self.predictions_base_dir is not None:
                 result['scene_metrics_csv'] = evaluator_utils.save_scene_stats(
                     self.predictions_base_dir, ds.data_split, global_step, SCENE_METRIC_NAMES, result['scene_stats'])
+        if surface is not None:
+            from monopsr_amd.core.scene_reconstruction import SURFACE_METRIC_NAMES
+            self.surface_table = surface + (frame,)
+            stats = evaluator_utils.metric_stats(surface[0], frame, range(len(SURFACE_METRIC_NAMES)),
+                                                 len(SURFACE_METRIC_NAMES), ds.num_samples,
+                                                 evaluator_utils.NAN_RULE_ENTRY)
+            result['surface_stats'] = evaluator_utils.metric_stats_dict(SURFACE_METRIC_NAMES, stats.cpu().numpy())
+            if self.predictions_base_dir is not None:
+                result['surface_metrics_csv'] = evaluator_utils.save_surface_stats(
+                    self.predictions_base_dir, ds.data_split, global_step, SURFACE_METRIC_NAMES,
+                    result['surface_stats'])
         if self.predictions_base_dir is not None:
             out_dir = evaluator_utils.kitti_output_dir(self.predictions_base_dir, ds.data_split, self.score_threshold,
                                                        global_step)

@@ -197,6 +197,30 @@ def save_scene_stats(predictions_base_dir, data_split, global_step, names, scene
     return path
 
 
+def save_surface_stats(predictions_base_dir, data_split, global_step, names, surface_stats):
+    """Appends one line per call to <predictions_base_dir>/metrics/<split>/surface_metrics_<split>.csv, in the format
+    of save_scene_stats: the step, then count, mean and std of every metric of `names`, in that order; into an empty
+    file first a header ('step', then <name>_count, <name>_mean, <name>_std with the 'surface_' prefix left off).  The
+    step is right-justified to 8, the other fields to 22; counts as integers, means and stds as '{:.5f}'.  Returns the
+    path."""
+    out_dir = metrics_dir(predictions_base_dir, data_split)
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, 'surface_metrics_%s.csv' % data_split)
+    short = [n[len('surface_'):] if n.startswith('surface_') else n for n in names]
+    with open(path, 'a', newline='') as f:
+        writer = csv.writer(f, delimiter=',')
+        if f.tell() == 0:
+            writer.writerow(['step'.rjust(8)] + [('%s_%s' % (n, stat)).rjust(22) for n in short
+                                                 for stat in ('count', 'mean', 'std')])
+        row = ['{}'.format(global_step).rjust(8)]
+        for n in names:
+            st = surface_stats[n]
+            row += ['{:d}'.format(int(st['count'])).rjust(22), '{:.5f}'.format(st['mean']).rjust(22),
+                    '{:.5f}'.format(st['std']).rjust(22)]
+        writer.writerow(row)
+    return path
+
+
 def kitti_label_rows(box_3d, box_2d, classes, score_threshold, image_boxes=None, keep=None):
     """Detections of one frame -> list of KITTI label lines (no line ends).
     box_3d (n,9), box_2d (n,7) as format_predictions returns them; `image_boxes` (n,4) [x1,y1,x2,y2] replaces the

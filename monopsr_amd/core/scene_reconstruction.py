@@ -21,6 +21,10 @@ section 7.8): SceneResult.scores, a SceneScores of six exact counts and three fp
 SCENE_METRIC_NAMES.  One limit: a box has 48 x 48 points, so a box larger than 48 x 48 pixels cannot fill its mask, and
 scene_mask_iou is bounded by pred_px / gt_px for near objects.  That is why the two precisions and the raw counts are
 reported next to it.
+
+render_instance_surfaces lifts that limit: it joins the cells of a box's map into triangles and
+rasterises them through a z-buffer of its own, so that the depth map and the instance image are dense, and scores them
+the same way (SurfaceResult, SurfaceScores, SURFACE_METRIC_NAMES).  reconstruct_frames(..., surfaces={...}) renders both.
 """
 import ctypes
 import os
@@ -36,6 +40,16 @@ SCENE_COUNT_NAMES = ('kept', 'on_points', 'pred_px', 'inter_px', 'gt_px', 'depth
 SCENE_SUM_NAMES = ('sum_e', 'sum_abs_e', 'sum_e2')
 SCENE_METRIC_NAMES = ('scene_mask_iou', 'scene_mask_precision', 'scene_point_precision', 'scene_depth_bias',
                       'scene_depth_mae', 'scene_depth_rmse')
+
+# the same of SurfaceScores (mpsr_scene_surface_score)
+SURFACE_COUNT_NAMES = ('tris', 'pred_px', 'inter_px', 'gt_px', 'depth_n')
+SURFACE_SUM_NAMES = ('sum_e', 'sum_abs_e', 'sum_e2')
+SURFACE_METRIC_NAMES = ('surface_mask_iou', 'surface_mask_precision', 'surface_mask_recall', 'surface_depth_bias',
+                        'surface_depth_mae', 'surface_depth_rmse')
+# the defaults of render_instance_surfaces.  1.0 m between neighbouring samples of one surface (about a quarter of a
+# car's length) is an assumption, not a measurement: DESIGN.md section 7.9
+SURFACE_MAX_EDGE_DZ = 1.0
+SURFACE_MAX_SPAN_PX = 64
 
 _PLY_DTYPE = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('green', 'u1'), ('blue', 'u1'),
                        ('box', '<i4')])
@@ -101,12 +115,14 @@ class SceneResult(object):
     int32 (index into the call's boxes), pixel (M,) int32, frame_offset (F+1,) int64 (frame f owns rows
     frame_offset[f] .. frame_offset[f+1]), depth_maps / instance_maps: lists of (H_f, W_f) float32 / uint8,
     kept_per_box / visible_per_box (B,) int32.  frame_offset_host and box_frame_host are their host copies.  scores: a
-    SceneScores when the call was given ground truth, else None."""
+    SceneScores when the call was given ground truth, else None.  surfaces: the SurfaceResult of the same chunk when
+    reconstruct_frames was asked for it, else None."""
     __slots__ = ('xyz', 'rgb', 'box', 'pixel', 'frame_offset', 'depth_maps', 'instance_maps', 'kept_per_box',
-                 'visible_per_box', 'frame_offset_host', 'box_frame_host', 'scores')
+                 'visible_per_box', 'frame_offset_host', 'box_frame_host', 'scores', 'surfaces')
 
     def __init__(self, **kw):
         kw.setdefault('scores', None)
+        kw.setdefault('surfaces', None)
         for k in self.__slots__:
             setattr(self, k, kw[k])
 
@@ -160,6 +176,55 @@ def _ground_truth_tables(ground_truth, hw, nb, dev):
     return out_d, out_i, ids.clamp(-1, 255).to(torch.int32).contiguous()
 
 
+def _frame_tables(frame_shapes, box_frame, nb):
+    """-> the host tables of a chunk, checked: hw (F, 2) int32, box_frame (B,) int32, pixel offsets (F + 1,) int64."""
+    nf = len(frame_shapes)
+    hw = np.ascontiguousarray(np.asarray([[int(s[0]), int(s[1])] for s in frame_shapes], np.int32).reshape(nf, 2))
+    if nf and int(hw.min()) <= 0:
+        raise _lib.InvalidArgumentError('frame_shapes must be positive, got %s' % (hw.tolist(),))
+    bf = _host_ints(box_frame).reshape(-1)
+    if len(bf) != nb:
+        raise _lib.InvalidArgumentError('box_frame has %d entries for %d boxes' % (len(bf), nb))
+    if nb and (int(bf.min()) < 0 or int(bf.max()) >= nf or bool(np.any(np.diff(bf) < 0))):
+        raise _lib.InvalidArgumentError('box_frame must lie in [0, %d) and never decrease' % nf)
+    if nb and int(np.bincount(bf).max()) > MAX_BOXES:
+        raise _lib.InvalidArgumentError('a frame has %d boxes, more than %d (255 of an instance image is the '
+                                        'background)' % (int(np.bincount(bf).max()), MAX_BOXES))
+    offs = np.zeros(nf + 1, np.int64)
+    offs[1:] = np.cumsum(hw[:, 0].astype(np.int64) * hw[:, 1])
+    return hw, bf, offs
+
+
+def _cameras(cam_p, nf, dev):
+    """cam_p (a tensor, an array or a list of (3, 4)) -> (F, 3, 4) float64 on the device."""
+    import torch
+    if torch.is_tensor(cam_p):
+        cam = cam_p.to(dev).double().reshape(-1, 3, 4).contiguous()
+    else:
+        cam = torch.from_numpy(np.ascontiguousarray(np.stack(
+            [(c.detach().cpu().numpy() if torch.is_tensor(c) else np.asarray(c)).astype(np.float64).reshape(3, 4)
+             for c in cam_p] or [np.zeros((3, 4))]))).to(dev)
+    if nf and cam.shape[0] != nf:
+        raise _lib.InvalidArgumentError('%d cameras for %d frames' % (cam.shape[0], nf))
+    return cam
+
+
+def _mask_and_keep(valid_mask, keep, nb, npts, dev):
+    """-> (valid_mask as (B, P) float32 or None, keep as (B,) int32 of 0 / 1 or None), on the device."""
+    import torch
+    mask = keep_d = None
+    if valid_mask is not None:
+        if valid_mask.numel() != nb * npts:
+            raise _lib.InvalidArgumentError('valid_mask %s does not match %d boxes of %d points'
+                                            % (tuple(valid_mask.shape), nb, npts))
+        mask = valid_mask.detach().to(dev).to(torch.float32).reshape(nb, npts).contiguous()
+    if keep is not None:
+        keep_d = torch.as_tensor(keep, device=dev).reshape(-1).ne(0).to(torch.int32).contiguous()
+        if keep_d.numel() != nb:
+            raise _lib.InvalidArgumentError('keep has %d entries for %d boxes' % (keep_d.numel(), nb))
+    return mask, keep_d
+
+
 def project_instance_points(xyz_global, box_frame, cam_p, frame_shapes, images=None, valid_mask=None, keep=None,
                             visible_only=False, ground_truth=None):
     """The direct wrapper of mpsr_scene_project / _resolve / _compact (and, with ground_truth, mpsr_scene_score).
@@ -181,48 +246,19 @@ def project_instance_points(xyz_global, box_frame, cam_p, frame_shapes, images=N
     dev = xyz_global.device
     nb = int(xyz_global.shape[0])
     npts = int(np.prod(xyz_global.shape[1:-1]))
-    nf = len(frame_shapes)
-    hw = np.ascontiguousarray(np.asarray([[int(s[0]), int(s[1])] for s in frame_shapes], np.int32).reshape(nf, 2))
-    if nf and int(hw.min()) <= 0:
-        raise _lib.InvalidArgumentError('frame_shapes must be positive, got %s' % (hw.tolist(),))
-    bf = _host_ints(box_frame).reshape(-1)
-    if len(bf) != nb:
-        raise _lib.InvalidArgumentError('box_frame has %d entries for %d boxes' % (len(bf), nb))
-    if nb and (int(bf.min()) < 0 or int(bf.max()) >= nf or bool(np.any(np.diff(bf) < 0))):
-        raise _lib.InvalidArgumentError('box_frame must lie in [0, %d) and never decrease' % nf)
-    if nb and int(np.bincount(bf).max()) > MAX_BOXES:
-        raise _lib.InvalidArgumentError('a frame has %d boxes, more than %d (255 of an instance image is the '
-                                        'background)' % (int(np.bincount(bf).max()), MAX_BOXES))
+    hw, bf, offs = _frame_tables(frame_shapes, box_frame, nb)
+    nf = len(hw)
     if nb * npts >= 2 ** 32:
         raise _lib.InvalidArgumentError('%d boxes of %d points: the point index does not fit 32 bits' % (nb, npts))
     if images is not None and len(images) != nf:
         raise _lib.InvalidArgumentError('%d images for %d frames' % (len(images), nf))
-    offs = np.zeros(nf + 1, np.int64)
-    offs[1:] = np.cumsum(hw[:, 0].astype(np.int64) * hw[:, 1])
     total = int(offs[-1])
     lib = _lib.lib()
     i32, i64, f32 = torch.int32, torch.int64, torch.float32
     with torch.cuda.device(dev):
-        if torch.is_tensor(cam_p):
-            cam = cam_p.to(dev).double().reshape(-1, 3, 4).contiguous()
-        else:
-            cam = torch.from_numpy(np.ascontiguousarray(np.stack(
-                [(c.detach().cpu().numpy() if torch.is_tensor(c) else np.asarray(c)).astype(np.float64).reshape(3, 4)
-                 for c in cam_p] or [np.zeros((3, 4))]))).to(dev)
-        if nf and cam.shape[0] != nf:
-            raise _lib.InvalidArgumentError('%d cameras for %d frames' % (cam.shape[0], nf))
+        cam = _cameras(cam_p, nf, dev)
         xyz_in = xyz_global.detach().to(f32).reshape(nb, npts, 3).contiguous()
-        mask = None
-        if valid_mask is not None:
-            if valid_mask.numel() != nb * npts:
-                raise _lib.InvalidArgumentError('valid_mask %s does not match %d boxes of %d points'
-                                                % (tuple(valid_mask.shape), nb, npts))
-            mask = valid_mask.detach().to(dev).to(f32).reshape(nb, npts).contiguous()
-        keep_d = None
-        if keep is not None:
-            keep_d = torch.as_tensor(keep, device=dev).reshape(-1).ne(0).to(i32).contiguous()
-            if keep_d.numel() != nb:
-                raise _lib.InvalidArgumentError('keep has %d entries for %d boxes' % (keep_d.numel(), nb))
+        mask, keep_d = _mask_and_keep(valid_mask, keep, nb, npts, dev)
         table = rgb = None
         imgs = []
         if images is not None:
@@ -285,13 +321,15 @@ def project_instance_points(xyz_global, box_frame, cam_p, frame_shapes, images=N
         kept_per_box=kept, visible_per_box=visible, frame_offset_host=fo_host, box_frame_host=bf, scores=scores)
 
 
-def reconstruct_frames(model, samples, outs, min_score=None, visible_only=False, ground_truth=None):
+def reconstruct_frames(model, samples, outs, min_score=None, visible_only=False, ground_truth=None, surfaces=None):
     """The scene of a chunk: `samples` as dataset.get_sample_dict returns them, `outs` as model.build_batch returns
     them.  The first num_objs rows of each frame: KEY_INST_XYZ_MAP_LOCAL placed with KEY_VIEW_ANG and KEY_CENTROIDS
     (instance_utils.tf_inst_xyz_map_local_to_global), masked by gt_valid_mask_maps where the sample carries them, kept
     where label_scores >= min_score (None: all), coloured from rgb_image, projected with cam_p.  ground_truth: as
     project_instance_points takes it (box_gt_id over the frames' first num_objs rows, frame after frame).
-    -> SceneResult."""
+    surfaces: None, or a dict of render_instance_surfaces' options max_edge_dz and max_span_px ({} for the defaults):
+    the same global maps, masks and keep flags are also rendered as surfaces, with the same ground truth, into
+    result.surfaces.  -> SceneResult."""
     import torch
     from monopsr_amd.core import constants
     from monopsr_amd.datasets.kitti import instance_utils
@@ -315,9 +353,203 @@ def reconstruct_frames(model, samples, outs, min_score=None, visible_only=False,
             keep = cat([s['label_scores'][0:n] for s, n in zip(samples, counts)], ()) >= float(min_score)
         cam_p = torch.stack([s['cam_p'].reshape(3, 4) for s in samples], 0)
         box_frame = np.repeat(np.arange(len(samples)), counts)
-        return project_instance_points(glob, box_frame, cam_p, [tuple(s['rgb_image'].shape) for s in samples],
-                                       images=[s['rgb_image'] for s in samples], valid_mask=mask, keep=keep,
-                                       visible_only=visible_only, ground_truth=ground_truth)
+        shapes = [tuple(s['rgb_image'].shape) for s in samples]
+        result = project_instance_points(glob, box_frame, cam_p, shapes, images=[s['rgb_image'] for s in samples],
+                                         valid_mask=mask, keep=keep, visible_only=visible_only,
+                                         ground_truth=ground_truth)
+        if surfaces is not None:
+            unknown = set(surfaces) - {'max_edge_dz', 'max_span_px'}
+            if unknown:
+                raise ValueError('surfaces: unknown options %s' % sorted(unknown))
+            result.surfaces = render_instance_surfaces(glob, box_frame, cam_p, shapes, valid_mask=mask, keep=keep,
+                                                       ground_truth=ground_truth, **surfaces)
+        return result
+
+
+# ---- surfaces
+
+
+def surface_score_table(counts, sums, box_gt_id):
+    """The (B, 6) float32 per-box metric table in SURFACE_METRIC_NAMES order from counts (B, 5) int, sums (B, 3)
+    float64 and box_gt_id (B,) int, tensors of one device: computed in fp64, rounded once.
+        surface_mask_iou        inter_px / (pred_px + gt_px - inter_px); NaN when the box has no ground truth (id
+                                outside [0, 254]) or the union is 0
+        surface_mask_precision  inter_px / pred_px; NaN when pred_px == 0
+        surface_mask_recall     inter_px / gt_px; NaN when gt_px == 0
+        surface_depth_bias      sum e / depth_n          (e = rendered depth - LiDAR depth over the depth_n pixels)
+        surface_depth_mae       sum |e| / depth_n
+        surface_depth_rmse      sqrt(sum e^2 / depth_n); all three NaN when depth_n == 0"""
+    import torch
+    c = counts.to(torch.float64)
+    _, pred_px, inter_px, gt_px, depth_n = (c[:, k] for k in range(5))
+    has_gt = (box_gt_id >= 0) & (box_gt_id <= 254)
+    nan = torch.full_like(pred_px, float('nan'))
+    ratio = lambda num, den, ok: torch.where(ok & (den > 0), num / torch.where(den > 0, den, torch.ones_like(den)), nan)
+    every = torch.ones_like(has_gt)
+    return torch.stack([ratio(inter_px, pred_px + gt_px - inter_px, has_gt), ratio(inter_px, pred_px, every),
+                        ratio(inter_px, gt_px, every), ratio(sums[:, 0], depth_n, every),
+                        ratio(sums[:, 1], depth_n, every), torch.sqrt(ratio(sums[:, 2], depth_n, every))],
+                       1).to(torch.float32)
+
+
+class SurfaceScores(object):
+    """The surfaces against their ground truth, per box, device tensors: counts (B, 5) int32 (SURFACE_COUNT_NAMES),
+    sums (B, 3) float64 (SURFACE_SUM_NAMES), box_gt_id (B,) int32 as given.  table(): surface_score_table of them."""
+    __slots__ = ('counts', 'sums', 'box_gt_id')
+
+    def __init__(self, counts, sums, box_gt_id):
+        self.counts, self.sums, self.box_gt_id = counts, sums, box_gt_id
+
+    def table(self):
+        return surface_score_table(self.counts, self.sums, self.box_gt_id)
+
+
+class FrameSurface(object):
+    """One frame of a SurfaceResult: depth_map (h,w) float32, instance_map (h,w) uint8, tri_map (h,w) int32 or None."""
+    __slots__ = ('depth_map', 'instance_map', 'tri_map')
+
+    def __init__(self, depth_map, instance_map, tri_map):
+        self.depth_map, self.instance_map, self.tri_map = depth_map, instance_map, tri_map
+
+
+class SurfaceResult(object):
+    """What render_instance_surfaces returns, device tensors: depth_maps / instance_maps: lists of (H_f, W_f) float32 /
+    uint8 (0 / 255 where no triangle fell); tri_maps: the same of int32 triangle ids (-1: none), or None;
+    tris_per_box / pixels_per_box (B,) int32: the triangles a box draws and the pixels it wins; scores: a
+    SurfaceScores when the call was given ground truth, else None."""
+    __slots__ = ('depth_maps', 'instance_maps', 'tri_maps', 'tris_per_box', 'pixels_per_box', 'scores')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    @property
+    def num_frames(self):
+        return len(self.depth_maps)
+
+    def frame(self, f):
+        return FrameSurface(self.depth_maps[f], self.instance_maps[f], None if self.tri_maps is None else self.tri_maps[f])
+
+
+def render_instance_surfaces(xyz_global_maps, box_frame, cam_p, frame_shapes, valid_mask=None, keep=None,
+                             max_edge_dz=SURFACE_MAX_EDGE_DZ, max_span_px=SURFACE_MAX_SPAN_PX, ground_truth=None,
+                             want_tri=False, device=None):
+    """The direct wrapper of mpsr_scene_surface_render / _resolve / _score: the boxes' xyz maps rendered as surfaces.
+
+    xyz_global_maps (B, Hm, Wm, 3) float32 CUDA tensor in the camera frame, Hm and Wm 2 or more: neighbouring samples
+    are joined into two triangles per grid cell.  box_frame, cam_p, frame_shapes, valid_mask ((B, Hm, Wm[, 1]) or
+    (B, Hm Wm)), keep and ground_truth as project_instance_points takes them.  max_edge_dz: a triangle whose three
+    depths span more than this many metres is not drawn (it would bridge a depth discontinuity; inf: never);
+    max_span_px: nor is one whose pixel extent exceeds this in either direction (1..1024).  want_tri: also return the
+    winning triangle id per pixel.  device: where to run (default: the maps' device).  Nothing is copied to the host.
+    -> SurfaceResult."""
+    import torch
+    if not torch.is_tensor(xyz_global_maps) or not xyz_global_maps.is_cuda:
+        raise _lib.MpsrError('expected xyz_global_maps on the GPU; monopsr_amd has no CPU path')
+    if xyz_global_maps.dim() != 4 or xyz_global_maps.shape[-1] != 3:
+        raise _lib.InvalidArgumentError('xyz_global_maps must be (B, Hm, Wm, 3), got %s' % (tuple(xyz_global_maps.shape),))
+    dev = xyz_global_maps.device if device is None else torch.device(device)
+    nb, mh, mw = (int(v) for v in xyz_global_maps.shape[:3])
+    if mh < 2 or mw < 2:
+        raise _lib.InvalidArgumentError('a map of %d x %d has no cell (2 x 2 or more)' % (mh, mw))
+    max_edge_dz, max_span_px = float(max_edge_dz), int(max_span_px)
+    if not max_edge_dz > 0.0:
+        raise _lib.InvalidArgumentError('max_edge_dz %r must be greater than 0 (inf: no limit)' % (max_edge_dz,))
+    if not 1 <= max_span_px <= 1024:
+        raise _lib.InvalidArgumentError('max_span_px %r is outside 1..1024' % (max_span_px,))
+    hw, bf, offs = _frame_tables(frame_shapes, box_frame, nb)
+    nf = len(hw)
+    if nb * (mh - 1) * (mw - 1) * 2 >= 2 ** 32:
+        raise _lib.InvalidArgumentError('%d boxes of %d x %d cells: the triangle id does not fit 32 bits'
+                                        % (nb, mh - 1, mw - 1))
+    total = int(offs[-1])
+    lib = _lib.lib()
+    i32, f32 = torch.int32, torch.float32
+    with torch.cuda.device(dev):
+        cam = _cameras(cam_p, nf, dev)
+        xyz_in = xyz_global_maps.detach().to(dev).to(f32).contiguous()
+        mask, keep_d = _mask_and_keep(valid_mask, keep, nb, mh * mw, dev)
+        scores = gt = None
+        if ground_truth is not None:
+            gt = _ground_truth_tables(ground_truth, hw, nb, dev)
+            scores = SurfaceScores(_empty((nb, 5), i32, dev), _empty((nb, 3), torch.float64, dev), gt[2])
+        depth = _empty((total,), f32, dev)
+        inst = _empty((total,), torch.uint8, dev)
+        tri = _empty((total,), i32, dev) if want_tri else None
+        if nf == 0 or nb == 0 or total == 0:  # nothing to launch: empty maps
+            depth.zero_()
+            inst.fill_(255)
+            if tri is not None:
+                tri.fill_(-1)
+            tris = torch.zeros((nb,), dtype=i32, device=dev)
+            pixels = torch.zeros((nb,), dtype=i32, device=dev)
+            if scores is not None:
+                scores.counts.zero_()
+                scores.sums.zero_()
+        else:
+            bf_d, hw_d, offs_d = torch.from_numpy(bf).to(dev), torch.from_numpy(hw).to(dev), torch.from_numpy(offs).to(dev)
+            ws = _empty((lib.mpsr_scene_surface_workspace_bytes(nf, total, nb, mh, mw),), torch.uint8, dev)
+            stream = _lib.stream()
+            host = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+            _lib.check(lib.mpsr_scene_surface_render(
+                _lib.ptr(xyz_in), _lib.ptr(mask), _lib.ptr(bf_d), host(bf), _lib.ptr(keep_d), _lib.ptr(cam),
+                _lib.ptr(hw_d), host(hw), _lib.ptr(offs_d), host(offs), nf, nb, mh, mw, max_edge_dz, max_span_px,
+                _lib.ptr(ws), ws.numel(), stream))
+            _lib.check(lib.mpsr_scene_surface_resolve(_lib.ptr(bf_d), host(bf), nf, total, nb, mh, mw, _lib.ptr(ws),
+                                                      ws.numel(), _lib.ptr(depth), _lib.ptr(inst), _lib.ptr(tri), stream))
+            if scores is None:  # without ground truth: the two per-box counts alone
+                counts, sums = _empty((nb, 5), i32, dev), _empty((nb, 3), torch.float64, dev)
+                gt_args = (None, None, None)
+                scratch = None
+            else:
+                counts, sums = scores.counts, scores.sums
+                tables = torch.from_numpy(np.asarray([[_lib.ptr(t) for t in gt[0]], [_lib.ptr(t) for t in gt[1]]],
+                                                     np.uint64).view(np.int64)).to(dev)
+                gt_args = (_lib.ptr(scores.box_gt_id), _lib.ptr(tables[0]), _lib.ptr(tables[1]))
+                scratch = _empty((lib.mpsr_scene_score_scratch_bytes(nf),), torch.uint8, dev)
+            _lib.check(lib.mpsr_scene_surface_score(
+                _lib.ptr(bf_d), host(bf), gt_args[0], gt_args[1], gt_args[2], _lib.ptr(hw_d), _lib.ptr(offs_d), nf,
+                total, nb, mh, mw, _lib.ptr(ws), ws.numel(), _lib.ptr(scratch), 0 if scratch is None else scratch.numel(),
+                _lib.ptr(counts), _lib.ptr(sums), stream))
+            tris, pixels = counts[:, 0], counts[:, 1]
+    view = lambda flat: [flat[int(offs[f]):int(offs[f + 1])].view(int(hw[f, 0]), int(hw[f, 1])) for f in range(nf)]
+    return SurfaceResult(depth_maps=view(depth), instance_maps=view(inst), tri_maps=None if tri is None else view(tri),
+                         tris_per_box=tris, pixels_per_box=pixels, scores=scores)
+
+
+SURFACE_DIRS = ('depth_surface', 'instances_surface')
+
+
+def surface_output_dirs(base):
+    """{'depth_surface' | 'instances_surface': <base>/<kind>}, created."""
+    dirs = {k: os.path.join(base, k) for k in SURFACE_DIRS}
+    for d in dirs.values():
+        os.makedirs(d, exist_ok=True)
+    return dirs
+
+
+def save_surface_frame(out_dirs, name, frame_surface):
+    """depth_surface/<name>.png and instances_surface/<name>.png of a FrameSurface, in the formats of save_frame's depth
+    and instance files.  -> the two paths."""
+    from monopsr_amd.datasets.kitti import depth_map_utils, instance_utils
+    paths = (os.path.join(out_dirs['depth_surface'], name + '.png'),
+             os.path.join(out_dirs['instances_surface'], name + '.png'))
+    depth = frame_surface.depth_map.detach().cpu().numpy()
+    # (a depth beyond the PNG's 16 bits, 256 m, has no place in the format: stored as 0, "no depth")
+    depth_map_utils.save_depth_map(paths[0], np.where(depth < 256.0, depth, np.float32(0.0)))
+    instance_utils.save_instance_image(paths[1], frame_surface.instance_map.detach().cpu().numpy())
+    return paths
+
+
+def save_empty_surface_frame(out_dirs, name, image_shape):
+    """The two files of a frame without a box: depth 0, instance 255 everywhere.  -> the two paths."""
+    from monopsr_amd.datasets.kitti import depth_map_utils, instance_utils
+    h, w = int(image_shape[0]), int(image_shape[1])
+    paths = (os.path.join(out_dirs['depth_surface'], name + '.png'),
+             os.path.join(out_dirs['instances_surface'], name + '.png'))
+    depth_map_utils.save_depth_map(paths[0], np.zeros((h, w), np.float32))
+    instance_utils.save_instance_image(paths[1], np.full((h, w), 255, np.uint8))
+    return paths
 
 
 # ---- files

@@ -5,8 +5,8 @@
 // mpsr_scene_project: one thread per point computes, in fp64 without contraction (rows3 and rint as in depth_fill.hip),
 //   pixel = rint(u0 / u2), rint(u1 / u2) of cam_p . [x y z 1], stores the pixel index of a kept point (-1 of a dropped
 //   one) and lowers the pixel's 64-bit key ((uint64) float_bits(z) << 32 | point index) with an unsigned atomicMin: the
-//   one atomic of this file.  A kept point has z > 0, so its float bits order as its value: the NEARER point wins, and
-//   on equal float32 depth the LOWER point index, in whatever order the waves run.  This is a true z-buffer.  The LiDAR
+//   one atomic of the point rendering.  A kept point has z > 0, so its float bits order as its value: the NEARER point
+//   wins, and on equal float32 depth the LOWER point index, in whatever order the waves run.  A true z-buffer.  The LiDAR
 //   projection of depth_fill.hip is not: it keeps the LAST duplicate of a pixel, near or far, because that is what the
 //   reference's fancy assignment does with a LiDAR cloud.
 // mpsr_scene_resolve: one thread per pixel turns the key into depth (the key's upper half, the winner's z bit for bit;
@@ -417,6 +417,36 @@ int check_box_frames(const char *who, const int *box_frame_host, int n_boxes, in
     return MPSR_OK;
 }
 
+// frame_hw and pixel_offset (host): positive sizes of at most 2^30 pixels, offsets that start at 0 and agree with them
+int check_frame_tables(const char *who, const int *frame_hw_host, const long long *pixel_offset_host, int n_frames)
+{
+    MPSR_REQUIRE(pixel_offset_host[0] == 0, "%s: pixel_offset[0] = %lld, expected 0", who, pixel_offset_host[0]);
+    for (int f = 0; f < n_frames; ++f) {
+        const int h = frame_hw_host[2 * f], w = frame_hw_host[2 * f + 1];
+        MPSR_REQUIRE(h > 0 && w > 0 && (long long)h * w <= (1LL << 30), "%s: frame %d is %d x %d", who, f, h, w);
+        MPSR_REQUIRE(pixel_offset_host[f + 1] - pixel_offset_host[f] == (long long)h * w,
+                     "%s: pixel_offset of frame %d spans %lld pixels, its image has %lld", who, f,
+                     pixel_offset_host[f + 1] - pixel_offset_host[f], (long long)h * w);
+    }
+    return MPSR_OK;
+}
+
+// hist (n_frames, 256) int32 = the value counts of the ground-truth instance images: zeroed, then hist_kernel
+int launch_hist(const unsigned char *const *gt_instance, const long long *pixel_offset, int n_frames,
+                long long total_pixels, int *hist, hipStream_t s)
+{
+    MPSR_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)n_frames * 256 * sizeof(int), s));
+    // workgroups per frame: one per 64 KiB of an average frame (a frame of any size is walked with the grid's stride)
+    const long long per_frame = (total_pixels + n_frames - 1) / n_frames;
+    const unsigned gx = (unsigned)std::min<long long>(std::max<long long>((per_frame + 65535) / 65536, 1), 64);
+    for (int f0 = 0; f0 < n_frames; f0 += 65535) {  // (gridDim.y holds 65535)
+        const int nf = std::min(n_frames - f0, 65535);
+        hipLaunchKernelGGL(hist_kernel, dim3(gx, nf), dim3(kThreads), 0, s, gt_instance + f0, pixel_offset + f0,
+                           hist + 256 * (size_t)f0);
+    }
+    return MPSR_OK;
+}
+
 unsigned grid_for(long long n) { return (unsigned)std::min<long long>((n + kThreads - 1) / kThreads, 1 << 16); }
 
 }  // namespace
@@ -442,14 +472,8 @@ extern "C" int mpsr_scene_project(const float *xyz_global, const float *valid_ma
     MPSR_REQUIRE(xyz_global && box_frame && box_frame_host, "scene_project: points or box_frame is null");
     MPSR_REQUIRE(cam_p && frame_hw && frame_hw_host && pixel_offset && pixel_offset_host,
                  "scene_project: cameras, frame sizes or pixel offsets are null");
-    MPSR_REQUIRE(pixel_offset_host[0] == 0, "scene_project: pixel_offset[0] = %lld, expected 0", pixel_offset_host[0]);
-    for (int f = 0; f < n_frames; ++f) {
-        const int h = frame_hw_host[2 * f], w = frame_hw_host[2 * f + 1];
-        MPSR_REQUIRE(h > 0 && w > 0 && (long long)h * w <= (1LL << 30), "scene_project: frame %d is %d x %d", f, h, w);
-        MPSR_REQUIRE(pixel_offset_host[f + 1] - pixel_offset_host[f] == (long long)h * w,
-                     "scene_project: pixel_offset of frame %d spans %lld pixels, its image has %lld", f,
-                     pixel_offset_host[f + 1] - pixel_offset_host[f], (long long)h * w);
-    }
+    st = check_frame_tables("scene_project", frame_hw_host, pixel_offset_host, n_frames);
+    if (st) return st;
     const long long total_pixels = pixel_offset_host[n_frames];
     st = check_sizes("scene_project", n_frames, total_pixels, n_boxes, points_per_box, &empty);
     if (st) return st;
@@ -560,17 +584,458 @@ extern "C" int mpsr_scene_score(const float *xyz_global, const int *box_frame, c
     const int *pix = reinterpret_cast<const int *>(ws + L.pix);
     int *hist = static_cast<int *>(scratch);
     hipStream_t s = mpsr::as_stream(stream);
-    MPSR_CHECK_HIP(hipMemsetAsync(hist, 0, need, s));
-    // workgroups per frame: one per 64 KiB of an average frame (a frame of any size is walked with the grid's stride)
-    const long long per_frame = (total_pixels + n_frames - 1) / n_frames;
-    const unsigned gx = (unsigned)std::min<long long>(std::max<long long>((per_frame + 65535) / 65536, 1), 64);
-    for (int f0 = 0; f0 < n_frames; f0 += 65535) {  // (gridDim.y holds 65535)
-        const int nf = std::min(n_frames - f0, 65535);
-        hipLaunchKernelGGL(hist_kernel, dim3(gx, nf), dim3(kThreads), 0, s, gt_instance + f0, pixel_offset + f0,
-                           hist + 256 * (size_t)f0);
-    }
+    st = launch_hist(gt_instance, pixel_offset, n_frames, total_pixels, hist, s);
+    if (st) return st;
     hipLaunchKernelGGL(score_kernel, dim3(n_boxes), dim3(kThreads), 0, s, keys, pix, box_frame, box_gt_id, gt_depth,
                        gt_instance, pixel_offset, hist, points_per_box, counts, sums);
     MPSR_CHECK_LAUNCH("scene_score");
+    return MPSR_OK;
+}
+
+// ---- Surfaces: a box's (map_h, map_w) xyz map rendered as the triangles of its grid cells
+// through the same 64-bit z-buffer, next to the point rendering above and in a workspace of its own.
+// mpsr_scene_surface_render: surface_vertex_kernel, one thread per map point, snaps a valid vertex to fixed-point
+//   screen coordinates with 8 sub-pixel bits (the centre of pixel (col, row) is (256 col, 256 row), as a point's pixel
+//   is rint(u)); surface_triangle_kernel, one thread per triangle, walks the pixel centres of the triangle's extent
+//   with exact int64 edge functions and an ownership rule for centres on an edge, computes the perspective-correct
+//   depth in fp64 and lowers the pixel's key ((uint64) float_bits(depth) << 32 | triangle id) with the unsigned
+//   atomicMin.  Per box it counts the drawn triangles and takes the bounding rectangle of their clamped extents:
+//   integer atomics, one set per wave where the wave's triangles are of one box.
+// mpsr_scene_surface_resolve: keys -> depth, instance and (optionally) triangle id maps.
+// mpsr_scene_surface_score: hist_kernel, then one workgroup per box over the box's rectangle, row-major in slices of
+//   256 pixels, reduced as score_kernel reduces.
+
+namespace {
+
+constexpr int kSubPixel = 256;             // fixed-point units per pixel
+constexpr int kNoVertex = INT_MIN;         // X of an invalid vertex
+constexpr double kMaxScreen = 1048576.0;   // 2^20 pixels: |u / u2| of a valid vertex is below it
+constexpr int kMaxSpan = 1024;
+
+__device__ __forceinline__ int floor_div256(int v) { return v >> 8; }  // arithmetic shift: floor for v < 0 too
+__device__ __forceinline__ int ceil_div256(int v) { return -((-v) >> 8); }
+
+// does the directed edge with direction (dx, dy) own the pixel centres that lie exactly on it?
+__device__ __forceinline__ bool owns(long long dx, long long dy) { return dy > 0 || (dy == 0 && dx < 0); }
+
+// one thread per map point: vert[i] = (X, Y), X = kNoVertex for an invalid vertex; the first n_boxes threads also
+// reset the per-box tables (tris 0, an empty rectangle)
+__global__ void __launch_bounds__(kThreads) surface_vertex_kernel(const float *__restrict__ xyz,
+                                                                  const float *__restrict__ valid_mask,
+                                                                  const int *__restrict__ box_frame,
+                                                                  const int *__restrict__ box_keep,
+                                                                  const double *__restrict__ cam_p, long long n,
+                                                                  int points_per_box, int n_boxes,
+                                                                  int2 *__restrict__ vert, int *__restrict__ box_tris,
+                                                                  int *__restrict__ box_rect)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        if (i < n_boxes) {
+            box_tris[i] = 0;
+            box_rect[4 * i] = box_rect[4 * i + 1] = INT_MAX;      // min col, min row
+            box_rect[4 * i + 2] = box_rect[4 * i + 3] = INT_MIN;  // max col, max row
+        }
+        const int b = (int)(i / points_per_box);
+        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+        int2 v = make_int2(kNoVertex, 0);
+        const bool on = (box_keep == nullptr || box_keep[b] != 0) && (valid_mask == nullptr || valid_mask[i] > 0.0f) &&
+                        isfinite(x) && isfinite(y) && isfinite(z) && z > 0.0f;
+        if (on) {
+            double u[3];
+            rows3(cam_p + 12 * box_frame[b], (double)x, (double)y, (double)z, u);
+            const double c = u[0] / u[2], r = u[1] / u[2];
+            // NaN fails both range tests
+            if (u[2] > 0.0 && fabs(c) < kMaxScreen && fabs(r) < kMaxScreen)
+                v = make_int2((int)rint(c * (double)kSubPixel), (int)rint(r * (double)kSubPixel));
+        }
+        vert[i] = v;
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) surface_triangle_kernel(const float *__restrict__ xyz,
+                                                                    const int2 *__restrict__ vert,
+                                                                    const int *__restrict__ box_frame,
+                                                                    const int *__restrict__ frame_hw,
+                                                                    const long long *__restrict__ pixel_offset,
+                                                                    long long n_tris, int map_h, int map_w,
+                                                                    float max_edge_dz, int max_span_px,
+                                                                    unsigned long long *__restrict__ keys,
+                                                                    int *__restrict__ box_tris,
+                                                                    int *__restrict__ box_rect)
+{
+    const int cells_w = map_w - 1, cells_h = map_h - 1;
+    const long long points_per_box = (long long)map_h * map_w;
+    // every lane of a wave makes the same number of rounds, so that the wave can combine its per-box bookkeeping
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long first = (long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63);
+    for (long long t0 = first; t0 < n_tris; t0 += stride) {
+        const long long t = t0 + (threadIdx.x & 63);
+        const bool live = t < n_tris;
+        int b = -1, drawn = 0;
+        int lo_c = INT_MAX, lo_r = INT_MAX, hi_c = INT_MIN, hi_r = INT_MIN;  // the clamped extent, empty
+        if (live) {
+            const int k = (int)(t & 1);
+            const long long cell = t >> 1;
+            const int j = (int)(cell % cells_w);
+            const long long rest = cell / cells_w;
+            const int i = (int)(rest % cells_h);
+            b = (int)(rest / cells_h);
+            const long long v00 = (long long)b * points_per_box + (long long)i * map_w + j;
+            // k = 0: (v00, v01, v10); k = 1: (v11, v10, v01)
+            long long ia = k ? v00 + map_w + 1 : v00, ib = k ? v00 + map_w : v00 + 1, ic = k ? v00 + 1 : v00 + map_w;
+            int2 pa = vert[ia], pb = vert[ib], pc = vert[ic];
+            if (pa.x != kNoVertex && pb.x != kNoVertex && pc.x != kNoVertex) {
+                float za = xyz[3 * ia + 2], zb = xyz[3 * ib + 2], zc = xyz[3 * ic + 2];
+                const float dz = fmaxf(fmaxf(za, zb), zc) - fminf(fminf(za, zb), zc);
+                long long A = (long long)(pb.x - pa.x) * (pc.y - pa.y) - (long long)(pb.y - pa.y) * (pc.x - pa.x);
+                const int c0 = ceil_div256(min(min(pa.x, pb.x), pc.x)), c1 = floor_div256(max(max(pa.x, pb.x), pc.x));
+                const int r0 = ceil_div256(min(min(pa.y, pb.y), pc.y)), r1 = floor_div256(max(max(pa.y, pb.y), pc.y));
+                if (!(dz > max_edge_dz) && A != 0 && c1 - c0 + 1 <= max_span_px && r1 - r0 + 1 <= max_span_px) {
+                    drawn = 1;
+                    if (A < 0) {  // the other facing: swap the second and the third vertex
+                        const int2 p = pb;
+                        pb = pc;
+                        pc = p;
+                        const float zz = zb;
+                        zb = zc;
+                        zc = zz;
+                        A = -A;
+                    }
+                    const int f = box_frame[b];
+                    const int h = frame_hw[2 * f], w = frame_hw[2 * f + 1];
+                    const int cc0 = max(c0, 0), cc1 = min(c1, w - 1), rr0 = max(r0, 0), rr1 = min(r1, h - 1);
+                    if (cc0 <= cc1 && rr0 <= rr1) {
+                        lo_c = cc0, hi_c = cc1, lo_r = rr0, hi_r = rr1;
+                        unsigned long long *fkeys = keys + pixel_offset[f];
+                        const long long bcx = pc.x - pb.x, bcy = pc.y - pb.y, cax = pa.x - pc.x, cay = pa.y - pc.y;
+                        const long long abx = pb.x - pa.x, aby = pb.y - pa.y;
+                        const bool own0 = owns(bcx, bcy), own1 = owns(cax, cay), own2 = owns(abx, aby);
+                        const double wa = 1.0 / (double)za, wb = 1.0 / (double)zb, wc = 1.0 / (double)zc;
+                        for (int row = rr0; row <= rr1; ++row) {
+                            const long long sy = (long long)row * kSubPixel;
+                            for (int col = cc0; col <= cc1; ++col) {
+                                const long long sx = (long long)col * kSubPixel;
+                                const long long e0 = bcx * (sy - pb.y) - bcy * (sx - pb.x);
+                                const long long e1 = cax * (sy - pc.y) - cay * (sx - pc.x);
+                                const long long e2 = abx * (sy - pa.y) - aby * (sx - pa.x);
+                                if ((e0 > 0 || (e0 == 0 && own0)) && (e1 > 0 || (e1 == 0 && own1)) &&
+                                    (e2 > 0 || (e2 == 0 && own2))) {
+                                    const double q = ((double)e0 * wa + (double)e1 * wb) + (double)e2 * wc;
+                                    const float zf = (float)((double)A / q);
+                                    atomicMin(fkeys + (long long)row * w + col,
+                                              ((unsigned long long)__float_as_uint(zf) << 32) |
+                                                  (unsigned long long)(unsigned)t);
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        // bookkeeping: the wave's triangles are of one box almost always (a box has thousands)
+        const int b_first = __shfl(b, 0);  // (lane 0 is live whenever any lane is)
+        if (__all(!live || b == b_first)) {
+            for (int o = 32; o > 0; o >>= 1) {
+                drawn += __shfl_down(drawn, o);
+                lo_c = min(lo_c, __shfl_down(lo_c, o));
+                lo_r = min(lo_r, __shfl_down(lo_r, o));
+                hi_c = max(hi_c, __shfl_down(hi_c, o));
+                hi_r = max(hi_r, __shfl_down(hi_r, o));
+            }
+            if ((threadIdx.x & 63) != 0) drawn = 0;  // lane 0 speaks for the wave
+        }
+        if (drawn) {
+            atomicAdd(box_tris + b, drawn);
+            if (lo_c <= hi_c) {
+                atomicMin(box_rect + 4 * (long long)b, lo_c);
+                atomicMin(box_rect + 4 * (long long)b + 1, lo_r);
+                atomicMax(box_rect + 4 * (long long)b + 2, hi_c);
+                atomicMax(box_rect + 4 * (long long)b + 3, hi_r);
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) surface_resolve_kernel(const unsigned long long *__restrict__ keys,
+                                                                   long long total_pixels,
+                                                                   const int *__restrict__ box_frame,
+                                                                   const int *__restrict__ frame_box,
+                                                                   unsigned tris_per_box, float *__restrict__ depth,
+                                                                   unsigned char *__restrict__ instance,
+                                                                   int *__restrict__ tri)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total_pixels;
+         i += (long long)gridDim.x * blockDim.x) {
+        const unsigned long long key = keys[i];
+        float d = 0.0f;
+        unsigned char id = 255;
+        int t = -1;
+        if (key != kEmptyKey) {
+            d = __uint_as_float((unsigned)(key >> 32));
+            t = (int)(unsigned)key;
+            const int b = (int)((unsigned)key / tris_per_box);
+            id = (unsigned char)(b - frame_box[box_frame[b]]);
+        }
+        depth[i] = d;
+        instance[i] = id;
+        if (tri) tri[i] = t;
+    }
+}
+
+// one workgroup per box: counts[b][5] = tris, pred_px, inter_px, gt_px, depth_n and sums[b][3] = the sums of e, |e| and
+// e * e over the depth_n pixels, e = (double) rendered depth - (double) ground-truth depth.  The box's rectangle is
+// walked row-major in slices of 256 pixels.
+__global__ void __launch_bounds__(kThreads) surface_score_kernel(const unsigned long long *__restrict__ keys,
+                                                                 const int *__restrict__ box_tris,
+                                                                 const int *__restrict__ box_rect,
+                                                                 const int *__restrict__ box_frame,
+                                                                 const int *__restrict__ box_gt_id,
+                                                                 const float *const *__restrict__ gt_depth,
+                                                                 const unsigned char *const *__restrict__ gt_instance,
+                                                                 const int *__restrict__ frame_hw,
+                                                                 const long long *__restrict__ pixel_offset,
+                                                                 const int *__restrict__ hist, unsigned tris_per_box,
+                                                                 int *__restrict__ counts, double *__restrict__ sums)
+{
+    __shared__ int part[3][kWaves];
+    __shared__ double dpart[3][kWaves];
+    const int b = blockIdx.x, f = box_frame[b], g = box_gt_id ? box_gt_id[b] : -1;  // (null: no ground truth at all)
+    const bool has_gt = g >= 0 && g <= 254;
+    const unsigned long long *fkeys = keys + pixel_offset[f];
+    const unsigned char *inst = has_gt ? gt_instance[f] : nullptr;
+    const float *depth = has_gt ? gt_depth[f] : nullptr;
+    const int w = frame_hw[2 * f + 1];
+    const int c0 = box_rect[4 * (long long)b], r0 = box_rect[4 * (long long)b + 1];
+    const int c1 = box_rect[4 * (long long)b + 2], r1 = box_rect[4 * (long long)b + 3];
+    const long long rw = c0 <= c1 ? (long long)c1 - c0 + 1 : 0;
+    const long long area = r0 <= r1 ? rw * ((long long)r1 - r0 + 1) : 0;
+    int n[3] = {0, 0, 0};           // per wave: every lane holds its wave's counts
+    double s[3] = {0.0, 0.0, 0.0};  // per thread, in slice order
+    for (long long q0 = 0; q0 < area; q0 += kThreads) {
+        const long long q = q0 + threadIdx.x;
+        bool mine = false, inter = false, measured = false;
+        if (q < area) {
+            const long long at = (r0 + q / rw) * w + (c0 + q % rw);
+            const unsigned long long key = fkeys[at];
+            mine = key != kEmptyKey && (unsigned)key / tris_per_box == (unsigned)b;
+            inter = mine && has_gt && (int)inst[at] == g;
+            if (inter) {
+                const float d = depth[at];
+                if (isfinite(d) && d > 0.0f) {
+                    measured = true;
+                    const double e = (double)__uint_as_float((unsigned)(key >> 32)) - (double)d;
+                    s[0] += e;
+                    s[1] += fabs(e);
+                    s[2] += e * e;
+                }
+            }
+        }
+        n[0] += __popcll(__ballot(mine));
+        n[1] += __popcll(__ballot(inter));
+        n[2] += __popcll(__ballot(measured));
+    }
+    for (int k = 0; k < 3; ++k)
+        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_down(s[k], o);  // lane l += lane l + o: a fixed tree
+    if ((threadIdx.x & 63) == 0) {
+        for (int k = 0; k < 3; ++k) part[k][threadIdx.x >> 6] = n[k];
+        for (int k = 0; k < 3; ++k) dpart[k][threadIdx.x >> 6] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c[3] = {0, 0, 0};
+        double t[3] = {0.0, 0.0, 0.0};
+        for (int v = 0; v < kWaves; ++v) {  // in wave order
+            for (int k = 0; k < 3; ++k) c[k] += part[k][v];
+            for (int k = 0; k < 3; ++k) t[k] += dpart[k][v];
+        }
+        int *out = counts + 5 * (long long)b;
+        out[0] = box_tris[b];
+        out[1] = c[0];
+        out[2] = c[1];
+        out[3] = has_gt ? hist[256 * (long long)f + g] : 0;
+        out[4] = c[2];
+        for (int k = 0; k < 3; ++k) sums[3 * (long long)b + k] = t[k];
+    }
+}
+
+// workspace: [keys: one uint64 per pixel] [vert: one int2 per map point] [frame_box: n_frames + 1 ints]
+// [box_tris: n_boxes ints] [box_rect: n_boxes x 4 ints]
+struct SurfaceLayout {
+    size_t keys, vert, frame_box, box_tris, box_rect, total;
+};
+
+SurfaceLayout surface_layout(int n_frames, long long total_pixels, int n_boxes, int map_h, int map_w)
+{
+    SurfaceLayout L;
+    size_t o = 0;
+    L.keys = o;
+    o += mpsr::align_up((size_t)total_pixels * sizeof(unsigned long long), 256);
+    L.vert = o;
+    o += mpsr::align_up((size_t)n_boxes * map_h * map_w * sizeof(int2), 256);
+    L.frame_box = o;
+    o += mpsr::align_up(((size_t)n_frames + 1) * sizeof(int), 256);
+    L.box_tris = o;
+    o += mpsr::align_up((size_t)n_boxes * sizeof(int), 256);
+    L.box_rect = o;
+    o += mpsr::align_up((size_t)n_boxes * 4 * sizeof(int), 256);
+    L.total = o;
+    return L;
+}
+
+long long surface_tris(int n_boxes, int map_h, int map_w)
+{
+    return 2LL * n_boxes * ((long long)(map_h - 1) * (map_w - 1));  // (n_boxes and the cells each below 2^31)
+}
+
+unsigned tris_of_a_box(int map_h, int map_w) { return 2u * (unsigned)(map_h - 1) * (unsigned)(map_w - 1); }
+
+// the sizes every surface entry point takes; *empty: nothing to do
+int check_surface_sizes(const char *who, int n_frames, long long total_pixels, int n_boxes, int map_h, int map_w,
+                        bool *empty)
+{
+    MPSR_REQUIRE(map_h >= 2 && map_w >= 2 && (long long)map_h * map_w <= INT_MAX,
+                 "%s: a map of %d x %d has no cell (map_h and map_w must be 2 or more)", who, map_h, map_w);
+    int st = check_sizes(who, n_frames, total_pixels, n_boxes, 1, empty);
+    if (st) return st;
+    MPSR_REQUIRE(surface_tris(n_boxes, map_h, map_w) < (1LL << 32),
+                 "%s: %d boxes of %d x %d cells: the triangle id does not fit the key's 32 bits", who, n_boxes,
+                 map_h - 1, map_w - 1);
+    return MPSR_OK;
+}
+
+int check_surface_workspace(const char *who, const void *workspace, size_t workspace_bytes, const SurfaceLayout &L)
+{
+    if (!workspace || workspace_bytes < L.total)
+        return mpsr::fail(MPSR_ERR_WORKSPACE, "%s: workspace %zu bytes < %zu", who, workspace_bytes, L.total);
+    return MPSR_OK;
+}
+
+}  // namespace
+
+extern "C" size_t mpsr_scene_surface_workspace_bytes(int n_frames, long long total_pixels, int n_boxes, int map_h,
+                                                     int map_w)
+{
+    if (n_frames <= 0 || total_pixels <= 0 || n_boxes <= 0 || map_h < 2 || map_w < 2) return 0;
+    if ((long long)map_h * map_w > INT_MAX || total_pixels > (1LL << 40)) return 0;
+    if (surface_tris(n_boxes, map_h, map_w) >= (1LL << 32)) return 0;
+    return surface_layout(n_frames, total_pixels, n_boxes, map_h, map_w).total;
+}
+
+extern "C" int mpsr_scene_surface_render(const float *xyz_global, const float *valid_mask, const int *box_frame,
+                                         const int *box_frame_host, const int *box_keep, const double *cam_p,
+                                         const int *frame_hw, const int *frame_hw_host, const long long *pixel_offset,
+                                         const long long *pixel_offset_host, int n_frames, int n_boxes, int map_h,
+                                         int map_w, float max_edge_dz, int max_span_px, void *workspace,
+                                         size_t workspace_bytes, mpsr_stream_t stream)
+{
+    const char *who = "scene_surface_render";
+    bool empty;
+    int st = check_surface_sizes(who, n_frames, 0, n_boxes, map_h, map_w, &empty);
+    if (st) return st;
+    MPSR_REQUIRE(max_span_px >= 1 && max_span_px <= kMaxSpan, "%s: max_span_px %d is outside 1..%d", who, max_span_px,
+                 kMaxSpan);
+    MPSR_REQUIRE(max_edge_dz > 0.0f, "%s: max_edge_dz %g must be greater than 0 (+inf: no limit)", who,
+                 (double)max_edge_dz);  // NaN fails the comparison
+    if (empty) return MPSR_OK;
+    MPSR_REQUIRE(xyz_global && box_frame && box_frame_host, "%s: points or box_frame is null", who);
+    MPSR_REQUIRE(cam_p && frame_hw && frame_hw_host && pixel_offset && pixel_offset_host,
+                 "%s: cameras, frame sizes or pixel offsets are null", who);
+    st = check_frame_tables(who, frame_hw_host, pixel_offset_host, n_frames);
+    if (st) return st;
+    const long long total_pixels = pixel_offset_host[n_frames];
+    st = check_surface_sizes(who, n_frames, total_pixels, n_boxes, map_h, map_w, &empty);
+    if (st) return st;
+    st = check_box_frames(who, box_frame_host, n_boxes, n_frames, 0);
+    if (st) return st;
+    const SurfaceLayout L = surface_layout(n_frames, total_pixels, n_boxes, map_h, map_w);
+    st = check_surface_workspace(who, workspace, workspace_bytes, L);
+    if (st) return st;
+
+    char *ws = static_cast<char *>(workspace);
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws + L.keys);
+    int2 *vert = reinterpret_cast<int2 *>(ws + L.vert);
+    int *frame_box = reinterpret_cast<int *>(ws + L.frame_box);
+    int *box_tris = reinterpret_cast<int *>(ws + L.box_tris), *box_rect = reinterpret_cast<int *>(ws + L.box_rect);
+    hipStream_t s = mpsr::as_stream(stream);
+    MPSR_CHECK_HIP(hipMemsetAsync(keys, 0xff, (size_t)total_pixels * sizeof(unsigned long long), s));  // kEmptyKey
+    hipLaunchKernelGGL(frame_box_kernel, dim3((n_frames + 1 + kThreads - 1) / kThreads), dim3(kThreads), 0, s,
+                       box_frame, n_boxes, n_frames, frame_box);
+    const int points_per_box = map_h * map_w;
+    const long long n = (long long)n_boxes * points_per_box;  // n >= n_boxes: the vertex pass resets the box tables
+    hipLaunchKernelGGL(surface_vertex_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, xyz_global, valid_mask,
+                       box_frame, box_keep, cam_p, n, points_per_box, n_boxes, vert, box_tris, box_rect);
+    const long long n_tris = surface_tris(n_boxes, map_h, map_w);
+    hipLaunchKernelGGL(surface_triangle_kernel, dim3(grid_for(n_tris)), dim3(kThreads), 0, s, xyz_global, vert,
+                       box_frame, frame_hw, pixel_offset, n_tris, map_h, map_w, max_edge_dz, max_span_px, keys,
+                       box_tris, box_rect);
+    MPSR_CHECK_LAUNCH("scene_surface_render");
+    return MPSR_OK;
+}
+
+extern "C" int mpsr_scene_surface_resolve(const int *box_frame, const int *box_frame_host, int n_frames,
+                                          long long total_pixels, int n_boxes, int map_h, int map_w,
+                                          const void *workspace, size_t workspace_bytes, float *depth,
+                                          unsigned char *instance, int *tri, mpsr_stream_t stream)
+{
+    const char *who = "scene_surface_resolve";
+    bool empty;
+    int st = check_surface_sizes(who, n_frames, total_pixels, n_boxes, map_h, map_w, &empty);
+    if (st) return st;
+    if (empty || total_pixels == 0) return MPSR_OK;
+    MPSR_REQUIRE(box_frame && box_frame_host && depth && instance, "%s: box_frame or an output is null", who);
+    st = check_box_frames(who, box_frame_host, n_boxes, n_frames, MPSR_INSTANCE_MAX_BOXES);
+    if (st) return st;
+    const SurfaceLayout L = surface_layout(n_frames, total_pixels, n_boxes, map_h, map_w);
+    st = check_surface_workspace(who, workspace, workspace_bytes, L);
+    if (st) return st;
+    const char *ws = static_cast<const char *>(workspace);
+    hipLaunchKernelGGL(surface_resolve_kernel, dim3(grid_for(total_pixels)), dim3(kThreads), 0,
+                       mpsr::as_stream(stream), reinterpret_cast<const unsigned long long *>(ws + L.keys),
+                       total_pixels, box_frame, reinterpret_cast<const int *>(ws + L.frame_box),
+                       tris_of_a_box(map_h, map_w), depth, instance, tri);
+    MPSR_CHECK_LAUNCH("scene_surface_resolve");
+    return MPSR_OK;
+}
+
+extern "C" int mpsr_scene_surface_score(const int *box_frame, const int *box_frame_host, const int *box_gt_id,
+                                        const float *const *gt_depth, const unsigned char *const *gt_instance,
+                                        const int *frame_hw, const long long *pixel_offset, int n_frames,
+                                        long long total_pixels, int n_boxes, int map_h, int map_w,
+                                        const void *workspace, size_t workspace_bytes, void *scratch,
+                                        size_t scratch_bytes, int *counts, double *sums, mpsr_stream_t stream)
+{
+    const char *who = "scene_surface_score";
+    bool empty;
+    int st = check_surface_sizes(who, n_frames, total_pixels, n_boxes, map_h, map_w, &empty);
+    if (st) return st;
+    if (empty || total_pixels == 0) return MPSR_OK;
+    MPSR_REQUIRE(box_frame && box_frame_host && frame_hw && pixel_offset,
+                 "%s: box_frame, frame_hw or pixel_offset is null", who);
+    // without ground truth (all three null): tris and pred_px alone, every other count and sum 0, no scratch
+    const bool with_gt = box_gt_id || gt_depth || gt_instance;
+    MPSR_REQUIRE(!with_gt || (box_gt_id && gt_depth && gt_instance),
+                 "%s: box_gt_id or a ground-truth table is null (all three, or none)", who);
+    MPSR_REQUIRE(counts && sums, "%s: an output is null", who);
+    st = check_box_frames(who, box_frame_host, n_boxes, n_frames, 0);
+    if (st) return st;
+    const SurfaceLayout L = surface_layout(n_frames, total_pixels, n_boxes, map_h, map_w);
+    st = check_surface_workspace(who, workspace, workspace_bytes, L);
+    if (st) return st;
+    const size_t need = mpsr_scene_score_scratch_bytes(n_frames);
+    if (with_gt && (!scratch || scratch_bytes < need))
+        return mpsr::fail(MPSR_ERR_WORKSPACE, "%s: scratch %zu bytes < %zu", who, scratch_bytes, need);
+    const char *ws = static_cast<const char *>(workspace);
+    int *hist = static_cast<int *>(scratch);
+    hipStream_t s = mpsr::as_stream(stream);
+    if (with_gt) {
+        st = launch_hist(gt_instance, pixel_offset, n_frames, total_pixels, hist, s);
+        if (st) return st;
+    }
+    hipLaunchKernelGGL(surface_score_kernel, dim3(n_boxes), dim3(kThreads), 0, s,
+                       reinterpret_cast<const unsigned long long *>(ws + L.keys),
+                       reinterpret_cast<const int *>(ws + L.box_tris), reinterpret_cast<const int *>(ws + L.box_rect),
+                       box_frame, box_gt_id, gt_depth, gt_instance, frame_hw, pixel_offset, hist,
+                       tris_of_a_box(map_h, map_w), counts, sums);
+    MPSR_CHECK_LAUNCH("scene_surface_score");
     return MPSR_OK;
 }

@@ -8,7 +8,8 @@ Under --predictions-dir: kitti_predictions_3d/ (the label files), metrics/<split
 kitti_reports/<split>/<step>_<iou>.txt and evaluated_<split>.txt, which a later run reads to skip what is done.
 With --scene-metrics every checkpoint's reconstructed scenes are also scored against the LiDAR depth maps and the
 instance images (mask IoU, precisions, depth error: DESIGN.md section 7.8): six more lines per checkpoint and
-metrics/<split>/scene_metrics_<split>.csv.
+metrics/<split>/scene_metrics_<split>.csv.  --surface-metrics implies that and also renders the instance maps as
+surfaces and scores those: six more lines and metrics/<split>/surface_metrics_<split>.csv.
 """
 import argparse
 import sys
@@ -33,17 +34,19 @@ def build_parser():
     ap.add_argument('--low-iou', action='store_true', help='MIN_OVERLAP 0.5 / 0.25 / 0.25')
     ap.add_argument('--scene-metrics', action='store_true',
                     help='also score the reconstructed scenes against ground truth: mask IoU and depth error per box')
+    ap.add_argument('--surface-metrics', action='store_true',
+                    help='the scene metrics, and the same of the instance maps rendered as surfaces')
     return ap
 
 
 def format_result(result):
-    """The report of one checkpoint and a line of its four statistics per metric (the scene metrics, where the result
-    has them, in their own order after the others)."""
+    """The report of one checkpoint and a line of its four statistics per metric (the scene metrics and then the
+    surface metrics, where the result has them, in their own order after the others)."""
     lines = [result['report'] or '']
     for name, st in sorted(result.get('metric_stats', {}).items()):
         lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
             name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
-    for name, st in result.get('scene_stats', {}).items():
+    for name, st in list(result.get('scene_stats', {}).items()) + list(result.get('surface_stats', {}).items()):
         lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
             name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
     return ''.join(lines)
@@ -63,7 +66,7 @@ def main(argv=None):
     threshold = getattr(train_config, 'kitti_score_threshold', 0.1)
     ev = evaluator.Evaluator(model, dataset, score_threshold=threshold, predictions_base_dir=args.predictions_dir,
                              iou='low' if args.low_iou else 'standard', metric_stats=True,
-                             scene_metrics=args.scene_metrics)
+                             scene_metrics='surface' if args.surface_metrics else args.scene_metrics)
     if args.repeat:
         max_iterations = getattr(train_config, 'max_iterations', None)
         if max_iterations is None and args.max_idle is None:

@@ -4,10 +4,13 @@ core/scene_reconstruction.py).
 
     python -m monopsr_amd.experiments.run_inference CONFIG CHECKPOINT --mscnn-dir DIR --output-dir DIR
         [--data-split val|test] [--width-div N] [--no-scenes] [--min-score S] [--visible-only]
+        [--surfaces [--max-edge-dz M] [--max-span-px N]]
 
 Under --output-dir: kitti_predictions_3d/<split>/<threshold>/<step>/data/<name>.txt as run_evaluation writes them, and
 scenes/<split>/<step>/points/<name>.ply, depth/<name>.png, instances/<name>.png.  One network pass serves both: the
-scenes are written from the Evaluator's chunks through its chunk_hook.  Split 'test' reads <dataset_dir>/testing and has
+scenes are written from the Evaluator's chunks through its chunk_hook.  With --surfaces the instance maps are also
+rendered as surfaces: depth_surface/<name>.png and instances_surface/<name>.png beside the three,
+in the formats of depth/ and instances/.  Split 'test' reads <dataset_dir>/testing and has
 no labels; any other split reads the config's data_split_dir, and the AP report is printed when it has a label_2.
 """
 import argparse
@@ -30,6 +33,12 @@ def build_parser():
                     help='2-D detection score a box needs to enter the scene (default: the label files\' threshold)')
     ap.add_argument('--visible-only', action='store_true',
                     help='keep only the points that win their pixel (drop what another point hides)')
+    ap.add_argument('--surfaces', action='store_true',
+                    help='also render the instance maps as surfaces: depth_surface/ and instances_surface/')
+    ap.add_argument('--max-edge-dz', type=float, default=scene_reconstruction.SURFACE_MAX_EDGE_DZ,
+                    help='--surfaces: a triangle whose depths span more than this many metres is not drawn')
+    ap.add_argument('--max-span-px', type=int, default=scene_reconstruction.SURFACE_MAX_SPAN_PX,
+                    help='--surfaces: nor is a triangle that spans more than this many pixels')
     return ap
 
 
@@ -39,32 +48,43 @@ def scene_dir(output_dir, data_split, global_step):
 
 class SceneWriter(object):
     """An Evaluator chunk_hook: reconstruct_frames of every chunk, save_frame of every frame.  `base` is the directory
-    that takes points/, depth/ and instances/; names collects the frames written."""
+    that takes points/, depth/ and instances/; names collects the frames written.  surfaces: None, or the dict of
+    options reconstruct_frames takes: depth_surface/ and instances_surface/ are written as well."""
 
-    def __init__(self, model, base, min_score=None, visible_only=False):
+    def __init__(self, model, base, min_score=None, visible_only=False, surfaces=None):
         self.model, self.base, self.min_score, self.visible_only = model, base, min_score, bool(visible_only)
+        self.surfaces = surfaces
         self.names = []
-        self._dirs = None
+        self._dirs = self._surface_dirs = None
 
-    def __call__(self, rows, samples, outs):
+    def _make_dirs(self):
         if self._dirs is None:
             self._dirs = scene_reconstruction.scene_output_dirs(self.base)
-        scene = scene_reconstruction.reconstruct_frames(self.model, samples, outs, self.min_score, self.visible_only)
+            if self.surfaces is not None:
+                self._surface_dirs = scene_reconstruction.surface_output_dirs(self.base)
+
+    def __call__(self, rows, samples, outs):
+        self._make_dirs()
+        scene = scene_reconstruction.reconstruct_frames(self.model, samples, outs, self.min_score, self.visible_only,
+                                                        surfaces=self.surfaces)
         for f, s in enumerate(samples):
             scene_reconstruction.save_frame(self._dirs, s['sample_name'], scene.frame(f))
+            if self.surfaces is not None:
+                scene_reconstruction.save_surface_frame(self._surface_dirs, s['sample_name'], scene.surfaces.frame(f))
             self.names.append(s['sample_name'])
 
     def finish(self, dataset):
         """The frames of the split that keep no detection are no sample of the dataset: an empty scene for each, as the
         Evaluator writes an empty label file for them."""
         from monopsr_amd.datasets.kitti import depth_map_utils
-        if self._dirs is None:
-            self._dirs = scene_reconstruction.scene_output_dirs(self.base)
+        self._make_dirs()
         done = set(self.names)
         for name in dataset.split_sample_names:
             if name not in done:
                 shape = depth_map_utils.image_shape(os.path.join(dataset.rgb_image_dir, name + '.png'))
                 scene_reconstruction.save_empty_frame(self._dirs, name, shape)
+                if self.surfaces is not None:
+                    scene_reconstruction.save_empty_surface_frame(self._surface_dirs, name, shape)
                 self.names.append(name)
 
 
@@ -91,7 +111,8 @@ def main(argv=None):
     writer = None
     if not args.no_scenes:
         writer = SceneWriter(model, scene_dir(args.output_dir, dataset.data_split, step),
-                             ev.score_threshold if args.min_score is None else args.min_score, args.visible_only)
+                             ev.score_threshold if args.min_score is None else args.min_score, args.visible_only,
+                             dict(max_edge_dz=args.max_edge_dz, max_span_px=args.max_span_px) if args.surfaces else None)
         ev.chunk_hook = writer
     result = ev.run_once(step)
     if writer is not None:
