@@ -1135,6 +1135,41 @@ int mpsr_scene_surface_score(const int *box_frame, const int *box_frame_host, co
                              int n_boxes, int map_h, int map_w, const void *workspace, size_t workspace_bytes,
                              void *scratch, size_t scratch_bytes, int *counts, double *sums, mpsr_stream_t stream);
 
+/* ---- Fitting a centroid to its 2-D box (additive to ABI 13) ----
+ * The reference's inference-time projection alignment (core/instances/instance_metrics.py np_proj_error and
+ * scipy_proj_error*, datasets/kitti/instance_utils.py proj_points and get_exp_proj_uv_map).  Per box: local (h w, 3)
+ * float32 points in map order (point i at row i / w, column i % w), x = [xz_dist d, centroid_y cy, viewing_angle va],
+ * a 2-D box [y1, x1, y2, x2], cameras as mpsr_proj_err_norm_cams takes them (an index outside [0, n_cams) is never
+ * dereferenced), mask (b, h w) float32 or NULL.
+ * The objective, float32 products each rounded: r = R_y(va) p (r = p with rotate_view 0); g = r + (d sin va, cy,
+ * d cos va); valid = |r_x| + |r_y| + |r_z| > 0.1 and mask != 0; with cam0_shift g_x += -P[0,3] / P[0,0];
+ * (U, V, Wc) = P (g, 1); u = U / Wc, v = V / Wc; the expected grid is np.linspace's start + index * step over the box
+ * (rounded half to even with round_box_2d): from the first to the last pixel's top-left corner, or centre with
+ * use_pixel_centres.  err = sum over valid points of |u - eu| + |v - ev|, divided by their number; the sum is fp64 in
+ * a fixed order without atomics.  No valid point: err = NaN.  A valid point with Wc <= 0: err = +inf. */
+
+/* uv (b, 2, h w) float32 or NULL (0 at points that are not valid), valid (b, h w) uint8 or NULL, err (b) fp64.  A box
+ * whose camera index is out of range gets NaN uv, valid 0 and err NaN. */
+int mpsr_proj_points(const float *local, const float *x, const float *boxes_2d, const float *cam_p, int n_cams,
+                     const int *cam_index, const float *mask, float *uv, unsigned char *valid, double *err, int b,
+                     int h, int w, int rotate_view, int cam0_shift, int round_box_2d, int use_pixel_centres,
+                     mpsr_stream_t stream);
+
+/* Nelder-Mead on that objective over (d, cy) (n_fit 2) or (d, cy, va) (n_fit 3), one workgroup per box, h w <= 2304.
+ * SciPy's rule: vertices x0 and x0 with coordinate k times 1.05 (0.00025 where it is 0); reflection 1, expansion 2,
+ * contractions 0.5, shrink 0.5; vertices stably ordered by value; stop when max |x_i - x_best| <= xatol and
+ * max |f_i - f_best| <= fatol, or at max_iter iterations or evaluations (<= 0: 200 n_fit; an evaluation past the cap
+ * ends the iteration where it stands).  The simplex is fp64; the objective is taken at its float32 rounding; an
+ * evaluation without a valid point ranks as +inf.
+ * x (b, 3) float32 (va copied through with n_fit 2), err and err0 (b) fp64: the objective at x and at x0, the bits
+ * mpsr_proj_points returns there, err <= err0; iters, evals (b) int32 (SciPy's nit and nfev); status (b) int32: 0
+ * converged, 1 stopped at the cap, 2 no valid point at x0 or camera index out of range (x = x0, err = err0 = NaN,
+ * iters 0, evals 1 or, for the camera, 0). */
+int mpsr_proj_fit(const float *local, const float *x0, const float *boxes_2d, const float *cam_p, int n_cams,
+                  const int *cam_index, const float *mask, int b, int h, int w, int n_fit, int rotate_view,
+                  int cam0_shift, int round_box_2d, int use_pixel_centres, double xatol, double fatol, int max_iter,
+                  float *x, double *err, double *err0, int *iters, int *evals, int *status, mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -238,6 +238,10 @@ SIGNATURES = {
                                          c_f, c_f, c_f]),
     "mpsr_scene_surface_score": (c_i, [c_f, ctypes.c_void_p, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_longlong, c_i, c_i,
                                        c_i, c_f, c_sz, c_f, c_sz, c_f, c_f, c_f]),
+    "mpsr_proj_points": (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                               c_f]),
+    "mpsr_proj_fit": (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_double,
+                            ctypes.c_double, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
 }
 
 

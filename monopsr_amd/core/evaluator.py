@@ -36,6 +36,13 @@ takes their statistics with NAN_RULE_ENTRY (a box without overlap drops its own 
 result['scene_stats'], and with predictions_base_dir one line in metrics/<split>/scene_metrics_<split>.csv
 (evaluator_utils.save_scene_stats).  DESIGN.md section 7.8.
 
+centroid_fit: None, or a dict of instance_metrics.fit_centroids' options ({} for its defaults).  With it every chunk's
+predicted centroids are fitted to their 2-D boxes straight after build_batch: the label files,
+AP, the scene and surface metrics and the chunk_hook all see the fitted boxes, and result['centroid_fit'] holds the
+numbers of boxes that converged, stopped at the cap and were not fitted, and the mean projection error at the fit's
+start (the predicted centroid put on its viewing ray: not the unfitted scene's error) and at its end over the fitted
+ones.  The per-object metric table and the losses come from the 'val'-mode graph and are not affected.
+
 scene_metrics='surface' does what True does and also renders every chunk's maps as surfaces (DESIGN.md section 7.9:
 scene_reconstruction.render_instance_surfaces with its default max_edge_dz and max_span_px) and scores them against the
 same ground truth: result['surface_stats'] over scene_reconstruction.SURFACE_METRIC_NAMES, and with predictions_base_dir
@@ -65,6 +72,9 @@ METRIC_COLUMNS = ((constants.METRIC_EMD, 1), (constants.METRIC_CHAMFER, 1), (con
                   (constants.METRIC_CEN_Z_ERR, 1), (constants.METRIC_DIM_ERR, 3))
 METRIC_NAMES = tuple(name for name, _ in METRIC_COLUMNS)
 COLUMN_METRIC = tuple(k for k, (_, width) in enumerate(METRIC_COLUMNS) for _ in range(width))
+
+# what Evaluator(centroid_fit={...}) may hold: instance_metrics.fit_centroids' options
+_CENTROID_FIT_OPTIONS = ('fit_viewing_angle', 'use_pixel_centres', 'cam0_shift')
 
 
 def sweep_checkpoints(checkpoints, evaluated, run, ckpt_indices=None):
@@ -118,7 +128,7 @@ class Evaluator:
 
     def __init__(self, model, dataset, score_threshold=0.1, predictions_base_dir=None, batch_size=8,
                  project_3d_box=False, iou='standard', compute_metrics=True, compute_losses=True, metric_stats=False,
-                 skip_evaluated_checkpoints=True, scene_metrics=False, chunk_hook=None):
+                 skip_evaluated_checkpoints=True, scene_metrics=False, centroid_fit=None, chunk_hook=None):
         if iou not in kitti_eval.MIN_OVERLAP:
             raise ValueError('iou must be one of %s' % sorted(kitti_eval.MIN_OVERLAP))
         if int(batch_size) < 1:
@@ -131,7 +141,14 @@ class Evaluator:
                              "dataset, got %r" % (getattr(dataset, 'train_val_test', None),))
         if isinstance(scene_metrics, str) and scene_metrics != 'surface':
             raise ValueError("scene_metrics must be False, True or 'surface', got %r" % (scene_metrics,))
+        if centroid_fit is not None:
+            unknown = set(centroid_fit) - set(_CENTROID_FIT_OPTIONS)
+            if unknown:
+                raise ValueError('centroid_fit: unknown options %s' % sorted(unknown))
         self.model = model
+        # None, or a dict of instance_metrics.fit_centroids' options ({} for the defaults): every chunk's centroids are
+        # fitted to their 2-D boxes straight after build_batch, and everything below sees the fitted boxes
+        self.centroid_fit = None if centroid_fit is None else dict(centroid_fit)
         self.scene_metrics = bool(scene_metrics)
         self.surface_metrics = scene_metrics == 'surface'
         # after a run_once with scene_metrics='surface': (table (n,6) float32 in SURFACE_METRIC_NAMES order, counts
@@ -178,6 +195,7 @@ class Evaluator:
         loss_names, loss_sums = [], None
         table = []
         scene_parts, surface_parts = [], []
+        self._fits = []
         if with_losses or with_table:
             # the 'val'-mode graph of the same net: method by method, with the ground truth and the offsets
             from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
@@ -190,6 +208,10 @@ class Evaluator:
                 rows = np.arange(a, min(a + self.batch_size, ds.num_samples))
                 samples = ds.get_sample_dict(position[rows], epoch=0)
                 outs = model.build_batch(samples)
+                if self.centroid_fit is not None:
+                    from monopsr_amd.core.instances import instance_metrics
+                    outs, fit = instance_metrics.fit_centroids(model, samples, outs, **self.centroid_fit)
+                    self._fits.append(fit)
                 if self.chunk_hook is not None:
                     self.chunk_hook(rows, samples, outs)
                 if self.scene_metrics:
@@ -283,6 +305,15 @@ class Evaluator:
         result = dict(num_frames=len(ds.split_sample_names), num_frames_with_detections=len(per_frame),
                       num_detections=int(len(rows)), num_predictions=int(b3.shape[0]), global_step=global_step,
                       kitti=None, report=None, metrics={}, losses={})
+        if self.centroid_fit is not None:
+            from monopsr_amd.core.instances import instance_metrics
+            c = instance_metrics.fit_summary(self._fits).cpu().numpy()  # reduced on the card, one copy
+            self._fits = []
+            fitted = c[0] + c[1]
+            result['centroid_fit'] = dict(
+                converged=int(c[0]), capped=int(c[1]), not_fitted=int(c[2]),
+                mean_err0=float(c[3] / fitted) if fitted else float('nan'),
+                mean_err=float(c[4] / fitted) if fitted else float('nan'))
         if ds.train_val_test == 'val' and (self.compute_metrics or loss_names or table is not None):
             # one copy for all tables
             names = [constants.METRIC_EMD, constants.METRIC_CHAMFER] + list(loss_names)
@@ -429,6 +460,21 @@ class Evaluator:
                               max_iterations, eval_wait_interval, max_idle_seconds)
 
 
+def centroid_fit_options(ap, args):
+    """The Evaluator's centroid_fit of a command line's --fit-centroids and --fit-viewing-angle (None without
+    --fit-centroids); run_inference and run_evaluation share it."""
+    if args.fit_viewing_angle and not args.fit_centroids:
+        ap.error('--fit-viewing-angle requires --fit-centroids')
+    return dict(fit_viewing_angle=args.fit_viewing_angle) if args.fit_centroids else None
+
+
+def format_centroid_fit(c):
+    """result['centroid_fit'] as one line.  The first error is the objective at the fit's start, the predicted centroid
+    moved onto its viewing ray (fit_centroids' x0): not the error of the unfitted scene."""
+    return '%d converged, %d at the cap, %d not fitted; mean projection error %.4f (at the start) -> %.4f px' % (
+        c['converged'], c['capped'], c['not_fitted'], c['mean_err0'], c['mean_err'])
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description='KITTI AP of one checkpoint on a split, with MSCNN 2-D detections')
     ap.add_argument('config', help='experiment config (yaml)')
@@ -438,6 +484,8 @@ def build_parser():
     ap.add_argument('--low-iou', action='store_true', help='MIN_OVERLAP 0.5 / 0.25 / 0.25')
     ap.add_argument('--predictions-dir', default=None, help='also write the KITTI label files under this directory')
     ap.add_argument('--width-div', type=int, default=1, help='channel divisor of the net the checkpoint was saved from')
+    ap.add_argument('--fit-centroids', action='store_true',
+                    help='fit every predicted centroid to its 2-D box before scoring (DESIGN.md section 7.10)')
     return ap
 
 
@@ -453,9 +501,11 @@ def main(argv=None):
     model = MonoPSRModel(cfg.model_config, cfg.dataset_config, None, 'test')
     threshold = getattr(cfg.get('train_config'), 'kitti_score_threshold', 0.1)
     ev = Evaluator(model, dataset, score_threshold=threshold, predictions_base_dir=args.predictions_dir,
-                   iou='low' if args.low_iou else 'standard')
+                   iou='low' if args.low_iou else 'standard', centroid_fit={} if args.fit_centroids else None)
     result = ev.run_checkpoint_once(args.checkpoint, width_div=args.width_div)
     sys.stdout.write(result['report'])
+    for key, value in sorted(result.get('centroid_fit', {}).items()):
+        sys.stdout.write('centroid_fit %s: %s\n' % (key, value))
     for key, value in sorted(result['metrics'].items()) + sorted(result['losses'].items()):
         sys.stdout.write('%s: %.6f\n' % (key, value))
     return 0

@@ -84,4 +84,14 @@ __device__ __forceinline__ int fdiv(int n, const FastDiv &f)
     return f.m == 0 ? n : (int)(__umulhi((unsigned)n, f.m) >> f.s);
 }
 
+// Per-box cameras (the convention of mpsr_heads_fwd_cams, network.hip): cam_p (n_cams,12), cam_index (b) picks each box's
+// matrix, nullptr = every box reads the first.  An index outside [0, n_cams) is never dereferenced: nullptr comes back and
+// the caller fills that box's camera-dependent outputs with NaN.
+__device__ __forceinline__ const float *cam_of(const float *cam_p, const int *cam_index, int n_cams, int b)
+{
+    if (!cam_index) return cam_p;
+    const int i = cam_index[b];
+    return (i >= 0 && i < n_cams) ? cam_p + 12 * i : nullptr;
+}
+
 }  // namespace mpsr

@@ -230,6 +230,84 @@ def format_boxes(lwh, view_angs, alpha_bins, alpha_regs, centroids, boxes_2d, sc
     return b3, b2
 
 
+# ------------------------------------------------------------------------------ placing a cloud on its viewing ray
+
+def get_exp_proj_uv_map(boxes_2d, roi_size, round_box_2d=False, use_pixel_centres=False):
+    """instance_utils.py:684-735 for N boxes: (N,4) [y1,x1,y2,x2] -> (N,H,W,2) expected [u, v] of an evenly spaced
+    roi_size grid over each box, on the boxes' device: the pixels' top-left corners, or their centres with
+    use_pixel_centres.  np.linspace's start + index * step in float32, the arithmetic of mpsr_proj_points."""
+    h, w = int(roi_size[0]), int(roi_size[1])
+    b = _f32(boxes_2d).reshape(-1, 4)
+    if round_box_2d:
+        b = torch.round(b)  # half to even, as np.round
+    v1, u1, v2, u2 = b[:, 0:1], b[:, 1:2], b[:, 2:3], b[:, 3:4]
+    su, sv = (u2 - u1) / w, (v2 - v1) / h
+    if use_pixel_centres:
+        u0, ue, v0, ve = u1 + su / 2.0, u2 - su / 2.0, v1 + sv / 2.0, v2 - sv / 2.0
+    else:
+        u0, ue, v0, ve = u1, u2 - su, v1, v2 - sv
+    du = (ue - u0) / (w - 1) if w > 1 else torch.zeros_like(u0)
+    dv = (ve - v0) / (h - 1) if h > 1 else torch.zeros_like(v0)
+    grid_u = u0 + du * torch.arange(w, dtype=torch.float32, device=b.device)[None]
+    grid_v = v0 + dv * torch.arange(h, dtype=torch.float32, device=b.device)[None]
+    return torch.stack([grid_u[:, None, :].expand(-1, h, w), grid_v[:, :, None].expand(-1, h, w)], 3).contiguous()
+
+
+def _placement(xz_dist, centroid_y, viewing_angle, n):
+    """-> x (n,3) float32 [xz_dist, centroid_y, viewing_angle]"""
+    cols = [_f32(torch.as_tensor(t)).reshape(-1) for t in (xz_dist, centroid_y, viewing_angle)]
+    if any(c.numel() != n for c in cols):
+        raise _lib.InvalidArgumentError("xz_dist, centroid_y and viewing_angle must have one entry per box (%d)" % n)
+    return torch.stack(cols, 1).contiguous()
+
+
+def proj_points_err(x, inst_points_local, boxes_2d, cam_p, roi_size, valid_mask=None, rotate_view=True,
+                    cam0_shift=True, round_box_2d=False, use_pixel_centres=False, cam_index=None, want_points=True):
+    """The direct wrapper of mpsr_proj_points: x (N,3) [xz_dist, centroid_y, viewing_angle], local points (N,P,3) in map
+    order, boxes (N,4) -> (points_uv (N,2,P) float32, valid (N,P) bool, err (N,) float64); the first two None without
+    want_points."""
+    n = int(inst_points_local.shape[0])
+    h, w = int(roi_size[0]), int(roi_size[1])
+    if inst_points_local.numel() != n * h * w * 3:
+        raise _lib.InvalidArgumentError("inst_points_local %s does not hold %d x %d points per box"
+                                        % (tuple(inst_points_local.shape), h, w))
+    local = _f32(inst_points_local).reshape(n, h * w, 3)
+    if tuple(x.shape) != (n, 3) or tuple(boxes_2d.shape) != (n, 4):
+        raise _lib.InvalidArgumentError("x must be (N,3) and boxes_2d (N,4)")
+    if valid_mask is not None and valid_mask.numel() != n * h * w:
+        raise _lib.InvalidArgumentError("valid_mask must hold one entry per point")
+    _check_cams(cam_p, cam_index, n)
+    dev = local.device
+    x, boxes, cam, idx = _f32(x), _f32(boxes_2d), _f32(cam_p).reshape(-1), _cam_index(cam_index)
+    mask = None if valid_mask is None else _f32(valid_mask).reshape(n, h * w)
+    uv = torch.empty((n, 2, h * w), dtype=torch.float32, device=dev) if want_points else None
+    valid = torch.empty((n, h * w), dtype=torch.uint8, device=dev) if want_points else None
+    err = torch.empty((n,), dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().mpsr_proj_points(
+        _lib.ptr(local), _lib.ptr(x), _lib.ptr(boxes), _lib.ptr(cam), cam.numel() // 12, _lib.ptr(idx), _lib.ptr(mask),
+        _lib.ptr(uv), _lib.ptr(valid), _lib.ptr(err), n, h, w, int(bool(rotate_view)), int(bool(cam0_shift)),
+        int(bool(round_box_2d)), int(bool(use_pixel_centres)), _lib.stream()))
+    return uv, (valid.bool() if want_points else None), err
+
+
+def proj_points(xz_dist, centroid_y, viewing_angle, inst_points_local, cam_p, rotate_view=True, cam0_shift=True,
+                cam_index=None):
+    """instance_utils.py:791-838, batched over boxes: (N,) distances along the viewing ray, heights and viewing angles,
+    (N,P,3) local points -> (points_uv (N,2,P) float32, valid (N,P) bool).  Every cloud is rotated by its viewing angle
+    (unless rotate_view is False), moved to (d sin va, cy, d cos va), shifted into the cam0 frame (the reference always
+    does; cam0_shift=False projects it where it stands, as the rest of this package does) and projected with cam_p:
+    one (3,4) matrix, or (n_cams,3,4) with cam_index (N).  A point is valid where the sum of its rotated |x|, |y|, |z|
+    exceeds 0.1; uv is 0 elsewhere."""
+    n = int(inst_points_local.shape[0])
+    npts = int(np.prod(inst_points_local.shape[1:-1]))
+    dev = inst_points_local.device
+    x = _placement(xz_dist, centroid_y, viewing_angle, n).to(dev)
+    boxes = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+    uv, valid, _ = proj_points_err(x, inst_points_local, boxes, cam_p, (1, npts), rotate_view=rotate_view,
+                                   cam0_shift=cam0_shift, cam_index=cam_index)
+    return uv, valid
+
+
 # ---------------------------------------------------------------------------------------------- training ground truth
 
 # gen_instance_masks.py: the classes that get an instance id, and each class's inflation of (x, y, z, l, w, h, ry)

@@ -36,6 +36,10 @@ def build_parser():
                     help='also score the reconstructed scenes against ground truth: mask IoU and depth error per box')
     ap.add_argument('--surface-metrics', action='store_true',
                     help='the scene metrics, and the same of the instance maps rendered as surfaces')
+    ap.add_argument('--fit-centroids', action='store_true',
+                    help='fit every predicted centroid to its 2-D box before scoring (DESIGN.md section 7.10)')
+    ap.add_argument('--fit-viewing-angle', action='store_true',
+                    help='--fit-centroids: fit the viewing angle as well')
     return ap
 
 
@@ -49,11 +53,15 @@ def format_result(result):
     for name, st in list(result.get('scene_stats', {}).items()) + list(result.get('surface_stats', {}).items()):
         lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
             name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
+    if 'centroid_fit' in result:
+        lines.append('centroid fit: %s\n' % evaluator.format_centroid_fit(result['centroid_fit']))
     return ''.join(lines)
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    centroid_fit = evaluator.centroid_fit_options(ap, args)
     from monopsr_amd.core import config_utils
     from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
     from monopsr_amd.datasets.kitti.kitti_dataset import KittiDataset
@@ -66,7 +74,8 @@ def main(argv=None):
     threshold = getattr(train_config, 'kitti_score_threshold', 0.1)
     ev = evaluator.Evaluator(model, dataset, score_threshold=threshold, predictions_base_dir=args.predictions_dir,
                              iou='low' if args.low_iou else 'standard', metric_stats=True,
-                             scene_metrics='surface' if args.surface_metrics else args.scene_metrics)
+                             scene_metrics='surface' if args.surface_metrics else args.scene_metrics,
+                             centroid_fit=centroid_fit)
     if args.repeat:
         max_iterations = getattr(train_config, 'max_iterations', None)
         if max_iterations is None and args.max_idle is None:

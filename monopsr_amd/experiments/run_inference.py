@@ -39,6 +39,10 @@ def build_parser():
                     help='--surfaces: a triangle whose depths span more than this many metres is not drawn')
     ap.add_argument('--max-span-px', type=int, default=scene_reconstruction.SURFACE_MAX_SPAN_PX,
                     help='--surfaces: nor is a triangle that spans more than this many pixels')
+    ap.add_argument('--fit-centroids', action='store_true',
+                    help='fit every predicted centroid to its 2-D box first: labels and scenes hold the fitted boxes')
+    ap.add_argument('--fit-viewing-angle', action='store_true',
+                    help='--fit-centroids: fit the viewing angle as well')
     return ap
 
 
@@ -89,7 +93,9 @@ class SceneWriter(object):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    centroid_fit = evaluator.centroid_fit_options(ap, args)
     from monopsr_amd.core import config_utils
     from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
     from monopsr_amd.datasets.kitti.kitti_dataset import KittiDataset
@@ -106,7 +112,8 @@ def main(argv=None):
     dataset = KittiDataset(dcfg, 'test', mscnn_label_dir=args.mscnn_dir)
     model = MonoPSRModel(cfg.model_config, dcfg, None, 'test')
     threshold = getattr(cfg.get('train_config'), 'kitti_score_threshold', 0.1)
-    ev = evaluator.Evaluator(model, dataset, score_threshold=threshold, predictions_base_dir=args.output_dir)
+    ev = evaluator.Evaluator(model, dataset, score_threshold=threshold, predictions_base_dir=args.output_dir,
+                             centroid_fit=centroid_fit)
     step = ev.restore_checkpoint(args.checkpoint, width_div=args.width_div)
     writer = None
     if not args.no_scenes:
@@ -124,6 +131,8 @@ def main(argv=None):
         result['kitti_predictions_dir']))
     if writer is not None:
         sys.stdout.write('%d scenes: %s\n' % (len(writer.names), writer.base))
+    if 'centroid_fit' in result:
+        sys.stdout.write('centroid fit: %s\n' % evaluator.format_centroid_fit(result['centroid_fit']))
     return 0
 
 
