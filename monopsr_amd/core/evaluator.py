@@ -335,27 +335,19 @@ class Evaluator:
         if 'metric_stats' in result and self.predictions_base_dir is not None:
             result['metrics_csv'] = evaluator_utils.save_metric_stats(self.predictions_base_dir, ds.data_split,
                                                                       global_step, result['metric_stats'])
-        if scene is not None:
-            from monopsr_amd.core.scene_reconstruction import SCENE_METRIC_NAMES
-            self.scene_table = scene + (frame,)
-            stats = evaluator_utils.metric_stats(scene[0], frame, range(len(SCENE_METRIC_NAMES)),
-                                                 len(SCENE_METRIC_NAMES), ds.num_samples,
-                                                 evaluator_utils.NAN_RULE_ENTRY)
-            result['scene_stats'] = evaluator_utils.metric_stats_dict(SCENE_METRIC_NAMES, stats.cpu().numpy())
+        from monopsr_amd.core.scene_reconstruction import SCENE_METRIC_NAMES, SURFACE_METRIC_NAMES
+        for kind, metric_names, parts, save in (
+                ('scene', SCENE_METRIC_NAMES, scene, evaluator_utils.save_scene_stats),
+                ('surface', SURFACE_METRIC_NAMES, surface, evaluator_utils.save_surface_stats)):
+            if parts is None:
+                continue
+            setattr(self, kind + '_table', parts + (frame,))
+            stats = evaluator_utils.metric_stats(parts[0], frame, range(len(metric_names)), len(metric_names),
+                                                 ds.num_samples, evaluator_utils.NAN_RULE_ENTRY)
+            result[kind + '_stats'] = evaluator_utils.metric_stats_dict(metric_names, stats.cpu().numpy())
             if self.predictions_base_dir is not None:
-                result['scene_metrics_csv'] = evaluator_utils.save_scene_stats(
-                    self.predictions_base_dir, ds.data_split, global_step, SCENE_METRIC_NAMES, result['scene_stats'])
-        if surface is not None:
-            from monopsr_amd.core.scene_reconstruction import SURFACE_METRIC_NAMES
-            self.surface_table = surface + (frame,)
-            stats = evaluator_utils.metric_stats(surface[0], frame, range(len(SURFACE_METRIC_NAMES)),
-                                                 len(SURFACE_METRIC_NAMES), ds.num_samples,
-                                                 evaluator_utils.NAN_RULE_ENTRY)
-            result['surface_stats'] = evaluator_utils.metric_stats_dict(SURFACE_METRIC_NAMES, stats.cpu().numpy())
-            if self.predictions_base_dir is not None:
-                result['surface_metrics_csv'] = evaluator_utils.save_surface_stats(
-                    self.predictions_base_dir, ds.data_split, global_step, SURFACE_METRIC_NAMES,
-                    result['surface_stats'])
+                result[kind + '_metrics_csv'] = save(self.predictions_base_dir, ds.data_split, global_step,
+                                                     metric_names, result[kind + '_stats'])
         if self.predictions_base_dir is not None:
             out_dir = evaluator_utils.kitti_output_dir(self.predictions_base_dir, ds.data_split, self.score_threshold,
                                                        global_step)

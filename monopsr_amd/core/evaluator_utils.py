@@ -174,15 +174,12 @@ def save_metric_stats(predictions_base_dir, data_split, global_step, metric_stat
     return paths
 
 
-def save_scene_stats(predictions_base_dir, data_split, global_step, names, scene_stats):
-    """Appends one line per call to <predictions_base_dir>/metrics/<split>/scene_metrics_<split>.csv: the step, then
-    count, mean and std of every metric of `names`, in that order; into an empty file first a header ('step', then
-    <name>_count, <name>_mean, <name>_std with the 'scene_' prefix left off).  The step is right-justified to 8, the
-    other fields to 22; counts as integers, means and stds as '{:.5f}'.  Returns the path."""
+def _save_prefixed_stats(prefix, predictions_base_dir, data_split, global_step, names, stats):
+    """save_scene_stats ('scene_') and save_surface_stats ('surface_'): <prefix>metrics_<split>.csv."""
     out_dir = metrics_dir(predictions_base_dir, data_split)
     os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, 'scene_metrics_%s.csv' % data_split)
-    short = [n[len('scene_'):] if n.startswith('scene_') else n for n in names]
+    path = os.path.join(out_dir, '%smetrics_%s.csv' % (prefix, data_split))
+    short = [n[len(prefix):] if n.startswith(prefix) else n for n in names]
     with open(path, 'a', newline='') as f:
         writer = csv.writer(f, delimiter=',')
         if f.tell() == 0:
@@ -190,11 +187,19 @@ def save_scene_stats(predictions_base_dir, data_split, global_step, names, scene
                                                  for stat in ('count', 'mean', 'std')])
         row = ['{}'.format(global_step).rjust(8)]
         for n in names:
-            st = scene_stats[n]
+            st = stats[n]
             row += ['{:d}'.format(int(st['count'])).rjust(22), '{:.5f}'.format(st['mean']).rjust(22),
                     '{:.5f}'.format(st['std']).rjust(22)]
         writer.writerow(row)
     return path
+
+
+def save_scene_stats(predictions_base_dir, data_split, global_step, names, scene_stats):
+    """Appends one line per call to <predictions_base_dir>/metrics/<split>/scene_metrics_<split>.csv: the step, then
+    count, mean and std of every metric of `names`, in that order; into an empty file first a header ('step', then
+    <name>_count, <name>_mean, <name>_std with the 'scene_' prefix left off).  The step is right-justified to 8, the
+    other fields to 22; counts as integers, means and stds as '{:.5f}'.  Returns the path."""
+    return _save_prefixed_stats('scene_', predictions_base_dir, data_split, global_step, names, scene_stats)
 
 
 def save_surface_stats(predictions_base_dir, data_split, global_step, names, surface_stats):
@@ -203,22 +208,7 @@ def save_surface_stats(predictions_base_dir, data_split, global_step, names, sur
     file first a header ('step', then <name>_count, <name>_mean, <name>_std with the 'surface_' prefix left off).  The
     step is right-justified to 8, the other fields to 22; counts as integers, means and stds as '{:.5f}'.  Returns the
     path."""
-    out_dir = metrics_dir(predictions_base_dir, data_split)
-    os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, 'surface_metrics_%s.csv' % data_split)
-    short = [n[len('surface_'):] if n.startswith('surface_') else n for n in names]
-    with open(path, 'a', newline='') as f:
-        writer = csv.writer(f, delimiter=',')
-        if f.tell() == 0:
-            writer.writerow(['step'.rjust(8)] + [('%s_%s' % (n, stat)).rjust(22) for n in short
-                                                 for stat in ('count', 'mean', 'std')])
-        row = ['{}'.format(global_step).rjust(8)]
-        for n in names:
-            st = surface_stats[n]
-            row += ['{:d}'.format(int(st['count'])).rjust(22), '{:.5f}'.format(st['mean']).rjust(22),
-                    '{:.5f}'.format(st['std']).rjust(22)]
-        writer.writerow(row)
-    return path
+    return _save_prefixed_stats('surface_', predictions_base_dir, data_split, global_step, names, surface_stats)
 
 
 def kitti_label_rows(box_3d, box_2d, classes, score_threshold, image_boxes=None, keep=None):

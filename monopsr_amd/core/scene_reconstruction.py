@@ -75,6 +75,23 @@ class FrameScene(object):
             setattr(self, k, kw[k])
 
 
+def _metric_table(count_names, third, counts, sums, box_gt_id):
+    """What score_table and surface_score_table share: mask IoU, mask precision, the ratio of the two counts named by
+    `third`, depth bias, MAE and RMSE from counts (B, len(count_names)), in fp64, rounded once.  A ratio whose
+    denominator is 0 is NaN, and so is the IoU of a box without ground truth."""
+    import torch
+    col = dict(zip(count_names, counts.to(torch.float64).unbind(1)))
+    pred_px, inter_px, gt_px, depth_n = (col[k] for k in ('pred_px', 'inter_px', 'gt_px', 'depth_n'))
+    has_gt = (box_gt_id >= 0) & (box_gt_id <= 254)
+    nan = torch.full_like(pred_px, float('nan'))
+    ratio = lambda num, den, ok: torch.where(ok & (den > 0), num / torch.where(den > 0, den, torch.ones_like(den)), nan)
+    every = torch.ones_like(has_gt)
+    return torch.stack([ratio(inter_px, pred_px + gt_px - inter_px, has_gt), ratio(inter_px, pred_px, every),
+                        ratio(col[third[0]], col[third[1]], every), ratio(sums[:, 0], depth_n, every),
+                        ratio(sums[:, 1], depth_n, every), torch.sqrt(ratio(sums[:, 2], depth_n, every))],
+                       1).to(torch.float32)
+
+
 def score_table(counts, sums, box_gt_id):
     """The (B, 6) float32 per-box metric table in SCENE_METRIC_NAMES order from counts (B, 6) int, sums (B, 3) float64
     and box_gt_id (B,) int, tensors of one device: computed in fp64, rounded once.
@@ -85,29 +102,25 @@ def score_table(counts, sums, box_gt_id):
         scene_depth_bias       sum e / depth_n          (e = z - LiDAR depth over the depth_n points)
         scene_depth_mae        sum |e| / depth_n
         scene_depth_rmse       sqrt(sum e^2 / depth_n); all three NaN when depth_n == 0"""
-    import torch
-    c = counts.to(torch.float64)
-    kept, on_points, pred_px, inter_px, gt_px, depth_n = (c[:, k] for k in range(6))
-    has_gt = (box_gt_id >= 0) & (box_gt_id <= 254)
-    nan = torch.full_like(kept, float('nan'))
-    ratio = lambda num, den, ok: torch.where(ok & (den > 0), num / torch.where(den > 0, den, torch.ones_like(den)), nan)
-    every = torch.ones_like(has_gt)
-    return torch.stack([ratio(inter_px, pred_px + gt_px - inter_px, has_gt), ratio(inter_px, pred_px, every),
-                        ratio(on_points, kept, every), ratio(sums[:, 0], depth_n, every),
-                        ratio(sums[:, 1], depth_n, every), torch.sqrt(ratio(sums[:, 2], depth_n, every))],
-                       1).to(torch.float32)
+    return _metric_table(SCENE_COUNT_NAMES, ('on_points', 'kept'), counts, sums, box_gt_id)
 
 
-class SceneScores(object):
-    """A reconstruction against its ground truth, per box, device tensors: counts (B, 6) int32 (SCENE_COUNT_NAMES),
-    sums (B, 3) float64 (SCENE_SUM_NAMES), box_gt_id (B,) int32 as given.  table(): score_table of them."""
+class _Scores(object):
+    """counts, sums and box_gt_id of a scoring call; table(): the subclass's table function of them."""
     __slots__ = ('counts', 'sums', 'box_gt_id')
 
     def __init__(self, counts, sums, box_gt_id):
         self.counts, self.sums, self.box_gt_id = counts, sums, box_gt_id
 
     def table(self):
-        return score_table(self.counts, self.sums, self.box_gt_id)
+        return self._table(self.counts, self.sums, self.box_gt_id)
+
+
+class SceneScores(_Scores):
+    """A reconstruction against its ground truth, per box, device tensors: counts (B, 6) int32 (SCENE_COUNT_NAMES),
+    sums (B, 3) float64 (SCENE_SUM_NAMES), box_gt_id (B,) int32 as given.  table(): score_table of them."""
+    __slots__ = ()
+    _table = staticmethod(score_table)
 
 
 class SceneResult(object):
@@ -225,6 +238,41 @@ def _mask_and_keep(valid_mask, keep, nb, npts, dev):
     return mask, keep_d
 
 
+def _host(a):
+    """The address of a host array, as an entry point takes it."""
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _device_tables(hw, bf, offs, dev):
+    """-> the device copies of _frame_tables' three."""
+    import torch
+    return torch.from_numpy(hw).to(dev), torch.from_numpy(bf).to(dev), torch.from_numpy(offs).to(dev)
+
+
+def _score_args(lib, gt, nf, dev):
+    """gt: what _ground_truth_tables returns -> (the device table of the depth maps' addresses, that of the instance
+    images', the scratch of a scoring call), as mpsr_scene_score and mpsr_scene_surface_score take them."""
+    import torch
+    tables = torch.from_numpy(np.asarray([[_lib.ptr(t) for t in gt[0]], [_lib.ptr(t) for t in gt[1]]],
+                                         np.uint64).view(np.int64)).to(dev)
+    return tables[0], tables[1], _empty((lib.mpsr_scene_score_scratch_bytes(nf),), torch.uint8, dev)
+
+
+def _fill_empty(depth, inst, scores):
+    """The outputs of a chunk with nothing to launch: depth 0, instance 255, no count and no sum (gt_px is not counted
+    either)."""
+    depth.zero_()
+    inst.fill_(255)
+    if scores is not None:
+        scores.counts.zero_()
+        scores.sums.zero_()
+
+
+def _frame_views(flat, hw, offs):
+    """A flat map over all pixels of the chunk -> the list of its (h_f, w_f) views."""
+    return [flat[int(offs[f]):int(offs[f + 1])].view(int(hw[f, 0]), int(hw[f, 1])) for f in range(len(hw))]
+
+
 def project_instance_points(xyz_global, box_frame, cam_p, frame_shapes, images=None, valid_mask=None, keep=None,
                             visible_only=False, ground_truth=None):
     """The direct wrapper of mpsr_scene_project / _resolve / _compact (and, with ground_truth, mpsr_scene_score).
@@ -281,43 +329,36 @@ def project_instance_points(xyz_global, box_frame, cam_p, frame_shapes, images=N
         kept, visible = _empty((nb,), i32, dev), _empty((nb,), i32, dev)
         frame_offset = _empty((nf + 1,), i64, dev)
         if nf == 0 or cap == 0 or total == 0:  # nothing to launch: empty maps, an empty cloud
-            depth.zero_()
-            inst.fill_(255)
+            _fill_empty(depth, inst, scores)
             kept.zero_()
             visible.zero_()
             frame_offset.zero_()
             fo_host = np.zeros(nf + 1, np.int64)
-            if scores is not None:  # (no point: no count; gt_px is not counted either)
-                scores.counts.zero_()
-                scores.sums.zero_()
         else:
-            bf_d, hw_d, offs_d = torch.from_numpy(bf).to(dev), torch.from_numpy(hw).to(dev), torch.from_numpy(offs).to(dev)
+            hw_d, bf_d, offs_d = _device_tables(hw, bf, offs, dev)
             ws = _empty((lib.mpsr_scene_workspace_bytes(nf, total, nb, npts),), torch.uint8, dev)
             stream = _lib.stream()
-            host = lambda a: a.ctypes.data_as(ctypes.c_void_p)
             _lib.check(lib.mpsr_scene_project(
-                _lib.ptr(xyz_in), _lib.ptr(mask), _lib.ptr(bf_d), host(bf), _lib.ptr(keep_d), _lib.ptr(cam),
-                _lib.ptr(hw_d), host(hw), _lib.ptr(offs_d), host(offs), nf, nb, npts, _lib.ptr(ws), ws.numel(), stream))
-            _lib.check(lib.mpsr_scene_resolve(_lib.ptr(bf_d), host(bf), nf, total, nb, npts, _lib.ptr(ws), ws.numel(),
+                _lib.ptr(xyz_in), _lib.ptr(mask), _lib.ptr(bf_d), _host(bf), _lib.ptr(keep_d), _lib.ptr(cam),
+                _lib.ptr(hw_d), _host(hw), _lib.ptr(offs_d), _host(offs), nf, nb, npts, _lib.ptr(ws), ws.numel(),
+                stream))
+            _lib.check(lib.mpsr_scene_resolve(_lib.ptr(bf_d), _host(bf), nf, total, nb, npts, _lib.ptr(ws), ws.numel(),
                                               _lib.ptr(depth), _lib.ptr(inst), stream))
             _lib.check(lib.mpsr_scene_compact(
                 _lib.ptr(xyz_in), _lib.ptr(bf_d), _lib.ptr(table), _lib.ptr(offs_d), nf, total, nb, npts,
                 int(bool(visible_only)), _lib.ptr(ws), ws.numel(), _lib.ptr(xyz), _lib.ptr(rgb), _lib.ptr(box),
                 _lib.ptr(pixel), _lib.ptr(frame_offset), _lib.ptr(kept), _lib.ptr(visible), stream))
             if scores is not None:
-                tables = torch.from_numpy(np.asarray([[_lib.ptr(t) for t in gt[0]], [_lib.ptr(t) for t in gt[1]]],
-                                                     np.uint64).view(np.int64)).to(dev)
-                scratch = _empty((lib.mpsr_scene_score_scratch_bytes(nf),), torch.uint8, dev)
+                gt_depth, gt_inst, scratch = _score_args(lib, gt, nf, dev)
                 _lib.check(lib.mpsr_scene_score(
-                    _lib.ptr(xyz_in), _lib.ptr(bf_d), host(bf), _lib.ptr(scores.box_gt_id), _lib.ptr(tables[0]),
-                    _lib.ptr(tables[1]), _lib.ptr(offs_d), nf, total, nb, npts, _lib.ptr(ws), ws.numel(),
+                    _lib.ptr(xyz_in), _lib.ptr(bf_d), _host(bf), _lib.ptr(scores.box_gt_id), _lib.ptr(gt_depth),
+                    _lib.ptr(gt_inst), _lib.ptr(offs_d), nf, total, nb, npts, _lib.ptr(ws), ws.numel(),
                     _lib.ptr(scratch), scratch.numel(), _lib.ptr(scores.counts), _lib.ptr(scores.sums), stream))
             fo_host = frame_offset.cpu().numpy()  # the one copy to the host: M and where each frame's points are
         m = int(fo_host[-1])
     return SceneResult(
         xyz=xyz[:m], rgb=None if rgb is None else rgb[:m], box=box[:m], pixel=pixel[:m], frame_offset=frame_offset,
-        depth_maps=[depth[int(offs[f]):int(offs[f + 1])].view(int(hw[f, 0]), int(hw[f, 1])) for f in range(nf)],
-        instance_maps=[inst[int(offs[f]):int(offs[f + 1])].view(int(hw[f, 0]), int(hw[f, 1])) for f in range(nf)],
+        depth_maps=_frame_views(depth, hw, offs), instance_maps=_frame_views(inst, hw, offs),
         kept_per_box=kept, visible_per_box=visible, frame_offset_host=fo_host, box_frame_host=bf, scores=scores)
 
 
@@ -379,29 +420,14 @@ def surface_score_table(counts, sums, box_gt_id):
         surface_depth_bias      sum e / depth_n          (e = rendered depth - LiDAR depth over the depth_n pixels)
         surface_depth_mae       sum |e| / depth_n
         surface_depth_rmse      sqrt(sum e^2 / depth_n); all three NaN when depth_n == 0"""
-    import torch
-    c = counts.to(torch.float64)
-    _, pred_px, inter_px, gt_px, depth_n = (c[:, k] for k in range(5))
-    has_gt = (box_gt_id >= 0) & (box_gt_id <= 254)
-    nan = torch.full_like(pred_px, float('nan'))
-    ratio = lambda num, den, ok: torch.where(ok & (den > 0), num / torch.where(den > 0, den, torch.ones_like(den)), nan)
-    every = torch.ones_like(has_gt)
-    return torch.stack([ratio(inter_px, pred_px + gt_px - inter_px, has_gt), ratio(inter_px, pred_px, every),
-                        ratio(inter_px, gt_px, every), ratio(sums[:, 0], depth_n, every),
-                        ratio(sums[:, 1], depth_n, every), torch.sqrt(ratio(sums[:, 2], depth_n, every))],
-                       1).to(torch.float32)
+    return _metric_table(SURFACE_COUNT_NAMES, ('inter_px', 'gt_px'), counts, sums, box_gt_id)
 
 
-class SurfaceScores(object):
+class SurfaceScores(_Scores):
     """The surfaces against their ground truth, per box, device tensors: counts (B, 5) int32 (SURFACE_COUNT_NAMES),
     sums (B, 3) float64 (SURFACE_SUM_NAMES), box_gt_id (B,) int32 as given.  table(): surface_score_table of them."""
-    __slots__ = ('counts', 'sums', 'box_gt_id')
-
-    def __init__(self, counts, sums, box_gt_id):
-        self.counts, self.sums, self.box_gt_id = counts, sums, box_gt_id
-
-    def table(self):
-        return surface_score_table(self.counts, self.sums, self.box_gt_id)
+    __slots__ = ()
+    _table = staticmethod(surface_score_table)
 
 
 class FrameSurface(object):
@@ -477,79 +503,83 @@ def render_instance_surfaces(xyz_global_maps, box_frame, cam_p, frame_shapes, va
         inst = _empty((total,), torch.uint8, dev)
         tri = _empty((total,), i32, dev) if want_tri else None
         if nf == 0 or nb == 0 or total == 0:  # nothing to launch: empty maps
-            depth.zero_()
-            inst.fill_(255)
+            _fill_empty(depth, inst, scores)
             if tri is not None:
                 tri.fill_(-1)
             tris = torch.zeros((nb,), dtype=i32, device=dev)
             pixels = torch.zeros((nb,), dtype=i32, device=dev)
-            if scores is not None:
-                scores.counts.zero_()
-                scores.sums.zero_()
         else:
-            bf_d, hw_d, offs_d = torch.from_numpy(bf).to(dev), torch.from_numpy(hw).to(dev), torch.from_numpy(offs).to(dev)
+            hw_d, bf_d, offs_d = _device_tables(hw, bf, offs, dev)
             ws = _empty((lib.mpsr_scene_surface_workspace_bytes(nf, total, nb, mh, mw),), torch.uint8, dev)
             stream = _lib.stream()
-            host = lambda a: a.ctypes.data_as(ctypes.c_void_p)
             _lib.check(lib.mpsr_scene_surface_render(
-                _lib.ptr(xyz_in), _lib.ptr(mask), _lib.ptr(bf_d), host(bf), _lib.ptr(keep_d), _lib.ptr(cam),
-                _lib.ptr(hw_d), host(hw), _lib.ptr(offs_d), host(offs), nf, nb, mh, mw, max_edge_dz, max_span_px,
+                _lib.ptr(xyz_in), _lib.ptr(mask), _lib.ptr(bf_d), _host(bf), _lib.ptr(keep_d), _lib.ptr(cam),
+                _lib.ptr(hw_d), _host(hw), _lib.ptr(offs_d), _host(offs), nf, nb, mh, mw, max_edge_dz, max_span_px,
                 _lib.ptr(ws), ws.numel(), stream))
-            _lib.check(lib.mpsr_scene_surface_resolve(_lib.ptr(bf_d), host(bf), nf, total, nb, mh, mw, _lib.ptr(ws),
+            _lib.check(lib.mpsr_scene_surface_resolve(_lib.ptr(bf_d), _host(bf), nf, total, nb, mh, mw, _lib.ptr(ws),
                                                       ws.numel(), _lib.ptr(depth), _lib.ptr(inst), _lib.ptr(tri), stream))
             if scores is None:  # without ground truth: the two per-box counts alone
                 counts, sums = _empty((nb, 5), i32, dev), _empty((nb, 3), torch.float64, dev)
-                gt_args = (None, None, None)
-                scratch = None
+                gt_id = gt_depth = gt_inst = scratch = None
             else:
-                counts, sums = scores.counts, scores.sums
-                tables = torch.from_numpy(np.asarray([[_lib.ptr(t) for t in gt[0]], [_lib.ptr(t) for t in gt[1]]],
-                                                     np.uint64).view(np.int64)).to(dev)
-                gt_args = (_lib.ptr(scores.box_gt_id), _lib.ptr(tables[0]), _lib.ptr(tables[1]))
-                scratch = _empty((lib.mpsr_scene_score_scratch_bytes(nf),), torch.uint8, dev)
+                counts, sums, gt_id = scores.counts, scores.sums, scores.box_gt_id
+                gt_depth, gt_inst, scratch = _score_args(lib, gt, nf, dev)
             _lib.check(lib.mpsr_scene_surface_score(
-                _lib.ptr(bf_d), host(bf), gt_args[0], gt_args[1], gt_args[2], _lib.ptr(hw_d), _lib.ptr(offs_d), nf,
-                total, nb, mh, mw, _lib.ptr(ws), ws.numel(), _lib.ptr(scratch), 0 if scratch is None else scratch.numel(),
-                _lib.ptr(counts), _lib.ptr(sums), stream))
+                _lib.ptr(bf_d), _host(bf), _lib.ptr(gt_id), _lib.ptr(gt_depth), _lib.ptr(gt_inst), _lib.ptr(hw_d),
+                _lib.ptr(offs_d), nf, total, nb, mh, mw, _lib.ptr(ws), ws.numel(), _lib.ptr(scratch),
+                0 if scratch is None else scratch.numel(), _lib.ptr(counts), _lib.ptr(sums), stream))
             tris, pixels = counts[:, 0], counts[:, 1]
-    view = lambda flat: [flat[int(offs[f]):int(offs[f + 1])].view(int(hw[f, 0]), int(hw[f, 1])) for f in range(nf)]
-    return SurfaceResult(depth_maps=view(depth), instance_maps=view(inst), tri_maps=None if tri is None else view(tri),
+    return SurfaceResult(depth_maps=_frame_views(depth, hw, offs), instance_maps=_frame_views(inst, hw, offs),
+                         tri_maps=None if tri is None else _frame_views(tri, hw, offs),
                          tris_per_box=tris, pixels_per_box=pixels, scores=scores)
 
 
 SURFACE_DIRS = ('depth_surface', 'instances_surface')
 
 
-def surface_output_dirs(base):
-    """{'depth_surface' | 'instances_surface': <base>/<kind>}, created."""
-    dirs = {k: os.path.join(base, k) for k in SURFACE_DIRS}
+def _output_dirs(base, kinds):
+    dirs = {k: os.path.join(base, k) for k in kinds}
     for d in dirs.values():
         os.makedirs(d, exist_ok=True)
     return dirs
 
 
+def _host_maps(frame):
+    """-> the depth map and the instance map of a FrameScene or a FrameSurface, as arrays."""
+    return frame.depth_map.detach().cpu().numpy(), frame.instance_map.detach().cpu().numpy()
+
+
+def _empty_maps(image_shape):
+    """-> the two maps of a frame without a box: depth 0, instance 255 everywhere."""
+    h, w = int(image_shape[0]), int(image_shape[1])
+    return np.zeros((h, w), np.float32), np.full((h, w), 255, np.uint8)
+
+
+def _save_maps(out_dirs, kinds, name, depth, inst):
+    """<kinds[0]>/<name>.png (depth_map_utils.save_depth_map: uint16, 1/256 m) and <kinds[1]>/<name>.png
+    (instance_utils.save_instance_image) of a depth map and an instance map, arrays.  -> the two paths."""
+    from monopsr_amd.datasets.kitti import depth_map_utils, instance_utils
+    paths = tuple(os.path.join(out_dirs[k], name + '.png') for k in kinds)
+    # (a depth beyond the PNG's 16 bits, 256 m, has no place in the format: stored as 0, "no depth")
+    depth_map_utils.save_depth_map(paths[0], np.where(depth < 256.0, depth, np.float32(0.0)))
+    instance_utils.save_instance_image(paths[1], inst)
+    return paths
+
+
+def surface_output_dirs(base):
+    """{'depth_surface' | 'instances_surface': <base>/<kind>}, created."""
+    return _output_dirs(base, SURFACE_DIRS)
+
+
 def save_surface_frame(out_dirs, name, frame_surface):
     """depth_surface/<name>.png and instances_surface/<name>.png of a FrameSurface, in the formats of save_frame's depth
     and instance files.  -> the two paths."""
-    from monopsr_amd.datasets.kitti import depth_map_utils, instance_utils
-    paths = (os.path.join(out_dirs['depth_surface'], name + '.png'),
-             os.path.join(out_dirs['instances_surface'], name + '.png'))
-    depth = frame_surface.depth_map.detach().cpu().numpy()
-    # (a depth beyond the PNG's 16 bits, 256 m, has no place in the format: stored as 0, "no depth")
-    depth_map_utils.save_depth_map(paths[0], np.where(depth < 256.0, depth, np.float32(0.0)))
-    instance_utils.save_instance_image(paths[1], frame_surface.instance_map.detach().cpu().numpy())
-    return paths
+    return _save_maps(out_dirs, SURFACE_DIRS, name, *_host_maps(frame_surface))
 
 
 def save_empty_surface_frame(out_dirs, name, image_shape):
     """The two files of a frame without a box: depth 0, instance 255 everywhere.  -> the two paths."""
-    from monopsr_amd.datasets.kitti import depth_map_utils, instance_utils
-    h, w = int(image_shape[0]), int(image_shape[1])
-    paths = (os.path.join(out_dirs['depth_surface'], name + '.png'),
-             os.path.join(out_dirs['instances_surface'], name + '.png'))
-    depth_map_utils.save_depth_map(paths[0], np.zeros((h, w), np.float32))
-    instance_utils.save_instance_image(paths[1], np.full((h, w), 255, np.uint8))
-    return paths
+    return _save_maps(out_dirs, SURFACE_DIRS, name, *_empty_maps(image_shape))
 
 
 # ---- files
@@ -607,36 +637,22 @@ SCENE_DIRS = ('points', 'depth', 'instances')
 
 def scene_output_dirs(base):
     """{'points' | 'depth' | 'instances': <base>/<kind>}, created."""
-    dirs = {k: os.path.join(base, k) for k in SCENE_DIRS}
-    for d in dirs.values():
-        os.makedirs(d, exist_ok=True)
-    return dirs
+    return _output_dirs(base, SCENE_DIRS)
 
 
 def save_frame(out_dirs, name, frame_result):
     """points/<name>.ply, depth/<name>.png (depth_map_utils.save_depth_map: uint16, 1/256 m) and instances/<name>.png
     (instance_utils.save_instance_image) of a FrameScene.  -> the three paths."""
-    from monopsr_amd.datasets.kitti import depth_map_utils, instance_utils
     fr = frame_result
     host = lambda t: None if t is None else t.detach().cpu().numpy()
-    paths = (os.path.join(out_dirs['points'], name + '.ply'), os.path.join(out_dirs['depth'], name + '.png'),
-             os.path.join(out_dirs['instances'], name + '.png'))
-    write_ply(paths[0], host(fr.xyz), host(fr.rgb), host(fr.box))
-    # (a depth beyond the PNG's 16 bits, 256 m, has no place in the format: stored as 0, "no depth")
-    depth = host(fr.depth_map)
-    depth_map_utils.save_depth_map(paths[1], np.where(depth < 256.0, depth, np.float32(0.0)))
-    instance_utils.save_instance_image(paths[2], host(fr.instance_map))
-    return paths
+    ply = os.path.join(out_dirs['points'], name + '.ply')
+    write_ply(ply, host(fr.xyz), host(fr.rgb), host(fr.box))
+    return (ply,) + _save_maps(out_dirs, SCENE_DIRS[1:], name, *_host_maps(fr))
 
 
 def save_empty_frame(out_dirs, name, image_shape):
     """The three files of a frame without a box (the Evaluator writes an empty label file for it): no vertex, depth 0,
     instance 255 everywhere.  -> the three paths."""
-    from monopsr_amd.datasets.kitti import depth_map_utils, instance_utils
-    h, w = int(image_shape[0]), int(image_shape[1])
-    paths = (os.path.join(out_dirs['points'], name + '.ply'), os.path.join(out_dirs['depth'], name + '.png'),
-             os.path.join(out_dirs['instances'], name + '.png'))
-    write_ply(paths[0], np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8), np.zeros(0, np.int32))
-    depth_map_utils.save_depth_map(paths[1], np.zeros((h, w), np.float32))
-    instance_utils.save_instance_image(paths[2], np.full((h, w), 255, np.uint8))
-    return paths
+    ply = os.path.join(out_dirs['points'], name + '.ply')
+    write_ply(ply, np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8), np.zeros(0, np.int32))
+    return (ply,) + _save_maps(out_dirs, SCENE_DIRS[1:], name, *_empty_maps(image_shape))

@@ -9,8 +9,10 @@
 //   wins, and on equal float32 depth the LOWER point index, in whatever order the waves run.  A true z-buffer.  The LiDAR
 //   projection of depth_fill.hip is not: it keeps the LAST duplicate of a pixel, near or far, because that is what the
 //   reference's fancy assignment does with a LiDAR cloud.
+//   alive() is the one rule for which point takes part; the surfaces' vertex pass calls it too.
 // mpsr_scene_resolve: one thread per pixel turns the key into depth (the key's upper half, the winner's z bit for bit;
 //   0 where no point fell) and instance (the winner box's ordinal within its frame; 255 where no point fell).
+//   resolve_kernel serves the surfaces' z-buffer as well: there the key's lower half is a triangle id.
 // mpsr_scene_compact: per-box counts of kept and of visible points (a visible point is its pixel's winner), a one-block
 //   exclusive scan over the boxes, and a write pass of one workgroup per box that places a point at its box's offset
 //   plus its rank within the box: __ballot / __popcll prefix counts within a wave, wave offsets through LDS, a running
@@ -21,9 +23,11 @@
 //   on order.  The frame pointers are NOT aligned (frame k of a stack of 5 x 7 images starts at byte 35 k): the pass
 //   PEELS to alignment -- the bytes in front of the first 16-byte boundary and behind the last one are read one by
 //   one, the body in 16-byte loads.  score_kernel, one workgroup per box, walks the box's points in slices of 256 as
-//   count_kernel does: the six counts from ballots and popcounts, the three fp64 sums per thread in slice order, then
-//   a lane-ordered wave reduction, wave partials through LDS and a combine in wave order.  No floating-point atomics:
-//   two calls return the same bytes.
+//   count_kernel does: the six counts from ballots and popcounts, the three fp64 sums per thread in slice order
+//   (add_depth_error), then block_tally, the end of every per-box pass here: a lane-ordered wave reduction, wave
+//   partials through LDS and a combine in wave order.  No floating-point atomics: two calls return the same bytes.
+// The host side of both z-buffers is shared too: ZLayout (the front of either workspace), check_render_args,
+//   start_zbuffer, resolve and launch_hist.
 #include "common.h"
 
 #include <algorithm>
@@ -38,6 +42,20 @@ constexpr unsigned long long kEmptyKey = ~0ULL;  // the memset's 0xff bytes; no 
 __device__ __forceinline__ void rows3(const double *m, double x, double y, double z, double *o)
 {
     for (int r = 0; r < 3; ++r) o[r] = ((m[4 * r] * x + m[4 * r + 1] * y) + m[4 * r + 2] * z) + m[4 * r + 3];
+}
+
+// Is point i, of box b, alive: its box kept, its mask > 0, x, y and z finite and z > 0?  u = cam_p of its frame .
+// [x y z 1]; what becomes of u is the caller's.  u is written for a dead point too, where nobody reads it: filled
+// under `on`, u would join the two paths behind the call, and the caller's `if` would be a second branch on the same
+// condition; written like this the products sink into that `if`.
+__device__ __forceinline__ bool alive(const float *xyz, const float *valid_mask, const int *box_frame,
+                                      const int *box_keep, const double *cam_p, long long i, int b, double *u)
+{
+    const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+    const bool on = (box_keep == nullptr || box_keep[b] != 0) && (valid_mask == nullptr || valid_mask[i] > 0.0f) &&
+                    isfinite(x) && isfinite(y) && isfinite(z) && z > 0.0f;
+    rows3(cam_p + 12 * box_frame[b], (double)x, (double)y, (double)z, u);
+    return on;
 }
 
 // frame_box[f] = the first box of frame f (box_frame is sorted), frame_box[n_frames] = n_boxes
@@ -69,21 +87,17 @@ __global__ void __launch_bounds__(kThreads) project_kernel(const float *__restri
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int b = (int)(i / points_per_box);
-        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
         int at = -1;
-        const bool on = (box_keep == nullptr || box_keep[b] != 0) && (valid_mask == nullptr || valid_mask[i] > 0.0f) &&
-                        isfinite(x) && isfinite(y) && isfinite(z) && z > 0.0f;
-        if (on) {
+        double u[3];
+        if (alive(xyz, valid_mask, box_frame, box_keep, cam_p, i, b, u)) {
             const int f = box_frame[b];
             const int h = frame_hw[2 * f], w = frame_hw[2 * f + 1];
-            double u[3];
-            rows3(cam_p + 12 * f, (double)x, (double)y, (double)z, u);
             const double col = rint(u[0] / u[2]), row = rint(u[1] / u[2]);
             // NaN fails every comparison; +-inf fails the range test; -0.0 is inside
             if (u[2] > 0.0 && col >= 0.0 && col < (double)w && row >= 0.0 && row < (double)h) {
                 at = (int)row * w + (int)col;
                 const unsigned long long key =
-                    ((unsigned long long)__float_as_uint(z) << 32) | (unsigned long long)(unsigned)i;
+                    ((unsigned long long)__float_as_uint(xyz[3 * i + 2]) << 32) | (unsigned long long)(unsigned)i;
                 atomicMin(keys + pixel_offset[f] + at, key);
             }
         }
@@ -91,31 +105,70 @@ __global__ void __launch_bounds__(kThreads) project_kernel(const float *__restri
     }
 }
 
+// one thread per pixel of either z-buffer: a key's lower half is the id of a point or of a triangle, ids_per_box of
+// them to a box; ids (may be null) takes it, -1 where nothing fell
 __global__ void __launch_bounds__(kThreads) resolve_kernel(const unsigned long long *__restrict__ keys,
                                                            long long total_pixels, const int *__restrict__ box_frame,
-                                                           const int *__restrict__ frame_box, int points_per_box,
+                                                           const int *__restrict__ frame_box, unsigned ids_per_box,
                                                            float *__restrict__ depth,
-                                                           unsigned char *__restrict__ instance)
+                                                           unsigned char *__restrict__ instance, int *__restrict__ ids)
 {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total_pixels;
          i += (long long)gridDim.x * blockDim.x) {
         const unsigned long long key = keys[i];
         float d = 0.0f;
-        unsigned char id = 255;
+        unsigned char inst = 255;
+        int id = -1;
         if (key != kEmptyKey) {
             d = __uint_as_float((unsigned)(key >> 32));
-            const int b = (int)((unsigned)key / (unsigned)points_per_box);
-            id = (unsigned char)(b - frame_box[box_frame[b]]);
+            id = (int)(unsigned)key;
+            const int b = (int)((unsigned)key / ids_per_box);
+            inst = (unsigned char)(b - frame_box[box_frame[b]]);
         }
         depth[i] = d;
-        instance[i] = id;
+        instance[i] = inst;
+        if (ids) ids[i] = id;
     }
 }
 
-// is point i (pixel `at` of its frame, whose keys start at fkeys) its pixel's winner?
-__device__ __forceinline__ bool wins(const unsigned long long *fkeys, int at, long long i)
+// is point i its pixel's winner, key being that pixel's?
+__device__ __forceinline__ bool wins(unsigned long long key, long long i) { return (unsigned)key == (unsigned)i; }
+
+// Adds the depth error of an element whose key won its pixel, against the ground-truth depth d there, to s = the sums
+// of e, |e| and e * e, e = (double) the key's depth - (double) d; false, and nothing added, where d is no measurement.
+__device__ __forceinline__ bool add_depth_error(unsigned long long key, float d, double *s)
 {
-    return (unsigned)fkeys[at] == (unsigned)i;
+    if (!(isfinite(d) && d > 0.0f)) return false;
+    const double e = (double)__uint_as_float((unsigned)(key >> 32)) - (double)d;
+    s[0] += e;
+    s[1] += fabs(e);
+    s[2] += e * e;
+    return true;
+}
+
+// The end of a one-workgroup-per-box pass.  n: N counts per wave (every lane holds its wave's); s: S fp64 sums per
+// thread.  On return thread 0 holds the workgroup's totals in both: s reduced within a wave by a fixed tree (lane l +=
+// lane l + o, o = 32 .. 1), then both combined in wave order through LDS.  The order does not depend on scheduling.
+template <int N, int S>
+__device__ __forceinline__ void block_tally(int *n, double *s)
+{
+    __shared__ int part[N][kWaves];
+    __shared__ double dpart[S ? S : 1][kWaves];  // (S = 0: never touched, and dropped)
+    for (int k = 0; k < S; ++k)
+        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_down(s[k], o);
+    if ((threadIdx.x & 63) == 0) {
+        for (int k = 0; k < N; ++k) part[k][threadIdx.x >> 6] = n[k];
+        for (int k = 0; k < S; ++k) dpart[k][threadIdx.x >> 6] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < N; ++k) n[k] = 0;
+        for (int k = 0; k < S; ++k) s[k] = 0.0;
+        for (int v = 0; v < kWaves; ++v) {  // in wave order
+            for (int k = 0; k < N; ++k) n[k] += part[k][v];
+            for (int k = 0; k < S; ++k) s[k] += dpart[k][v];
+        }
+    }
 }
 
 // one workgroup per box: kept[b] and visible[b]
@@ -126,30 +179,20 @@ __global__ void __launch_bounds__(kThreads) count_kernel(const unsigned long lon
                                                          int points_per_box, int *__restrict__ kept,
                                                          int *__restrict__ visible)
 {
-    __shared__ int part[2][kWaves];
     const int b = blockIdx.x;
     const unsigned long long *fkeys = keys + pixel_offset[box_frame[b]];
     const long long i0 = (long long)b * points_per_box;
-    int nk = 0, nv = 0;  // per wave: every lane holds its wave's sums
+    int n[2] = {0, 0};  // kept, visible
     for (int p0 = 0; p0 < points_per_box; p0 += kThreads) {
         const int p = p0 + threadIdx.x;
         const int at = p < points_per_box ? pix[i0 + p] : -1;
-        nk += __popcll(__ballot(at >= 0));
-        nv += __popcll(__ballot(at >= 0 && wins(fkeys, at, i0 + p)));
+        n[0] += __popcll(__ballot(at >= 0));
+        n[1] += __popcll(__ballot(at >= 0 && wins(fkeys[at], i0 + p)));
     }
-    if ((threadIdx.x & 63) == 0) {
-        part[0][threadIdx.x >> 6] = nk;
-        part[1][threadIdx.x >> 6] = nv;
-    }
-    __syncthreads();
+    block_tally<2, 0>(n, nullptr);
     if (threadIdx.x == 0) {
-        int sk = 0, sv = 0;
-        for (int v = 0; v < kWaves; ++v) {
-            sk += part[0][v];
-            sv += part[1][v];
-        }
-        kept[b] = sk;
-        visible[b] = sv;
+        kept[b] = n[0];
+        visible[b] = n[1];
     }
 }
 
@@ -215,7 +258,7 @@ __global__ void __launch_bounds__(kThreads) write_kernel(const float *__restrict
     for (int p0 = 0; p0 < points_per_box; p0 += kThreads) {
         const int p = p0 + threadIdx.x;
         const int at = p < points_per_box ? pix[i0 + p] : -1;
-        const bool take = at >= 0 && (!visible_only || wins(fkeys, at, i0 + p));
+        const bool take = at >= 0 && (!visible_only || wins(fkeys[at], i0 + p));
         const unsigned long long mask = __ballot(take);
         if (lane == 0) wave_n[wave] = __popcll(mask);
         __syncthreads();
@@ -297,87 +340,70 @@ __global__ void __launch_bounds__(kThreads) score_kernel(const unsigned long lon
                                                          const int *__restrict__ hist, int points_per_box,
                                                          int *__restrict__ counts, double *__restrict__ sums)
 {
-    __shared__ int part[5][kWaves];
-    __shared__ double dpart[3][kWaves];
     const int b = blockIdx.x, f = box_frame[b], g = box_gt_id[b];
     const bool has_gt = g >= 0 && g <= 254;
     const unsigned long long *fkeys = keys + pixel_offset[f];
     const unsigned char *inst = gt_instance[f];
     const float *depth = gt_depth[f];
     const long long i0 = (long long)b * points_per_box;
-    int n[5] = {0, 0, 0, 0, 0};          // per wave: every lane holds its wave's counts
-    double s[3] = {0.0, 0.0, 0.0};       // per thread, in slice order
+    int n[5] = {0, 0, 0, 0, 0};     // kept, on_points, pred_px, inter_px, depth_n
+    double s[3] = {0.0, 0.0, 0.0};  // in slice order
     for (int p0 = 0; p0 < points_per_box; p0 += kThreads) {
         const int p = p0 + threadIdx.x;
         const int at = p < points_per_box ? pix[i0 + p] : -1;
         const bool kept = at >= 0;
         const bool on = kept && has_gt && (int)inst[at] == g;
         const unsigned long long key = kept ? fkeys[at] : kEmptyKey;
-        const bool visible = kept && (unsigned)key == (unsigned)(i0 + p);
+        const bool visible = kept && wins(key, i0 + p);
         const bool inter = visible && on;
-        bool measured = false;
-        if (inter) {
-            const float d = depth[at];
-            if (isfinite(d) && d > 0.0f) {
-                measured = true;
-                const double e = (double)__uint_as_float((unsigned)(key >> 32)) - (double)d;
-                s[0] += e;
-                s[1] += fabs(e);
-                s[2] += e * e;
-            }
-        }
+        const bool measured = inter && add_depth_error(key, depth[at], s);
         n[0] += __popcll(__ballot(kept));
         n[1] += __popcll(__ballot(on));
         n[2] += __popcll(__ballot(visible));
         n[3] += __popcll(__ballot(inter));
         n[4] += __popcll(__ballot(measured));
     }
-    for (int k = 0; k < 3; ++k)
-        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_down(s[k], o);  // lane l += lane l + o: a fixed tree
-    if ((threadIdx.x & 63) == 0) {
-        for (int k = 0; k < 5; ++k) part[k][threadIdx.x >> 6] = n[k];
-        for (int k = 0; k < 3; ++k) dpart[k][threadIdx.x >> 6] = s[k];
-    }
-    __syncthreads();
+    block_tally<5, 3>(n, s);
     if (threadIdx.x == 0) {
-        int c[5] = {0, 0, 0, 0, 0};
-        double t[3] = {0.0, 0.0, 0.0};
-        for (int v = 0; v < kWaves; ++v) {  // in wave order
-            for (int k = 0; k < 5; ++k) c[k] += part[k][v];
-            for (int k = 0; k < 3; ++k) t[k] += dpart[k][v];
-        }
         int *out = counts + 6 * (long long)b;
-        out[0] = c[0];
-        out[1] = c[1];
-        out[2] = c[2];
-        out[3] = c[3];
+        out[0] = n[0];
+        out[1] = n[1];
+        out[2] = n[2];
+        out[3] = n[3];
         out[4] = has_gt ? hist[256 * (long long)f + g] : 0;
-        out[5] = c[4];
-        for (int k = 0; k < 3; ++k) sums[3 * (long long)b + k] = t[k];
+        out[5] = n[4];
+        for (int k = 0; k < 3; ++k) sums[3 * (long long)b + k] = s[k];
     }
 }
 
-// workspace: [keys: one uint64 per pixel] [pix: one int per point] [frame_box: n_frames + 1 ints]
-// [box_offset: n_boxes + 1 int64]
-struct SceneLayout {
-    size_t keys, pix, frame_box, box_offset, total;
+// A z-buffer's workspace begins [keys: one uint64 per pixel] [frame_box: n_frames + 1 ints], whatever is drawn into it;
+// take() lays the next region behind them, each aligned to 256 bytes.
+struct ZLayout {
+    size_t keys, frame_box, total = 0;
+
+    ZLayout(int n_frames, long long total_pixels)
+    {
+        keys = take((size_t)total_pixels * sizeof(unsigned long long));
+        frame_box = take(((size_t)n_frames + 1) * sizeof(int));
+    }
+    size_t take(size_t bytes)
+    {
+        const size_t at = total;
+        total += mpsr::align_up(bytes, 256);
+        return at;
+    }
 };
 
-SceneLayout scene_layout(int n_frames, long long total_pixels, int n_boxes, int points_per_box)
-{
-    SceneLayout L;
-    size_t o = 0;
-    L.keys = o;
-    o += mpsr::align_up((size_t)total_pixels * sizeof(unsigned long long), 256);
-    L.pix = o;
-    o += mpsr::align_up((size_t)n_boxes * points_per_box * sizeof(int), 256);
-    L.frame_box = o;
-    o += mpsr::align_up(((size_t)n_frames + 1) * sizeof(int), 256);
-    L.box_offset = o;
-    o += mpsr::align_up(((size_t)n_boxes + 1) * sizeof(long long), 256);
-    L.total = o;
-    return L;
-}
+// the points' workspace: ... [pix: one int per point] [box_offset: n_boxes + 1 int64]
+struct SceneLayout : ZLayout {
+    size_t pix, box_offset;
+
+    SceneLayout(int n_frames, long long total_pixels, int n_boxes, int points_per_box) : ZLayout(n_frames, total_pixels)
+    {
+        pix = take((size_t)n_boxes * points_per_box * sizeof(int));
+        box_offset = take(((size_t)n_boxes + 1) * sizeof(long long));
+    }
+};
 
 // the sizes every entry point takes; *empty: nothing to do
 int check_sizes(const char *who, int n_frames, long long total_pixels, int n_boxes, int points_per_box, bool *empty)
@@ -393,10 +419,10 @@ int check_sizes(const char *who, int n_frames, long long total_pixels, int n_box
     return MPSR_OK;
 }
 
-int check_workspace(const char *who, const void *workspace, size_t workspace_bytes, const SceneLayout &L)
+int check_workspace(const char *who, const void *workspace, size_t workspace_bytes, size_t need)
 {
-    if (!workspace || workspace_bytes < L.total)
-        return mpsr::fail(MPSR_ERR_WORKSPACE, "%s: workspace %zu bytes < %zu", who, workspace_bytes, L.total);
+    if (!workspace || workspace_bytes < need)
+        return mpsr::fail(MPSR_ERR_WORKSPACE, "%s: workspace %zu bytes < %zu", who, workspace_bytes, need);
     return MPSR_OK;
 }
 
@@ -431,10 +457,15 @@ int check_frame_tables(const char *who, const int *frame_hw_host, const long lon
     return MPSR_OK;
 }
 
-// hist (n_frames, 256) int32 = the value counts of the ground-truth instance images: zeroed, then hist_kernel
-int launch_hist(const unsigned char *const *gt_instance, const long long *pixel_offset, int n_frames,
-                long long total_pixels, int *hist, hipStream_t s)
+// scratch, checked = hist (n_frames, 256) int32 = the value counts of the ground-truth instance images: zeroed, then
+// hist_kernel
+int launch_hist(const char *who, const unsigned char *const *gt_instance, const long long *pixel_offset, int n_frames,
+                long long total_pixels, void *scratch, size_t scratch_bytes, hipStream_t s)
 {
+    const size_t need = mpsr_scene_score_scratch_bytes(n_frames);
+    if (!scratch || scratch_bytes < need)
+        return mpsr::fail(MPSR_ERR_WORKSPACE, "%s: scratch %zu bytes < %zu", who, scratch_bytes, need);
+    int *hist = static_cast<int *>(scratch);
     MPSR_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)n_frames * 256 * sizeof(int), s));
     // workgroups per frame: one per 64 KiB of an average frame (a frame of any size is walked with the grid's stride)
     const long long per_frame = (total_pixels + n_frames - 1) / n_frames;
@@ -449,13 +480,64 @@ int launch_hist(const unsigned char *const *gt_instance, const long long *pixel_
 
 unsigned grid_for(long long n) { return (unsigned)std::min<long long>((n + kThreads - 1) / kThreads, 1 << 16); }
 
+// What mpsr_scene_project and mpsr_scene_surface_render check alike once their own sizes are known good: the pointers,
+// the frame tables, the *total_pixels these give (read once the pointer is known to be there) and box_frame.
+int check_render_args(const char *who, const float *xyz_global, const int *box_frame, const int *box_frame_host,
+                      const double *cam_p, const int *frame_hw, const int *frame_hw_host,
+                      const long long *pixel_offset, const long long *pixel_offset_host, int n_frames, int n_boxes,
+                      long long *total_pixels)
+{
+    MPSR_REQUIRE(xyz_global && box_frame && box_frame_host, "%s: points or box_frame is null", who);
+    MPSR_REQUIRE(cam_p && frame_hw && frame_hw_host && pixel_offset && pixel_offset_host,
+                 "%s: cameras, frame sizes or pixel offsets are null", who);
+    int st = check_frame_tables(who, frame_hw_host, pixel_offset_host, n_frames);
+    if (st) return st;
+    *total_pixels = pixel_offset_host[n_frames];
+    bool empty;
+    st = check_sizes(who, n_frames, *total_pixels, n_boxes, 1, &empty);  // (the caller has checked what a box holds)
+    if (st) return st;
+    return check_box_frames(who, box_frame_host, n_boxes, n_frames, 0);
+}
+
+// starts a z-buffer in a checked workspace: every key empty, frame_box filled
+int start_zbuffer(const char *who, void *workspace, size_t workspace_bytes, const ZLayout &L, long long total_pixels,
+                  const int *box_frame, int n_boxes, int n_frames, hipStream_t s)
+{
+    int st = check_workspace(who, workspace, workspace_bytes, L.total);
+    if (st) return st;
+    char *ws = static_cast<char *>(workspace);
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws + L.keys);
+    MPSR_CHECK_HIP(hipMemsetAsync(keys, 0xff, (size_t)total_pixels * sizeof(unsigned long long), s));  // kEmptyKey
+    hipLaunchKernelGGL(frame_box_kernel, dim3((n_frames + 1 + kThreads - 1) / kThreads), dim3(kThreads), 0, s,
+                       box_frame, n_boxes, n_frames, reinterpret_cast<int *>(ws + L.frame_box));
+    return MPSR_OK;
+}
+
+// a non-empty z-buffer's keys -> depth, instance and (ids not null) id maps; ids_per_box: the points or triangles of a box
+int resolve(const char *who, const int *box_frame, const int *box_frame_host, int n_frames, long long total_pixels,
+            int n_boxes, unsigned ids_per_box, const void *workspace, size_t workspace_bytes, const ZLayout &L,
+            float *depth, unsigned char *instance, int *ids, mpsr_stream_t stream)
+{
+    MPSR_REQUIRE(box_frame && box_frame_host && depth && instance, "%s: box_frame or an output is null", who);
+    int st = check_box_frames(who, box_frame_host, n_boxes, n_frames, MPSR_INSTANCE_MAX_BOXES);
+    if (st) return st;
+    st = check_workspace(who, workspace, workspace_bytes, L.total);
+    if (st) return st;
+    const char *ws = static_cast<const char *>(workspace);
+    hipLaunchKernelGGL(resolve_kernel, dim3(grid_for(total_pixels)), dim3(kThreads), 0, mpsr::as_stream(stream),
+                       reinterpret_cast<const unsigned long long *>(ws + L.keys), total_pixels, box_frame,
+                       reinterpret_cast<const int *>(ws + L.frame_box), ids_per_box, depth, instance, ids);
+    MPSR_CHECK_LAUNCH(who);
+    return MPSR_OK;
+}
+
 }  // namespace
 
 extern "C" size_t mpsr_scene_workspace_bytes(int n_frames, long long total_pixels, int n_boxes, int points_per_box)
 {
     if (n_frames <= 0 || total_pixels <= 0 || n_boxes <= 0 || points_per_box <= 0) return 0;
     if ((long long)n_boxes * points_per_box >= (1LL << 32) || total_pixels > (1LL << 40)) return 0;
-    return scene_layout(n_frames, total_pixels, n_boxes, points_per_box).total;
+    return SceneLayout(n_frames, total_pixels, n_boxes, points_per_box).total;
 }
 
 extern "C" int mpsr_scene_project(const float *xyz_global, const float *valid_mask, const int *box_frame,
@@ -464,36 +546,25 @@ extern "C" int mpsr_scene_project(const float *xyz_global, const float *valid_ma
                                   const long long *pixel_offset_host, int n_frames, int n_boxes, int points_per_box,
                                   void *workspace, size_t workspace_bytes, mpsr_stream_t stream)
 {
+    const char *who = "scene_project";
     bool empty;
-    // (total_pixels is pixel_offset_host[n_frames]: read below, once the pointer is known to be there)
-    int st = check_sizes("scene_project", n_frames, 0, n_boxes, points_per_box, &empty);
+    int st = check_sizes(who, n_frames, 0, n_boxes, points_per_box, &empty);
     if (st) return st;
     if (empty) return MPSR_OK;
-    MPSR_REQUIRE(xyz_global && box_frame && box_frame_host, "scene_project: points or box_frame is null");
-    MPSR_REQUIRE(cam_p && frame_hw && frame_hw_host && pixel_offset && pixel_offset_host,
-                 "scene_project: cameras, frame sizes or pixel offsets are null");
-    st = check_frame_tables("scene_project", frame_hw_host, pixel_offset_host, n_frames);
+    long long total_pixels;
+    st = check_render_args(who, xyz_global, box_frame, box_frame_host, cam_p, frame_hw, frame_hw_host, pixel_offset,
+                           pixel_offset_host, n_frames, n_boxes, &total_pixels);
     if (st) return st;
-    const long long total_pixels = pixel_offset_host[n_frames];
-    st = check_sizes("scene_project", n_frames, total_pixels, n_boxes, points_per_box, &empty);
-    if (st) return st;
-    st = check_box_frames("scene_project", box_frame_host, n_boxes, n_frames, 0);
-    if (st) return st;
-    const SceneLayout L = scene_layout(n_frames, total_pixels, n_boxes, points_per_box);
-    st = check_workspace("scene_project", workspace, workspace_bytes, L);
-    if (st) return st;
-
-    char *ws = static_cast<char *>(workspace);
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws + L.keys);
-    int *pix = reinterpret_cast<int *>(ws + L.pix), *frame_box = reinterpret_cast<int *>(ws + L.frame_box);
+    const SceneLayout L(n_frames, total_pixels, n_boxes, points_per_box);
     hipStream_t s = mpsr::as_stream(stream);
-    MPSR_CHECK_HIP(hipMemsetAsync(keys, 0xff, (size_t)total_pixels * sizeof(unsigned long long), s));  // kEmptyKey
-    hipLaunchKernelGGL(frame_box_kernel, dim3((n_frames + 1 + kThreads - 1) / kThreads), dim3(kThreads), 0, s,
-                       box_frame, n_boxes, n_frames, frame_box);
+    st = start_zbuffer(who, workspace, workspace_bytes, L, total_pixels, box_frame, n_boxes, n_frames, s);
+    if (st) return st;
+    char *ws = static_cast<char *>(workspace);
     const long long n = (long long)n_boxes * points_per_box;
     hipLaunchKernelGGL(project_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, xyz_global, valid_mask, box_frame,
-                       box_keep, cam_p, frame_hw, pixel_offset, n, points_per_box, keys, pix);
-    MPSR_CHECK_LAUNCH("scene_project");
+                       box_keep, cam_p, frame_hw, pixel_offset, n, points_per_box,
+                       reinterpret_cast<unsigned long long *>(ws + L.keys), reinterpret_cast<int *>(ws + L.pix));
+    MPSR_CHECK_LAUNCH(who);
     return MPSR_OK;
 }
 
@@ -505,18 +576,9 @@ extern "C" int mpsr_scene_resolve(const int *box_frame, const int *box_frame_hos
     int st = check_sizes("scene_resolve", n_frames, total_pixels, n_boxes, points_per_box, &empty);
     if (st) return st;
     if (empty || total_pixels == 0) return MPSR_OK;
-    MPSR_REQUIRE(box_frame && box_frame_host && depth && instance, "scene_resolve: box_frame or an output is null");
-    st = check_box_frames("scene_resolve", box_frame_host, n_boxes, n_frames, MPSR_INSTANCE_MAX_BOXES);
-    if (st) return st;
-    const SceneLayout L = scene_layout(n_frames, total_pixels, n_boxes, points_per_box);
-    st = check_workspace("scene_resolve", workspace, workspace_bytes, L);
-    if (st) return st;
-    const char *ws = static_cast<const char *>(workspace);
-    hipLaunchKernelGGL(resolve_kernel, dim3(grid_for(total_pixels)), dim3(kThreads), 0, mpsr::as_stream(stream),
-                       reinterpret_cast<const unsigned long long *>(ws + L.keys), total_pixels, box_frame,
-                       reinterpret_cast<const int *>(ws + L.frame_box), points_per_box, depth, instance);
-    MPSR_CHECK_LAUNCH("scene_resolve");
-    return MPSR_OK;
+    return resolve("scene_resolve", box_frame, box_frame_host, n_frames, total_pixels, n_boxes,
+                   (unsigned)points_per_box, workspace, workspace_bytes,
+                   SceneLayout(n_frames, total_pixels, n_boxes, points_per_box), depth, instance, nullptr, stream);
 }
 
 extern "C" int mpsr_scene_compact(const float *xyz_global, const int *box_frame, const float *const *images,
@@ -533,8 +595,8 @@ extern "C" int mpsr_scene_compact(const float *xyz_global, const int *box_frame,
     MPSR_REQUIRE(xyz && box && pixel && frame_offset && kept_per_box && visible_per_box,
                  "scene_compact: an output is null");
     MPSR_REQUIRE((images == nullptr) == (rgb == nullptr), "scene_compact: images and rgb go together (both or neither)");
-    const SceneLayout L = scene_layout(n_frames, total_pixels, n_boxes, points_per_box);
-    st = check_workspace("scene_compact", workspace, workspace_bytes, L);
+    const SceneLayout L(n_frames, total_pixels, n_boxes, points_per_box);
+    st = check_workspace("scene_compact", workspace, workspace_bytes, L.total);
     if (st) return st;
     char *ws = static_cast<char *>(workspace);
     const unsigned long long *keys = reinterpret_cast<const unsigned long long *>(ws + L.keys);
@@ -573,21 +635,17 @@ extern "C" int mpsr_scene_score(const float *xyz_global, const int *box_frame, c
     MPSR_REQUIRE(counts && sums, "scene_score: an output is null");
     st = check_box_frames("scene_score", box_frame_host, n_boxes, n_frames, 0);
     if (st) return st;
-    const SceneLayout L = scene_layout(n_frames, total_pixels, n_boxes, points_per_box);
-    st = check_workspace("scene_score", workspace, workspace_bytes, L);
+    const SceneLayout L(n_frames, total_pixels, n_boxes, points_per_box);
+    st = check_workspace("scene_score", workspace, workspace_bytes, L.total);
     if (st) return st;
-    const size_t need = mpsr_scene_score_scratch_bytes(n_frames);
-    if (!scratch || scratch_bytes < need)
-        return mpsr::fail(MPSR_ERR_WORKSPACE, "scene_score: scratch %zu bytes < %zu", scratch_bytes, need);
+    hipStream_t s = mpsr::as_stream(stream);
+    st = launch_hist("scene_score", gt_instance, pixel_offset, n_frames, total_pixels, scratch, scratch_bytes, s);
+    if (st) return st;
     const char *ws = static_cast<const char *>(workspace);
     const unsigned long long *keys = reinterpret_cast<const unsigned long long *>(ws + L.keys);
     const int *pix = reinterpret_cast<const int *>(ws + L.pix);
-    int *hist = static_cast<int *>(scratch);
-    hipStream_t s = mpsr::as_stream(stream);
-    st = launch_hist(gt_instance, pixel_offset, n_frames, total_pixels, hist, s);
-    if (st) return st;
     hipLaunchKernelGGL(score_kernel, dim3(n_boxes), dim3(kThreads), 0, s, keys, pix, box_frame, box_gt_id, gt_depth,
-                       gt_instance, pixel_offset, hist, points_per_box, counts, sums);
+                       gt_instance, pixel_offset, static_cast<const int *>(scratch), points_per_box, counts, sums);
     MPSR_CHECK_LAUNCH("scene_score");
     return MPSR_OK;
 }
@@ -601,9 +659,9 @@ extern "C" int mpsr_scene_score(const float *xyz_global, const int *box_frame, c
 //   depth in fp64 and lowers the pixel's key ((uint64) float_bits(depth) << 32 | triangle id) with the unsigned
 //   atomicMin.  Per box it counts the drawn triangles and takes the bounding rectangle of their clamped extents:
 //   integer atomics, one set per wave where the wave's triangles are of one box.
-// mpsr_scene_surface_resolve: keys -> depth, instance and (optionally) triangle id maps.
+// mpsr_scene_surface_resolve: keys -> depth, instance and (optionally) triangle id maps, by the points' resolve_kernel.
 // mpsr_scene_surface_score: hist_kernel, then one workgroup per box over the box's rectangle, row-major in slices of
-//   256 pixels, reduced as score_kernel reduces.
+//   256 pixels, summed and reduced by score_kernel's add_depth_error and block_tally.
 
 namespace {
 
@@ -635,14 +693,9 @@ __global__ void __launch_bounds__(kThreads) surface_vertex_kernel(const float *_
             box_rect[4 * i] = box_rect[4 * i + 1] = INT_MAX;      // min col, min row
             box_rect[4 * i + 2] = box_rect[4 * i + 3] = INT_MIN;  // max col, max row
         }
-        const int b = (int)(i / points_per_box);
-        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
         int2 v = make_int2(kNoVertex, 0);
-        const bool on = (box_keep == nullptr || box_keep[b] != 0) && (valid_mask == nullptr || valid_mask[i] > 0.0f) &&
-                        isfinite(x) && isfinite(y) && isfinite(z) && z > 0.0f;
-        if (on) {
-            double u[3];
-            rows3(cam_p + 12 * box_frame[b], (double)x, (double)y, (double)z, u);
+        double u[3];
+        if (alive(xyz, valid_mask, box_frame, box_keep, cam_p, i, (int)(i / points_per_box), u)) {
             const double c = u[0] / u[2], r = u[1] / u[2];
             // NaN fails both range tests
             if (u[2] > 0.0 && fabs(c) < kMaxScreen && fabs(r) < kMaxScreen)
@@ -756,32 +809,6 @@ __global__ void __launch_bounds__(kThreads) surface_triangle_kernel(const float 
     }
 }
 
-__global__ void __launch_bounds__(kThreads) surface_resolve_kernel(const unsigned long long *__restrict__ keys,
-                                                                   long long total_pixels,
-                                                                   const int *__restrict__ box_frame,
-                                                                   const int *__restrict__ frame_box,
-                                                                   unsigned tris_per_box, float *__restrict__ depth,
-                                                                   unsigned char *__restrict__ instance,
-                                                                   int *__restrict__ tri)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total_pixels;
-         i += (long long)gridDim.x * blockDim.x) {
-        const unsigned long long key = keys[i];
-        float d = 0.0f;
-        unsigned char id = 255;
-        int t = -1;
-        if (key != kEmptyKey) {
-            d = __uint_as_float((unsigned)(key >> 32));
-            t = (int)(unsigned)key;
-            const int b = (int)((unsigned)key / tris_per_box);
-            id = (unsigned char)(b - frame_box[box_frame[b]]);
-        }
-        depth[i] = d;
-        instance[i] = id;
-        if (tri) tri[i] = t;
-    }
-}
-
 // one workgroup per box: counts[b][5] = tris, pred_px, inter_px, gt_px, depth_n and sums[b][3] = the sums of e, |e| and
 // e * e over the depth_n pixels, e = (double) rendered depth - (double) ground-truth depth.  The box's rectangle is
 // walked row-major in slices of 256 pixels.
@@ -797,8 +824,6 @@ __global__ void __launch_bounds__(kThreads) surface_score_kernel(const unsigned 
                                                                  const int *__restrict__ hist, unsigned tris_per_box,
                                                                  int *__restrict__ counts, double *__restrict__ sums)
 {
-    __shared__ int part[3][kWaves];
-    __shared__ double dpart[3][kWaves];
     const int b = blockIdx.x, f = box_frame[b], g = box_gt_id ? box_gt_id[b] : -1;  // (null: no ground truth at all)
     const bool has_gt = g >= 0 && g <= 254;
     const unsigned long long *fkeys = keys + pixel_offset[f];
@@ -809,8 +834,8 @@ __global__ void __launch_bounds__(kThreads) surface_score_kernel(const unsigned 
     const int c1 = box_rect[4 * (long long)b + 2], r1 = box_rect[4 * (long long)b + 3];
     const long long rw = c0 <= c1 ? (long long)c1 - c0 + 1 : 0;
     const long long area = r0 <= r1 ? rw * ((long long)r1 - r0 + 1) : 0;
-    int n[3] = {0, 0, 0};           // per wave: every lane holds its wave's counts
-    double s[3] = {0.0, 0.0, 0.0};  // per thread, in slice order
+    int n[3] = {0, 0, 0};           // pred_px, inter_px, depth_n
+    double s[3] = {0.0, 0.0, 0.0};  // in slice order
     for (long long q0 = 0; q0 < area; q0 += kThreads) {
         const long long q = q0 + threadIdx.x;
         bool mine = false, inter = false, measured = false;
@@ -819,75 +844,39 @@ __global__ void __launch_bounds__(kThreads) surface_score_kernel(const unsigned 
             const unsigned long long key = fkeys[at];
             mine = key != kEmptyKey && (unsigned)key / tris_per_box == (unsigned)b;
             inter = mine && has_gt && (int)inst[at] == g;
-            if (inter) {
-                const float d = depth[at];
-                if (isfinite(d) && d > 0.0f) {
-                    measured = true;
-                    const double e = (double)__uint_as_float((unsigned)(key >> 32)) - (double)d;
-                    s[0] += e;
-                    s[1] += fabs(e);
-                    s[2] += e * e;
-                }
-            }
+            measured = inter && add_depth_error(key, depth[at], s);
         }
         n[0] += __popcll(__ballot(mine));
         n[1] += __popcll(__ballot(inter));
         n[2] += __popcll(__ballot(measured));
     }
-    for (int k = 0; k < 3; ++k)
-        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_down(s[k], o);  // lane l += lane l + o: a fixed tree
-    if ((threadIdx.x & 63) == 0) {
-        for (int k = 0; k < 3; ++k) part[k][threadIdx.x >> 6] = n[k];
-        for (int k = 0; k < 3; ++k) dpart[k][threadIdx.x >> 6] = s[k];
-    }
-    __syncthreads();
+    block_tally<3, 3>(n, s);
     if (threadIdx.x == 0) {
-        int c[3] = {0, 0, 0};
-        double t[3] = {0.0, 0.0, 0.0};
-        for (int v = 0; v < kWaves; ++v) {  // in wave order
-            for (int k = 0; k < 3; ++k) c[k] += part[k][v];
-            for (int k = 0; k < 3; ++k) t[k] += dpart[k][v];
-        }
         int *out = counts + 5 * (long long)b;
         out[0] = box_tris[b];
-        out[1] = c[0];
-        out[2] = c[1];
+        out[1] = n[0];
+        out[2] = n[1];
         out[3] = has_gt ? hist[256 * (long long)f + g] : 0;
-        out[4] = c[2];
-        for (int k = 0; k < 3; ++k) sums[3 * (long long)b + k] = t[k];
+        out[4] = n[2];
+        for (int k = 0; k < 3; ++k) sums[3 * (long long)b + k] = s[k];
     }
 }
 
-// workspace: [keys: one uint64 per pixel] [vert: one int2 per map point] [frame_box: n_frames + 1 ints]
-// [box_tris: n_boxes ints] [box_rect: n_boxes x 4 ints]
-struct SurfaceLayout {
-    size_t keys, vert, frame_box, box_tris, box_rect, total;
+// the surfaces' workspace: ... [vert: one int2 per map point] [box_tris: n_boxes ints] [box_rect: n_boxes x 4 ints]
+struct SurfaceLayout : ZLayout {
+    size_t vert, box_tris, box_rect;
+
+    SurfaceLayout(int n_frames, long long total_pixels, int n_boxes, int map_h, int map_w)
+        : ZLayout(n_frames, total_pixels)
+    {
+        vert = take((size_t)n_boxes * map_h * map_w * sizeof(int2));
+        box_tris = take((size_t)n_boxes * sizeof(int));
+        box_rect = take((size_t)n_boxes * 4 * sizeof(int));
+    }
 };
 
-SurfaceLayout surface_layout(int n_frames, long long total_pixels, int n_boxes, int map_h, int map_w)
-{
-    SurfaceLayout L;
-    size_t o = 0;
-    L.keys = o;
-    o += mpsr::align_up((size_t)total_pixels * sizeof(unsigned long long), 256);
-    L.vert = o;
-    o += mpsr::align_up((size_t)n_boxes * map_h * map_w * sizeof(int2), 256);
-    L.frame_box = o;
-    o += mpsr::align_up(((size_t)n_frames + 1) * sizeof(int), 256);
-    L.box_tris = o;
-    o += mpsr::align_up((size_t)n_boxes * sizeof(int), 256);
-    L.box_rect = o;
-    o += mpsr::align_up((size_t)n_boxes * 4 * sizeof(int), 256);
-    L.total = o;
-    return L;
-}
-
-long long surface_tris(int n_boxes, int map_h, int map_w)
-{
-    return 2LL * n_boxes * ((long long)(map_h - 1) * (map_w - 1));  // (n_boxes and the cells each below 2^31)
-}
-
-unsigned tris_of_a_box(int map_h, int map_w) { return 2u * (unsigned)(map_h - 1) * (unsigned)(map_w - 1); }
+// the triangles of a box: two to a cell (below 2^32, as a map has at most INT_MAX points)
+long long tris_per_box(int map_h, int map_w) { return 2LL * (map_h - 1) * (map_w - 1); }
 
 // the sizes every surface entry point takes; *empty: nothing to do
 int check_surface_sizes(const char *who, int n_frames, long long total_pixels, int n_boxes, int map_h, int map_w,
@@ -897,16 +886,9 @@ int check_surface_sizes(const char *who, int n_frames, long long total_pixels, i
                  "%s: a map of %d x %d has no cell (map_h and map_w must be 2 or more)", who, map_h, map_w);
     int st = check_sizes(who, n_frames, total_pixels, n_boxes, 1, empty);
     if (st) return st;
-    MPSR_REQUIRE(surface_tris(n_boxes, map_h, map_w) < (1LL << 32),
+    MPSR_REQUIRE(n_boxes * tris_per_box(map_h, map_w) < (1LL << 32),
                  "%s: %d boxes of %d x %d cells: the triangle id does not fit the key's 32 bits", who, n_boxes,
                  map_h - 1, map_w - 1);
-    return MPSR_OK;
-}
-
-int check_surface_workspace(const char *who, const void *workspace, size_t workspace_bytes, const SurfaceLayout &L)
-{
-    if (!workspace || workspace_bytes < L.total)
-        return mpsr::fail(MPSR_ERR_WORKSPACE, "%s: workspace %zu bytes < %zu", who, workspace_bytes, L.total);
     return MPSR_OK;
 }
 
@@ -917,8 +899,8 @@ extern "C" size_t mpsr_scene_surface_workspace_bytes(int n_frames, long long tot
 {
     if (n_frames <= 0 || total_pixels <= 0 || n_boxes <= 0 || map_h < 2 || map_w < 2) return 0;
     if ((long long)map_h * map_w > INT_MAX || total_pixels > (1LL << 40)) return 0;
-    if (surface_tris(n_boxes, map_h, map_w) >= (1LL << 32)) return 0;
-    return surface_layout(n_frames, total_pixels, n_boxes, map_h, map_w).total;
+    if (n_boxes * tris_per_box(map_h, map_w) >= (1LL << 32)) return 0;
+    return SurfaceLayout(n_frames, total_pixels, n_boxes, map_h, map_w).total;
 }
 
 extern "C" int mpsr_scene_surface_render(const float *xyz_global, const float *valid_mask, const int *box_frame,
@@ -937,38 +919,26 @@ extern "C" int mpsr_scene_surface_render(const float *xyz_global, const float *v
     MPSR_REQUIRE(max_edge_dz > 0.0f, "%s: max_edge_dz %g must be greater than 0 (+inf: no limit)", who,
                  (double)max_edge_dz);  // NaN fails the comparison
     if (empty) return MPSR_OK;
-    MPSR_REQUIRE(xyz_global && box_frame && box_frame_host, "%s: points or box_frame is null", who);
-    MPSR_REQUIRE(cam_p && frame_hw && frame_hw_host && pixel_offset && pixel_offset_host,
-                 "%s: cameras, frame sizes or pixel offsets are null", who);
-    st = check_frame_tables(who, frame_hw_host, pixel_offset_host, n_frames);
+    long long total_pixels;
+    st = check_render_args(who, xyz_global, box_frame, box_frame_host, cam_p, frame_hw, frame_hw_host, pixel_offset,
+                           pixel_offset_host, n_frames, n_boxes, &total_pixels);
     if (st) return st;
-    const long long total_pixels = pixel_offset_host[n_frames];
-    st = check_surface_sizes(who, n_frames, total_pixels, n_boxes, map_h, map_w, &empty);
-    if (st) return st;
-    st = check_box_frames(who, box_frame_host, n_boxes, n_frames, 0);
-    if (st) return st;
-    const SurfaceLayout L = surface_layout(n_frames, total_pixels, n_boxes, map_h, map_w);
-    st = check_surface_workspace(who, workspace, workspace_bytes, L);
-    if (st) return st;
-
-    char *ws = static_cast<char *>(workspace);
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws + L.keys);
-    int2 *vert = reinterpret_cast<int2 *>(ws + L.vert);
-    int *frame_box = reinterpret_cast<int *>(ws + L.frame_box);
-    int *box_tris = reinterpret_cast<int *>(ws + L.box_tris), *box_rect = reinterpret_cast<int *>(ws + L.box_rect);
+    const SurfaceLayout L(n_frames, total_pixels, n_boxes, map_h, map_w);
     hipStream_t s = mpsr::as_stream(stream);
-    MPSR_CHECK_HIP(hipMemsetAsync(keys, 0xff, (size_t)total_pixels * sizeof(unsigned long long), s));  // kEmptyKey
-    hipLaunchKernelGGL(frame_box_kernel, dim3((n_frames + 1 + kThreads - 1) / kThreads), dim3(kThreads), 0, s,
-                       box_frame, n_boxes, n_frames, frame_box);
+    st = start_zbuffer(who, workspace, workspace_bytes, L, total_pixels, box_frame, n_boxes, n_frames, s);
+    if (st) return st;
+    char *ws = static_cast<char *>(workspace);
+    int2 *vert = reinterpret_cast<int2 *>(ws + L.vert);
+    int *box_tris = reinterpret_cast<int *>(ws + L.box_tris), *box_rect = reinterpret_cast<int *>(ws + L.box_rect);
     const int points_per_box = map_h * map_w;
     const long long n = (long long)n_boxes * points_per_box;  // n >= n_boxes: the vertex pass resets the box tables
     hipLaunchKernelGGL(surface_vertex_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, xyz_global, valid_mask,
                        box_frame, box_keep, cam_p, n, points_per_box, n_boxes, vert, box_tris, box_rect);
-    const long long n_tris = surface_tris(n_boxes, map_h, map_w);
+    const long long n_tris = n_boxes * tris_per_box(map_h, map_w);
     hipLaunchKernelGGL(surface_triangle_kernel, dim3(grid_for(n_tris)), dim3(kThreads), 0, s, xyz_global, vert,
-                       box_frame, frame_hw, pixel_offset, n_tris, map_h, map_w, max_edge_dz, max_span_px, keys,
-                       box_tris, box_rect);
-    MPSR_CHECK_LAUNCH("scene_surface_render");
+                       box_frame, frame_hw, pixel_offset, n_tris, map_h, map_w, max_edge_dz, max_span_px,
+                       reinterpret_cast<unsigned long long *>(ws + L.keys), box_tris, box_rect);
+    MPSR_CHECK_LAUNCH(who);
     return MPSR_OK;
 }
 
@@ -982,19 +952,9 @@ extern "C" int mpsr_scene_surface_resolve(const int *box_frame, const int *box_f
     int st = check_surface_sizes(who, n_frames, total_pixels, n_boxes, map_h, map_w, &empty);
     if (st) return st;
     if (empty || total_pixels == 0) return MPSR_OK;
-    MPSR_REQUIRE(box_frame && box_frame_host && depth && instance, "%s: box_frame or an output is null", who);
-    st = check_box_frames(who, box_frame_host, n_boxes, n_frames, MPSR_INSTANCE_MAX_BOXES);
-    if (st) return st;
-    const SurfaceLayout L = surface_layout(n_frames, total_pixels, n_boxes, map_h, map_w);
-    st = check_surface_workspace(who, workspace, workspace_bytes, L);
-    if (st) return st;
-    const char *ws = static_cast<const char *>(workspace);
-    hipLaunchKernelGGL(surface_resolve_kernel, dim3(grid_for(total_pixels)), dim3(kThreads), 0,
-                       mpsr::as_stream(stream), reinterpret_cast<const unsigned long long *>(ws + L.keys),
-                       total_pixels, box_frame, reinterpret_cast<const int *>(ws + L.frame_box),
-                       tris_of_a_box(map_h, map_w), depth, instance, tri);
-    MPSR_CHECK_LAUNCH("scene_surface_resolve");
-    return MPSR_OK;
+    return resolve(who, box_frame, box_frame_host, n_frames, total_pixels, n_boxes,
+                   (unsigned)tris_per_box(map_h, map_w), workspace, workspace_bytes,
+                   SurfaceLayout(n_frames, total_pixels, n_boxes, map_h, map_w), depth, instance, tri, stream);
 }
 
 extern "C" int mpsr_scene_surface_score(const int *box_frame, const int *box_frame_host, const int *box_gt_id,
@@ -1018,24 +978,20 @@ extern "C" int mpsr_scene_surface_score(const int *box_frame, const int *box_fra
     MPSR_REQUIRE(counts && sums, "%s: an output is null", who);
     st = check_box_frames(who, box_frame_host, n_boxes, n_frames, 0);
     if (st) return st;
-    const SurfaceLayout L = surface_layout(n_frames, total_pixels, n_boxes, map_h, map_w);
-    st = check_surface_workspace(who, workspace, workspace_bytes, L);
+    const SurfaceLayout L(n_frames, total_pixels, n_boxes, map_h, map_w);
+    st = check_workspace(who, workspace, workspace_bytes, L.total);
     if (st) return st;
-    const size_t need = mpsr_scene_score_scratch_bytes(n_frames);
-    if (with_gt && (!scratch || scratch_bytes < need))
-        return mpsr::fail(MPSR_ERR_WORKSPACE, "%s: scratch %zu bytes < %zu", who, scratch_bytes, need);
-    const char *ws = static_cast<const char *>(workspace);
-    int *hist = static_cast<int *>(scratch);
     hipStream_t s = mpsr::as_stream(stream);
     if (with_gt) {
-        st = launch_hist(gt_instance, pixel_offset, n_frames, total_pixels, hist, s);
+        st = launch_hist(who, gt_instance, pixel_offset, n_frames, total_pixels, scratch, scratch_bytes, s);
         if (st) return st;
     }
+    const char *ws = static_cast<const char *>(workspace);
     hipLaunchKernelGGL(surface_score_kernel, dim3(n_boxes), dim3(kThreads), 0, s,
                        reinterpret_cast<const unsigned long long *>(ws + L.keys),
                        reinterpret_cast<const int *>(ws + L.box_tris), reinterpret_cast<const int *>(ws + L.box_rect),
-                       box_frame, box_gt_id, gt_depth, gt_instance, frame_hw, pixel_offset, hist,
-                       tris_of_a_box(map_h, map_w), counts, sums);
-    MPSR_CHECK_LAUNCH("scene_surface_score");
+                       box_frame, box_gt_id, gt_depth, gt_instance, frame_hw, pixel_offset,
+                       static_cast<const int *>(scratch), (unsigned)tris_per_box(map_h, map_w), counts, sums);
+    MPSR_CHECK_LAUNCH(who);
     return MPSR_OK;
 }
