@@ -963,6 +963,50 @@ int mpsr_metric_stats(const float *values, const int *frame, int n_rows, int n_c
                       int n_metrics, int n_frames, int nan_rule, int *frame_flags, double *stats,
                       mpsr_stream_t stream);
 
+/* ---- Each predicted box against its own label (additive to ABI 13) ----
+ * n objects, one lane each, every value widened from float32 to fp64 first.  pred_box_3d and gt_box_3d (n, 7)
+ * [x y z l w h ry], y on the bottom face: the first seven columns of mpsr_format_boxes' box_3d and the label's
+ * boxes_3d row.  fed_box_2d (n, 4) [y1 x1 y2 x2], the box the network was fed, or null.  label_info (n, 6)
+ * [truncation, occlusion, x1, y1, x2, y2] of the KITTI label itself, or null.  depth_edges and box_iou_edges are HOST
+ * arrays of at most MPSR_OBJECT_PAIRS_MAX_EDGES finite, strictly increasing doubles (a count of 0: one bin).
+ * overlaps (n, 4) fp64: iou_2d_fed = mpsr_kitti_overlaps' image IoU of the fed box against the label's own box (NaN
+ * when either pointer is null or one of the eight values is not finite); iou_bev and iou_3d = that entry point's BEV
+ * and 3-D IoU (criterion -1, the same arithmetic: exact polygon clipping, non-positive l / w, or l / w / h, give 0);
+ * centre_dist = sqrt((dx dx + dy dy) + dz dz) between the box centres, y at half height.  A field among the two 3-D
+ * boxes that is not finite makes the last three NaN.
+ * table (n, 9) float32: those four rounded, then hit3d_70, hit3d_50, hit3d_25, hitbev_70, hitbev_50: 1.0 or 0.0 from
+ * `>=` on the fp64 IoU, NaN where the IoU is NaN.
+ * bins (n, 3) int32: depth = the number of depth_edges <= the label's z (a z on an edge goes to the upper bin; -1
+ * when z is not finite); difficulty = the KITTI program's level of the label's own box, height y2 - y1 in fp64:
+ * 0 height > 40, occlusion <= 0, truncation <= 0.15; 1 height > 25, <= 1, <= 0.3; 2 height > 25, <= 2, <= 0.5;
+ * otherwise 3 (-1 when label_info is null or one of the row's six values is not finite); the truncation limits are
+ * taken rounded to float32, as the truncation itself arrives, so that a label on a limit stays on it; fed_box = the number of
+ * box_iou_edges <= iou_2d_fed (-1 when that is NaN).
+ * Every output element is written on every call; n == 0 is a no-op.  Argument errors (negative n, a null box or
+ * output pointer with n > 0, edges that are too many, not finite or not increasing) are reported before any launch.
+ * DESIGN.md section 7.11. */
+#define MPSR_OBJECT_PAIRS_MAX_EDGES 15
+int mpsr_object_pairs(const float *pred_box_3d, const float *gt_box_3d, const float *fed_box_2d,
+                      const float *label_info, int n, const double *depth_edges, int n_depth_edges,
+                      const double *box_iou_edges, int n_box_iou_edges, double *overlaps, float *table, int *bins,
+                      mpsr_stream_t stream);
+
+/* mpsr_metric_stats under MPSR_NAN_RULE_ENTRY for several sets of rows ("slots") in one launch.  values, n_rows,
+ * n_cols, column_metric (HOST) and n_metrics as there.  bins (n_rows, n_axes) int32: the row's bin on every axis;
+ * axis_bins (n_axes) is a HOST array, the number of bins of each axis.  n_axes <= MPSR_METRIC_STATS_MAX_AXES, the sum
+ * of axis_bins <= MPSR_METRIC_STATS_MAX_BINS: more is an argument error, nothing is truncated.
+ * stats (1 + sum of axis_bins, n_metrics, 6) fp64, the six statistics of mpsr_metric_stats per (slot, metric): slot 0
+ * is every row, then axis 0's bins, axis 1's bins, ...  A row whose index on an axis is negative or >= axis_bins[a] is
+ * in none of that axis' bins (and still in slot 0); a row outside a slot is neither counted nor dropped there.  A
+ * slot without a value has count 0 and NaN in the four statistics.  Every element is written on every call.
+ * One workgroup per (slot, metric), each with mpsr_metric_stats' element-to-thread assignment and summation tree, no
+ * atomics: slot 0 holds the bits mpsr_metric_stats returns for the same table under MPSR_NAN_RULE_ENTRY, and two calls
+ * return the same bits.  bins may be null when no axis has a bin.  DESIGN.md section 7.11. */
+#define MPSR_METRIC_STATS_MAX_AXES 4
+#define MPSR_METRIC_STATS_MAX_BINS 64
+int mpsr_metric_stats_binned(const float *values, const int *bins, int n_rows, int n_cols, const int *column_metric,
+                             int n_metrics, int n_axes, const int *axis_bins, double *stats, mpsr_stream_t stream);
+
 /* ---- One step's row of the training log (additive to ABI 13) ----
  * Writes row `row` of the caller-owned table rows (n_rows, n_cols) float32, row-major, n_cols == n_terms +
  * MPSR_TRAIN_LOG_STAT_COLS, and steps[row] = step (steps: n_rows int64); no other element of either is touched.  One

@@ -220,6 +220,10 @@ SIGNATURES = {
                                     ctypes.c_double, c_i, c_f, c_f, c_f, c_f]),
     "mpsr_kitti_detection_rows": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, ctypes.c_double, c_i, c_f, c_f, c_f, c_f]),
     "mpsr_metric_stats": (c_i, [c_f, c_f, c_i, c_i, ctypes.POINTER(c_i), c_i, c_i, c_i, c_f, c_f, c_f]),
+    "mpsr_object_pairs": (c_i, [c_f, c_f, c_f, c_f, c_i, ctypes.POINTER(ctypes.c_double), c_i,
+                                ctypes.POINTER(ctypes.c_double), c_i, c_f, c_f, c_f, c_f]),
+    "mpsr_metric_stats_binned": (c_i, [c_f, c_f, c_i, c_i, ctypes.POINTER(c_i), c_i, c_i, ctypes.POINTER(c_i), c_f,
+                                       c_f]),
     "mpsr_train_log_append": (c_i, [TrainLogTerms, c_i, c_f, c_i, ctypes.c_float, ctypes.c_float, ctypes.c_longlong, c_f,
                                     c_f, c_i, c_i, c_i, c_f]),
     "mpsr_scene_workspace_bytes": (c_sz, [c_i, ctypes.c_longlong, c_i, c_i]),

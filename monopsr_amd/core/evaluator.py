@@ -48,7 +48,18 @@ scene_reconstruction.render_instance_surfaces with its default max_edge_dz and m
 same ground truth: result['surface_stats'] over scene_reconstruction.SURFACE_METRIC_NAMES, and with predictions_base_dir
 one line in metrics/<split>/surface_metrics_<split>.csv (evaluator_utils.save_surface_stats).
 
-Not built: TF summaries and metrics_to_show, both IoU settings in one pass.
+breakdown: None, or a dict of options ({} for the defaults), 'val' mode only.  With it every
+chunk's predicted boxes (format_boxes' output: the fitted boxes with centroid_fit) are set against their own labels in one
+mpsr_object_pairs launch -- the samples' boxes_3d and boxes_2d and dataset.frame_label_info(rows) -- and the per-object
+table of evaluator_utils.PAIR_COLUMNS stays on the card with each object's bins: the label's depth (depth_edges, default
+10 .. 50 m), its KITTI difficulty and the IoU of the fed 2-D box with the label's own (box_iou_edges, default 0.7, 0.8,
+0.9).  At the end one mpsr_metric_stats_binned launch per table kept ('object' always, 'metrics' with metric_stats,
+'scene' / 'surface' with scene_metrics) and one copy: result['breakdown'] (evaluator_utils.breakdown_dict), and with
+predictions_base_dir metrics/<split>/breakdown_<split>.csv (result['breakdown_csv']).  Bins use NAN_RULE_ENTRY.  The hit
+columns' means are shares of the evaluated labels, not KITTI recall: frames and labels the dataset's filter drops are
+not in the denominator.
+
+Not built: TF summaries and metrics_to_show, both IoU settings in one pass, AP per bin.
 """
 import argparse
 import os
@@ -75,6 +86,10 @@ COLUMN_METRIC = tuple(k for k, (_, width) in enumerate(METRIC_COLUMNS) for _ in 
 
 # what Evaluator(centroid_fit={...}) may hold: instance_metrics.fit_centroids' options
 _CENTROID_FIT_OPTIONS = ('fit_viewing_angle', 'use_pixel_centres', 'cam0_shift')
+
+# what Evaluator(breakdown={...}) may hold, with the defaults
+_BREAKDOWN_OPTIONS = dict(depth_edges=evaluator_utils.DEFAULT_DEPTH_EDGES,
+                          box_iou_edges=evaluator_utils.DEFAULT_BOX_IOU_EDGES)
 
 
 def sweep_checkpoints(checkpoints, evaluated, run, ckpt_indices=None):
@@ -128,7 +143,8 @@ class Evaluator:
 
     def __init__(self, model, dataset, score_threshold=0.1, predictions_base_dir=None, batch_size=8,
                  project_3d_box=False, iou='standard', compute_metrics=True, compute_losses=True, metric_stats=False,
-                 skip_evaluated_checkpoints=True, scene_metrics=False, centroid_fit=None, chunk_hook=None):
+                 skip_evaluated_checkpoints=True, scene_metrics=False, breakdown=None, centroid_fit=None,
+                 chunk_hook=None):
         if iou not in kitti_eval.MIN_OVERLAP:
             raise ValueError('iou must be one of %s' % sorted(kitti_eval.MIN_OVERLAP))
         if int(batch_size) < 1:
@@ -145,6 +161,20 @@ class Evaluator:
             unknown = set(centroid_fit) - set(_CENTROID_FIT_OPTIONS)
             if unknown:
                 raise ValueError('centroid_fit: unknown options %s' % sorted(unknown))
+        if breakdown is not None:
+            if getattr(dataset, 'train_val_test', None) != 'val':
+                raise ValueError("breakdown sets every prediction against its label: it needs a 'val'-mode dataset, "
+                                 "got %r" % (getattr(dataset, 'train_val_test', None),))
+            unknown = set(breakdown) - set(_BREAKDOWN_OPTIONS)
+            if unknown:
+                raise ValueError('breakdown: unknown options %s' % sorted(unknown))
+            breakdown = {k: tuple(float(v) for v in breakdown.get(k, default))
+                         for k, default in _BREAKDOWN_OPTIONS.items()}
+        # None, or {'depth_edges': (...), 'box_iou_edges': (...)}: the per-object overlap table and the binned statistics
+        self.breakdown = breakdown
+        # after a run_once with breakdown: (table (n,9) float32 in evaluator_utils.PAIR_COLUMNS' order, overlaps (n,4)
+        # float64, bins (n,3) int32 in evaluator_utils.BREAKDOWN_AXES' order, frame (n,) int32) on the device
+        self.pair_table = None
         self.model = model
         # None, or a dict of instance_metrics.fit_centroids' options ({} for the defaults): every chunk's centroids are
         # fitted to their 2-D boxes straight after build_batch, and everything below sees the fitted boxes
@@ -182,7 +212,8 @@ class Evaluator:
         [emd, chamfer] x [sum of the entries that are not NaN, their number]; loss names and their sums (n,2) in the
         same form; the metric table (N, 10) float32 in METRIC_COLUMNS' order, or None; with scene_metrics the scene
         scores (table (N,6) float32, counts (N,6) int32, sums (N,3) float64), else None; with scene_metrics='surface'
-        the surface scores in the same form (counts (N,5)), else None), all on the device."""
+        the surface scores in the same form (counts (N,5)), else None; with breakdown the pair table (table (N,9) float32,
+        overlaps (N,4) float64, bins (N,3) int32), else None), all on the device."""
         ds, model = self.dataset, self.model
         dev = ds.device
         # the frames in split order, whatever the epoch's shuffle made of sample_list
@@ -194,7 +225,7 @@ class Evaluator:
         with_table = ds.train_val_test == 'val' and self.metric_stats
         loss_names, loss_sums = [], None
         table = []
-        scene_parts, surface_parts = [], []
+        scene_parts, surface_parts, pair_parts = [], [], []
         self._fits = []
         if with_losses or with_table:
             # the 'val'-mode graph of the same net: method by method, with the ground truth and the offsets
@@ -226,6 +257,7 @@ class Evaluator:
                     if self.surface_metrics:
                         scores = scene.surfaces.scores
                         surface_parts.append((scores.table(), scores.counts, scores.sums))
+                chunk_b3 = []
                 for r, s, o in zip(rows, samples, outs):
                     n = int(s['num_objs'])
                     b3, b2 = instance_utils.format_boxes(
@@ -234,6 +266,7 @@ class Evaluator:
                         s['class_indices'], s['cam_p'], s['rgb_image'].shape, centroid_type=model.centroid_type,
                         post_process_cen_x=model.post_process_cen_x)
                     b3s.append(b3[0:n])
+                    chunk_b3.append(b3[0:n])
                     b2s.append(b2[0:n])
                     frames.append(torch.full((n,), int(r), dtype=torch.int32, device=dev))
                     if with_metrics or with_table:
@@ -268,10 +301,16 @@ class Evaluator:
                         ok = ~torch.isnan(v)
                         loss_sums[:, 0] += torch.where(ok, v, torch.zeros_like(v))
                         loss_sums[:, 1] += ok
+                if self.breakdown is not None:
+                    pair_parts.append(evaluator_utils.object_pairs(
+                        torch.cat(chunk_b3), torch.cat([s['boxes_3d'][0:int(s['num_objs'])] for s in samples]),
+                        torch.cat([s['boxes_2d'][0:int(s['num_objs'])] for s in samples]),
+                        torch.cat(ds.frame_label_info(rows)), **self.breakdown))
         return (torch.cat(b3s), torch.cat(b2s), torch.cat(frames), sums, loss_names, loss_sums,
                 torch.cat(table).contiguous() if with_table else None,
                 tuple(torch.cat(part).contiguous() for part in zip(*scene_parts)) if self.scene_metrics else None,
-                tuple(torch.cat(part).contiguous() for part in zip(*surface_parts)) if self.surface_metrics else None)
+                tuple(torch.cat(part).contiguous() for part in zip(*surface_parts)) if self.surface_metrics else None,
+                tuple(torch.cat(part).contiguous() for part in zip(*pair_parts)) if pair_parts else None)
 
     def _rows_to_host(self, b3, b2, frame):
         """One launch, one compaction, one copy: -> (rows (m,14) float64, class index (m,), frame (m,)) of the kept
@@ -295,7 +334,7 @@ class Evaluator:
 
     def run_once(self, global_step=None):
         ds = self.dataset
-        b3, b2, frame, sums, loss_names, loss_sums, table, scene, surface = self._predict()
+        b3, b2, frame, sums, loss_names, loss_sums, table, scene, surface, pairs = self._predict()
         rows, cls, frame_h = self._rows_to_host(b3, b2, frame)
         names = ds.sample_names
         per_frame = {}
@@ -348,6 +387,31 @@ class Evaluator:
             if self.predictions_base_dir is not None:
                 result[kind + '_metrics_csv'] = save(self.predictions_base_dir, ds.data_split, global_step,
                                                      metric_names, result[kind + '_stats'])
+        if pairs is not None:
+            self.pair_table = pairs + (frame,)
+            axes = [('depth', evaluator_utils.edge_labels(self.breakdown['depth_edges'])),
+                    ('difficulty', evaluator_utils.DIFFICULTY_LABELS),
+                    ('fed_box', evaluator_utils.edge_labels(self.breakdown['box_iou_edges']))]
+            kept = [('object', evaluator_utils.PAIR_COLUMNS, pairs[0], range(len(evaluator_utils.PAIR_COLUMNS)))]
+            if table is not None:
+                kept.append(('metrics', METRIC_NAMES, table, COLUMN_METRIC))
+            for kind, metric_names, parts in (('scene', SCENE_METRIC_NAMES, scene),
+                                              ('surface', SURFACE_METRIC_NAMES, surface)):
+                if parts is not None:
+                    kept.append((kind, metric_names, parts[0], range(len(metric_names))))
+            # one launch per table, one copy for all of them
+            stats = [evaluator_utils.metric_stats_binned(values, pairs[2], column_metric, len(metric_names),
+                                                         [len(labels) for _, labels in axes])
+                     for _, metric_names, values, column_metric in kept]
+            host, at, host_stats = torch.cat([t.reshape(-1) for t in stats]).cpu().numpy(), 0, []
+            for t in stats:
+                host_stats.append(host[at:at + t.numel()].reshape(tuple(t.shape)))
+                at += t.numel()
+            result['breakdown'] = evaluator_utils.breakdown_dict(
+                axes, [(kind, metric_names, st) for (kind, metric_names, _, _), st in zip(kept, host_stats)])
+            if self.predictions_base_dir is not None:
+                result['breakdown_csv'] = evaluator_utils.save_breakdown(self.predictions_base_dir, ds.data_split,
+                                                                         global_step, result['breakdown'])
         if self.predictions_base_dir is not None:
             out_dir = evaluator_utils.kitti_output_dir(self.predictions_base_dir, ds.data_split, self.score_threshold,
                                                        global_step)
@@ -458,6 +522,27 @@ def centroid_fit_options(ap, args):
     if args.fit_viewing_angle and not args.fit_centroids:
         ap.error('--fit-viewing-angle requires --fit-centroids')
     return dict(fit_viewing_angle=args.fit_viewing_angle) if args.fit_centroids else None
+
+
+def add_breakdown_arguments(ap):
+    """run_evaluation's --breakdown, --depth-edges and --box-iou-edges."""
+    ap.add_argument('--breakdown', action='store_true',
+                    help='also score every predicted box against its own label and split every per-object table by '
+                         'depth, KITTI difficulty and the IoU of the fed 2-D box (DESIGN.md section 7.11)')
+    ap.add_argument('--depth-edges', type=float, nargs='+', default=None, metavar='M',
+                    help='the depth bins\' edges in metres (default 10 20 30 40 50)')
+    ap.add_argument('--box-iou-edges', type=float, nargs='+', default=None, metavar='V',
+                    help='the edges of the fed box\'s IoU bins (default 0.7 0.8 0.9)')
+
+
+def breakdown_options(ap, args):
+    """The Evaluator's breakdown of a command line's --breakdown, --depth-edges and --box-iou-edges (None without
+    --breakdown)."""
+    edges = {k: v for k, v in (('depth_edges', args.depth_edges), ('box_iou_edges', args.box_iou_edges))
+             if v is not None}
+    if edges and not args.breakdown:
+        ap.error('--depth-edges and --box-iou-edges require --breakdown')
+    return edges if args.breakdown else None
 
 
 def format_centroid_fit(c):

@@ -17,6 +17,10 @@ straight from format_predictions output (`evaluate_predictions`, through `kitti_
 The metrics CSVs of the reference's save_metrics (evaluator_utils.py:280-403) are written by `save_metric_stats` from
 the statistics `metric_stats` (one mpsr_metric_stats launch) takes of the evaluator's device-resident table.  The
 TensorBoard summaries (evaluator_utils.py:376-456) are out of scope.
+
+`object_pairs` (one mpsr_object_pairs launch) sets each predicted box against its own label, `metric_stats_binned` (one
+mpsr_metric_stats_binned launch) takes the statistics of a per-object table over all rows and per bin of up to four
+axes, and `save_breakdown` writes them in long format.
 """
 import csv
 import os
@@ -139,6 +143,137 @@ def metric_stats_dict(names, stats):
     """{metric name: {count, mean, std, mean_abs, std_abs, dropped}} of a host copy of metric_stats' output."""
     return {name: dict(zip(STAT_NAMES, (int(row[0]), float(row[1]), float(row[2]), float(row[3]), float(row[4]),
                                         int(row[5])))) for name, row in zip(names, stats)}
+
+
+# mpsr_object_pairs' table columns, the axes of its bins and the difficulty axis' labels (KITTI's levels, then the rest)
+PAIR_COLUMNS = ('iou_2d_fed', 'iou_bev', 'iou_3d', 'centre_dist', 'hit3d_70', 'hit3d_50', 'hit3d_25', 'hitbev_70',
+                'hitbev_50')
+BREAKDOWN_AXES = ('depth', 'difficulty', 'fed_box')
+DIFFICULTY_LABELS = ('easy', 'moderate', 'hard', 'beyond')
+DEFAULT_DEPTH_EDGES = (10.0, 20.0, 30.0, 40.0, 50.0)
+DEFAULT_BOX_IOU_EDGES = (0.7, 0.8, 0.9)
+MAX_EDGES, MAX_AXES, MAX_BINS = 15, 4, 64  # MPSR_OBJECT_PAIRS_MAX_EDGES, MPSR_METRIC_STATS_MAX_AXES / _MAX_BINS
+
+
+def edge_labels(edges):
+    """The labels of the len(edges) + 1 bins that increasing edges cut: '<10', '10-20', ..., '>=50' ('all' for none)."""
+    e = ['%g' % float(v) for v in edges]
+    if not e:
+        return ['all']
+    return ['<' + e[0]] + ['%s-%s' % (a, b) for a, b in zip(e[:-1], e[1:])] + ['>=' + e[-1]]
+
+
+def object_pairs(pred_box_3d, gt_box_3d, fed_box_2d=None, label_info=None, depth_edges=DEFAULT_DEPTH_EDGES,
+                 box_iou_edges=DEFAULT_BOX_IOU_EDGES):
+    """Each predicted box against its own label in one mpsr_object_pairs launch (include/monopsr_hip.h).  pred_box_3d and
+    gt_box_3d (n, 7) [x y z l w h ry] float32 CUDA tensors (more columns, as format_boxes' (n, 9), are cut off);
+    fed_box_2d (n, 4) [y1 x1 y2 x2] and label_info (n, 6) [truncation, occlusion, x1, y1, x2, y2] float32, or None.
+    -> (table (n, 9) float32 in PAIR_COLUMNS' order, overlaps (n, 4) float64: its first four columns unrounded,
+    bins (n, 3) int32 in BREAKDOWN_AXES' order) on the device."""
+    import ctypes
+    import torch
+    from monopsr_amd import _lib
+    n = int(pred_box_3d.shape[0]) if pred_box_3d.dim() == 2 else -1
+
+    given = (('pred_box_3d', pred_box_3d, 7), ('gt_box_3d', gt_box_3d, 7), ('fed_box_2d', fed_box_2d, 4),
+             ('label_info', label_info, 6))
+    for name, t, width in given:
+        if t is not None and (t.dim() != 2 or int(t.shape[0]) != n or t.dtype != torch.float32 or
+                              (int(t.shape[1]) < width if width == 7 else int(t.shape[1]) != width)):
+            raise ValueError('object_pairs: %s must be (%d, %d) float32, got %s %s' % (name, n, width, tuple(t.shape),
+                                                                                      t.dtype))
+    for name, t, width in given:
+        _lib.ptr(None if t is None else t[0:0])  # (refuses tensors that are not on the GPU)
+    pred, gt, fed, info = (None if t is None else t[:, 0:width].contiguous() for _, t, width in given)
+    de, ie = [float(v) for v in depth_edges], [float(v) for v in box_iou_edges]
+    dev = pred.device
+    with torch.cuda.device(dev):
+        table = torch.empty((n, 9), dtype=torch.float32, device=dev)
+        overlaps = torch.empty((n, 4), dtype=torch.float64, device=dev)
+        bins = torch.empty((n, 3), dtype=torch.int32, device=dev)
+        p = _lib.ptr
+        _lib.check(_lib.lib().mpsr_object_pairs(
+            p(pred), p(gt), p(fed), p(info), n, (ctypes.c_double * max(len(de), 1))(*de), len(de),
+            (ctypes.c_double * max(len(ie), 1))(*ie), len(ie), p(overlaps), p(table), p(bins), _lib.stream()))
+    return table, overlaps, bins
+
+
+def metric_stats_binned(values, bins, column_metric, n_metrics, axis_bins, out=None):
+    """metric_stats under NAN_RULE_ENTRY of every row and of every bin of every axis in one mpsr_metric_stats_binned
+    launch.  values (n_rows, n_cols) float32 and bins (n_rows, n_axes) int32 CUDA tensors; axis_bins: the number of
+    bins per axis.  A row whose index on an axis is outside [0, axis_bins[a]) is in none of that axis' bins.
+    -> (1 + sum(axis_bins), n_metrics, 6) float64 on the device, columns STAT_NAMES: slot 0 is every row (the bits of
+    metric_stats(..., NAN_RULE_ENTRY)), then axis 0's bins, axis 1's, ...; `out` is written when given."""
+    import ctypes
+    import torch
+    from monopsr_amd import _lib
+    column_metric, axis_bins = [int(c) for c in column_metric], [int(b) for b in axis_bins]
+    n_rows, n_cols = (int(v) for v in values.shape) if values.dim() == 2 else (-1, -1)
+    if values.dtype != torch.float32 or n_cols != len(column_metric) or bins.dtype != torch.int32 \
+            or tuple(bins.shape) != (n_rows, len(axis_bins)):
+        raise ValueError('metric_stats_binned: values (n_rows, %d) float32 and bins (n_rows, %d) int32, got %s %s and '
+                         '%s %s' % (len(column_metric), len(axis_bins), tuple(values.shape), values.dtype,
+                                    tuple(bins.shape), bins.dtype))
+    dev = values.device
+    _lib.ptr(values), _lib.ptr(bins)  # (refuses tensors that are not on the GPU)
+    shape = (1 + max(sum(axis_bins), 0), int(n_metrics), 6)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != torch.float64:
+            raise ValueError('metric_stats_binned: out must be %s float64' % (shape,))
+        p = _lib.ptr
+        _lib.check(_lib.lib().mpsr_metric_stats_binned(
+            p(values), p(bins), n_rows, n_cols, (ctypes.c_int * max(n_cols, 1))(*column_metric), int(n_metrics),
+            len(axis_bins), (ctypes.c_int * max(len(axis_bins), 1))(*axis_bins), p(out), _lib.stream()))
+    return out
+
+
+def breakdown_dict(axes, tables):
+    """result['breakdown'] of host copies of metric_stats_binned's output.  axes: [(axis, [bin labels])] in the order of
+    the bins' columns; tables: [(table, metric names, stats (1 + the number of labels, n_metrics, 6))].
+    -> {'axes': {axis: [labels]}, 'all': {table: {metric: statistics}}, 'tables': {table: {axis: {label: {metric:
+    statistics}}}}}, every statistics a dict of STAT_NAMES."""
+    out = dict(axes={axis: list(labels) for axis, labels in axes}, all={}, tables={})
+    for table, names, stats in tables:
+        out['all'][table] = metric_stats_dict(names, stats[0])
+        slot, by_axis = 1, {}
+        for axis, labels in axes:
+            by_axis[axis] = {label: metric_stats_dict(names, stats[slot + k]) for k, label in enumerate(labels)}
+            slot += len(labels)
+        out['tables'][table] = by_axis
+    return out
+
+
+BREAKDOWN_HEADER = ('step', 'table', 'axis', 'bin', 'metric') + STAT_NAMES
+
+
+def save_breakdown(predictions_base_dir, data_split, global_step, breakdown):
+    """Appends breakdown_dict's statistics to <predictions_base_dir>/metrics/<split>/breakdown_<split>.csv in long
+    format: one line per (table, axis, bin, metric) -- step, table, axis, bin, metric, count, mean, std, mean_abs,
+    std_abs, dropped -- the tables, axes, bins and metrics in the dict's order, and before each table's bins its line
+    over every row (axis and bin 'all').  Counts as integers, the four statistics as '{:.5f}'; into an empty file
+    first the header; ',' between the fields and the csv module's line ending.  Returns the path."""
+    out_dir = metrics_dir(predictions_base_dir, data_split)
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, 'breakdown_%s.csv' % data_split)
+
+    def lines(table, axis, label, stats):
+        for metric, st in stats.items():
+            yield ['{}'.format(global_step), table, axis, label, metric, '{:d}'.format(int(st['count']))] + \
+                ['{:.5f}'.format(st[k]) for k in ('mean', 'std', 'mean_abs', 'std_abs')] + \
+                ['{:d}'.format(int(st['dropped']))]
+
+    with open(path, 'a', newline='') as f:
+        writer = csv.writer(f, delimiter=',')
+        if f.tell() == 0:
+            writer.writerow(BREAKDOWN_HEADER)
+        for table, by_axis in breakdown['tables'].items():
+            writer.writerows(lines(table, 'all', 'all', breakdown['all'][table]))
+            for axis, by_bin in by_axis.items():
+                for label, stats in by_bin.items():
+                    writer.writerows(lines(table, axis, label, stats))
+    return path
 
 
 def metrics_dir(predictions_base_dir, data_split):

@@ -4,33 +4,15 @@
 // summation and no atomics: two calls on one table give the same bits.  DESIGN.md section 7.5.
 // Built with -ffp-contract=off: the centred square (x - mean) * (x - mean) is rounded before it is added.
 #include "common.h"
+#include "metric_stats_core.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace mpsr_stats;  // the statistics' body, shared with object_pairs.hip's binned form
 
-struct MetricColumns {
-    int metric[MPSR_METRIC_STATS_MAX_COLS];  // column -> metric
-};
-
-// the sum of every thread's v, to every thread: a tree over LDS, the same pairs in the same order on every call
-__device__ __forceinline__ double block_sum(double v, double *lds)
-{
-    const int t = threadIdx.x;
-    __syncthreads();  // (the previous sum's readers are done with lds)
-    lds[t] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s >= 1; s >>= 1) {
-        if (t < s) lds[t] += lds[t + s];
-        __syncthreads();
-    }
-    return lds[0];
-}
-
-// One workgroup per metric.  Element e of the metric is (row e / k, the metric's (e % k)-th column), k = the number
-// of its columns; thread t owns the elements t, t + 256, ...
+// One workgroup per metric (metric_stats_core.h: the element-to-thread assignment and the sums).
 __global__ void __launch_bounds__(kThreads) metric_stats_kernel(
     const float *__restrict__ values, const int *__restrict__ frame, int n_rows, int n_cols, MetricColumns cm,
     int n_frames, int nan_rule, int *frame_flags, double *__restrict__ stats)
@@ -39,14 +21,7 @@ __global__ void __launch_bounds__(kThreads) metric_stats_kernel(
     __shared__ int cols[MPSR_METRIC_STATS_MAX_COLS];
     __shared__ int n_own;
     const int m = blockIdx.x, t = threadIdx.x;
-    if (t == 0) {
-        int k = 0;
-        for (int c = 0; c < n_cols; ++c)
-            if (cm.metric[c] == m) cols[k++] = c;
-        n_own = k;
-    }
-    __syncthreads();
-    const int k = n_own;
+    const int k = own_columns(cm, n_cols, m, cols, &n_own);
     const long long n_elem = (long long)n_rows * k;
     int *flags = nullptr;
     if (nan_rule == 1) {
@@ -63,57 +38,13 @@ __global__ void __launch_bounds__(kThreads) metric_stats_kernel(
         __threadfence_block();
         __syncthreads();
     }
-    // pass 1: which elements count, their sum and the sum of their magnitudes
-    double cnt = 0.0, drop = 0.0, sum = 0.0, sum_abs = 0.0;
-    for (long long e = t; e < n_elem; e += kThreads) {
-        const int r = (int)(e / k), c = cols[(int)(e % k)];
-        const float v = values[(long long)r * n_cols + c];
-        bool out = v != v;
-        if (nan_rule == 1) {
-            const int f = frame[r];
-            out = out || f < 0 || f >= n_frames || flags[f] != 0;
-        }
-        if (out) {
-            drop += 1.0;
-        } else {
-            cnt += 1.0;
-            sum += (double)v;
-            sum_abs += fabs((double)v);
-        }
-    }
-    cnt = block_sum(cnt, lds);
-    drop = block_sum(drop, lds);
-    sum = block_sum(sum, lds);
-    sum_abs = block_sum(sum_abs, lds);
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
-    const double mean = cnt > 0.0 ? sum / cnt : nan, mean_abs = cnt > 0.0 ? sum_abs / cnt : nan;
-    // pass 2: the centred squares
-    double sq = 0.0, sq_abs = 0.0;
-    for (long long e = t; e < n_elem && cnt > 0.0; e += kThreads) {
-        const int r = (int)(e / k), c = cols[(int)(e % k)];
-        const float v = values[(long long)r * n_cols + c];
-        bool out = v != v;
-        if (nan_rule == 1) {
-            const int f = frame[r];
-            out = out || f < 0 || f >= n_frames || flags[f] != 0;
-        }
-        if (!out) {
-            const double d = (double)v - mean, da = fabs((double)v) - mean_abs;
-            sq += d * d;
-            sq_abs += da * da;
-        }
-    }
-    sq = block_sum(sq, lds);
-    sq_abs = block_sum(sq_abs, lds);
-    if (t == 0) {
-        double *o = stats + 6 * (long long)m;
-        o[0] = cnt;
-        o[1] = mean;
-        o[2] = cnt > 0.0 ? sqrt(sq / cnt) : nan;
-        o[3] = mean_abs;
-        o[4] = cnt > 0.0 ? sqrt(sq_abs / cnt) : nan;
-        o[5] = drop;
-    }
+    // under the frame rule a row is dropped with its frame: a NaN among the frame's values, or no such frame
+    const auto row_state = [=](int r) {
+        if (nan_rule != 1) return (int)kRowIn;
+        const int f = frame[r];
+        return (int)(f < 0 || f >= n_frames || flags[f] != 0 ? kRowDropped : kRowIn);
+    };
+    metric_stats_body(values, n_rows, n_cols, cols, k, row_state, lds, stats + 6 * (long long)m);
 }
 
 }  // namespace

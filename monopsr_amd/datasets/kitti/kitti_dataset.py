@@ -431,6 +431,12 @@ class KittiDataset:
             cam_p = depth_map_utils.read_calibration(os.path.join(self.calib_dir, name + '.txt')).p2
             row = self._label_rows(obj_labels, cam_p, shape)
             row['instance_id'] = instance_ids.astype(np.int32)
+            if self.train_val_test == 'val':
+                # the KITTI label rows themselves: with MSCNN merging obj_labels carry the detections' boxes, and
+                # instance_ids are the rows of the label file either way (_split_labels)
+                kitti = obj_utils.read_labels(self.kitti_label_dir, name)[instance_ids]
+                row['label_info'] = np.asarray([[o.truncation, o.occlusion, o.x1, o.y1, o.x2, o.y2] for o in kitti],
+                                               np.float32).reshape(-1, 6)
             group = groups.setdefault(tuple(shape), _Group(tuple(shape)))
             frames.append(dict(name=name, split_index=split_index, shape=tuple(shape), cam_p=np.asarray(cam_p),
                                num_objs=len(obj_labels), group=group, local=len(group.frames)))
@@ -498,6 +504,9 @@ class KittiDataset:
             self._p00_p02 = self._upload([[f['cam_p'][0, 0], f['cam_p'][0, 2]] for f in frames], torch.float64)
             self._cam_p = self._upload(np.stack([f['cam_p'] for f in frames]), f32)
             self._status = torch.zeros(2, dtype=i32, device=self.device)
+            # frame_label_info's table: kept on the host, uploaded (and reserved) when the method is first called
+            self._label_info_host = cat('label_info') if self.train_val_test == 'val' else None
+            self._label_info = None
 
     # ---- the reference's interface
 
@@ -613,6 +622,23 @@ class KittiDataset:
                 out.append(dict(depth_map=g.depth[local], instance_image=g.inst[local],
                                 instance_ids=self._label_instance_ids(label_row)))
         return out
+
+    def frame_label_info(self, rows):
+        """The KITTI label rows of whole frames ('val' mode), for rows of the frame tables as frame_ground_truth takes
+        them.  -> one (num_objs, 6) float32 device tensor per frame, [truncation, occlusion, x1, y1, x2, y2] of the
+        label-file row of each kept object: with use_mscnn_detections the 2-D box is the label's own, not the
+        detection that replaced it in boxes_2d.  The table is uploaded on the first call."""
+        if self._label_info_host is None:
+            raise ValueError("frame_label_info: only a 'val'-mode dataset keeps its KITTI label rows, this one is %r"
+                             % (self.train_val_test,))
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        if len(rows) and (rows.min() < 0 or rows.max() >= self.num_samples):
+            raise IndexError('frame index out of range [0, %d)' % self.num_samples)
+        if self._label_info is None:
+            with torch.cuda.device(self.device):
+                self._label_info = self._upload(self._label_info_host, torch.float32)
+        starts = np.concatenate([[0], np.cumsum(self._num_objs_host)]).astype(np.int64)
+        return [self._label_info[int(starts[r]):int(starts[r + 1])] for r in rows]
 
     # ---- one batch
 

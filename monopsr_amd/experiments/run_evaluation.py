@@ -10,6 +10,10 @@ With --scene-metrics every checkpoint's reconstructed scenes are also scored aga
 instance images (mask IoU, precisions, depth error: DESIGN.md section 7.8): six more lines per checkpoint and
 metrics/<split>/scene_metrics_<split>.csv.  --surface-metrics implies that and also renders the instance maps as
 surfaces and scores those: six more lines and metrics/<split>/surface_metrics_<split>.csv.
+With --breakdown every predicted box is also set against its own label (image, BEV and 3-D IoU, centre distance, hit
+rates) and every per-object table is split by the label's depth (--depth-edges), its KITTI difficulty and the IoU of the
+fed 2-D box (--box-iou-edges): the overall overlap lines per checkpoint and, in long format,
+metrics/<split>/breakdown_<split>.csv.
 """
 import argparse
 import sys
@@ -40,6 +44,7 @@ def build_parser():
                     help='fit every predicted centroid to its 2-D box before scoring (DESIGN.md section 7.10)')
     ap.add_argument('--fit-viewing-angle', action='store_true',
                     help='--fit-centroids: fit the viewing angle as well')
+    evaluator.add_breakdown_arguments(ap)
     return ap
 
 
@@ -53,6 +58,9 @@ def format_result(result):
     for name, st in list(result.get('scene_stats', {}).items()) + list(result.get('surface_stats', {}).items()):
         lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
             name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
+    for name, st in result.get('breakdown', {}).get('all', {}).get('object', {}).items():
+        lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
+            name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
     if 'centroid_fit' in result:
         lines.append('centroid fit: %s\n' % evaluator.format_centroid_fit(result['centroid_fit']))
     return ''.join(lines)
@@ -62,6 +70,7 @@ def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
     centroid_fit = evaluator.centroid_fit_options(ap, args)
+    breakdown = evaluator.breakdown_options(ap, args)
     from monopsr_amd.core import config_utils
     from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
     from monopsr_amd.datasets.kitti.kitti_dataset import KittiDataset
@@ -75,7 +84,7 @@ def main(argv=None):
     ev = evaluator.Evaluator(model, dataset, score_threshold=threshold, predictions_base_dir=args.predictions_dir,
                              iou='low' if args.low_iou else 'standard', metric_stats=True,
                              scene_metrics='surface' if args.surface_metrics else args.scene_metrics,
-                             centroid_fit=centroid_fit)
+                             centroid_fit=centroid_fit, breakdown=breakdown)
     if args.repeat:
         max_iterations = getattr(train_config, 'max_iterations', None)
         if max_iterations is None and args.max_idle is None:
