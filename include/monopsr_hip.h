@@ -435,7 +435,14 @@ int mpsr_batch_norm_grad_z(const float *dy, const float *z, long long M, int C, 
  * hold each variable's squared norm on return, the rest the chunks' partial sums.  ABI 6 (signature changed: sumsq_floats):
  * the norms are summed in a FIXED order -- per chunk, then over a variable's chunks -- with no atomics, so every replica of
  * a data-parallel run scales the same reduced gradient by the same bits and the replicas' parameters stay bit-identical
- * (tests/test_sharded_training_step_gpu.py; an atomic accumulation left two ranks one ulp apart after one step). */
+ * (tests/test_sharded_training_step_gpu.py; an atomic accumulation left two ranks one ulp apart after one step).
+ * Any ascending table is served (tests/test_optim_gpu.py): chunk_begin needs no alignment (a chunk that does not start on
+ * 16 bytes is read float by float); a chunk of length 0 is allowed and adds nothing; a segment id in [0, n_segments) with
+ * no chunk gets the squared norm 0; chunks may leave gaps, and elements outside every chunk are neither read nor written.
+ * The scale is applied iff norm > clip_norm, strictly: a variable with norm == clip_norm keeps its bits, and so does one
+ * whose norm is NaN (a NaN among its elements) -- its gradient is left as it is.  An infinite norm over a finite
+ * clip_norm scales by clip_norm / inf = 0: finite elements become +-0, the infinite ones NaN (what
+ * g * clip / max(norm, clip) gives); against clip_norm = +inf it is norm == clip_norm, not scaled. */
 int mpsr_clip_by_norm_segments(float *grads, const int *chunk_seg, const long long *chunk_begin,
                                const int *chunk_len, int n_chunks, float *sumsq, size_t sumsq_floats, int n_segments,
                                float clip_norm, mpsr_stream_t stream);
@@ -447,7 +454,12 @@ int mpsr_clip_by_norm_segments(float *grads, const int *chunk_seg, const long lo
  * shadow += (1 - ema_decay) * (param - shadow).  Operation by operation the arithmetic of mpsr_clip_by_norm_segments ->
  * mpsr_adam_step -> that moving average; elements outside every chunk (alignment padding) are not touched.
  * clip_norm <= 0: no clipping (sumsq may be NULL).  sumsq / sumsq_floats as mpsr_clip_by_norm_segments (deterministic
- * norms).  step = 1-based Adam step (bias correction). */
+ * norms).  step = 1-based Adam step (bias correction).
+ * The table semantics are mpsr_clip_by_norm_segments': no alignment requirement on chunk_begin, zero-length chunks
+ * allowed, a segment id with no chunk gets norm 0, norm == clip_norm is not scaled, and a NaN norm leaves the segment's
+ * gradient as it is (scale 1: only the NaN elements' own param / m / v become NaN).  sumsq[0 .. n_segments) holds the
+ * same bits mpsr_clip_by_norm_segments writes for the same gradients.  Outside every chunk none of param, grad, m, v and
+ * shadow is read or written. */
 int mpsr_clip_adam_ema_step(float *param, const float *grad, float *m, float *v, float *shadow, const int *chunk_seg,
                             const long long *chunk_begin, const int *chunk_len, int n_chunks, float *sumsq,
                             size_t sumsq_floats, int n_segments, float clip_norm, float lr, float beta1, float beta2,
