@@ -746,6 +746,53 @@ int mpsr_kitti_stats(const mpsr_kitti_batch *batch, const double *overlaps, cons
                      const double *thresholds, const int *n_thresholds, int compute_aos, int *counts,
                      double *similarity, void *workspace, size_t workspace_bytes, mpsr_stream_t stream);
 
+/* ---- AP by slice (additive to ABI 13): both passes for several slices in one launch each ----
+ * A slice is an IoU set and, when depth_tested, a depth bin: a row is in it when lo <= z < hi, z the camera-frame depth
+ * (MPSR_KITTI_TZ) of the row itself; the open ends are -inf and +inf, and a NaN z is in no tested bin.  What the C++
+ * program prints after two rewrites of the label files defines the result: a ground truth outside the bin gets
+ * occlusion 3 (cleanData ignores it: ignored_gt 1 for a row of the evaluated class or its neighbour class, -1 stays -1),
+ * a detection outside the bin gets a class nobody evaluates (ignored_det -1, or 1 below the level's minimum height).
+ * With depth_tested = 0 no row is tested, a NaN z included: the slice is mpsr_kitti_match / mpsr_kitti_stats with its
+ * min_overlap, to the bit.  Those two are this code's one-slice case.
+ * A configuration is (slice, one of the 27), index slice * 27 + configuration.  The slice table comes twice, like the
+ * batch's offsets: in device memory for the kernels (together with n_thresholds and the list of launched
+ * configurations, which the statistics pass writes into its workspace: 32 slices are 864 configurations, more than a
+ * launch's arguments should carry) and in host memory, where it is checked before anything is launched:
+ * n_slices outside 1 .. MPSR_KITTI_MAX_SLICES, a null table, and a tested slice with hi < lo or a NaN edge are
+ * MPSR_ERR_INVALID_ARG with a message. */
+#define MPSR_KITTI_MAX_SLICES 32
+
+typedef struct mpsr_kitti_slice {
+    double min_overlap[9]; /* MIN_OVERLAP[metric][class] of the slice */
+    double lo, hi;         /* the depth bin, lo <= z < hi (read only when depth_tested) */
+    int depth_tested;      /* 0: no depth test whatever */
+    int reserved;          /* 0 */
+} mpsr_kitti_slice;
+
+/* mpsr_kitti_match of every slice: one block per (frame, group of 64 configurations), one lane per configuration.
+ * tp_scores (n_slices * 27, n_gt), n_care (n_slices * 27, n_frames): n_care counts the ground truths that are in the
+ * slice and pass the level.  tp_scores is written whole, NaN where a row has no true positive (every row of another
+ * class): 8 * 27 * n_slices * n_gt bytes, 113 MB at KITTI val's 37 540 ground truths and 14 slices (two IoU sets x
+ * ('all' + 6 bins)), and the caller copies as much to the host for getThresholds.  Not shrunk to the rows of the
+ * configuration's class: a third of the size, for an index table per class that every caller would have to build. */
+int mpsr_kitti_match_slices(const mpsr_kitti_batch *batch, const double *overlaps, const mpsr_kitti_slice *slices,
+                            const mpsr_kitti_slice *slices_host, int n_slices, double *tp_scores, int *n_care,
+                            mpsr_stream_t stream);
+
+/* Bytes of mpsr_kitti_stats_slices' workspace: the list of launched configurations and the per-frame results of
+ * n_configs configurations (those with thresholds, over all slices). */
+size_t mpsr_kitti_stats_slices_workspace_bytes(int n_frames, int n_configs);
+
+/* mpsr_kitti_stats of every slice: one block per (frame, launched configuration), one lane per threshold, then the sum
+ * over frames in frame order in a second kernel (no float atomics).  thresholds (n_slices * 27, MPSR_KITTI_POINTS) and
+ * n_thresholds (n_slices * 27) device; n_thresholds_host the same counts on the host, 0..41 (0: the configuration is
+ * skipped -- a class without a detection in the slice).  compute_aos is one flag for the run: a property of all
+ * detections, whatever their depth.  counts (n_slices * 27, 41, 3), similarity (n_slices * 27, 41, 2). */
+int mpsr_kitti_stats_slices(const mpsr_kitti_batch *batch, const double *overlaps, const mpsr_kitti_slice *slices,
+                            const mpsr_kitti_slice *slices_host, int n_slices, const double *thresholds,
+                            const int *n_thresholds, const int *n_thresholds_host, int compute_aos, int *counts,
+                            double *similarity, void *workspace, size_t workspace_bytes, mpsr_stream_t stream);
+
 /* ---- LiDAR depth maps (ABI 8): demos/depth_completion/save_lidar_depth_maps.py ----
  * Several frames that share one image size (h, w); all maps are (n_frames, h, w) float32. */
 

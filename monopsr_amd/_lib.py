@@ -74,6 +74,12 @@ class KittiBatch(ctypes.Structure):
                  "pair_off_host")] + [("n_det", ctypes.c_int32), ("n_gt", ctypes.c_int32), ("n_frames", ctypes.c_int32)]
 
 
+class KittiSlice(ctypes.Structure):
+    """struct mpsr_kitti_slice"""
+    _fields_ = [("min_overlap", ctypes.c_double * 9), ("lo", ctypes.c_double), ("hi", ctypes.c_double),
+                ("depth_tested", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class DepthFillOpts(ctypes.Structure):
     """struct mpsr_depth_fill_opts"""
     _fields_ = [("max_depth", ctypes.c_float), ("extrapolate", ctypes.c_int32), ("blur_type", ctypes.c_int32),
@@ -201,6 +207,12 @@ SIGNATURES = {
     "mpsr_kitti_stats_workspace_bytes": (c_sz, [c_i, c_i]),
     "mpsr_kitti_stats": (c_i, [ctypes.POINTER(KittiBatch), c_f, ctypes.POINTER(ctypes.c_double), c_f,
                                ctypes.POINTER(c_i), c_i, c_f, c_f, c_f, c_sz, c_f]),
+    # the slice table: a device pointer, then the same table on the host
+    "mpsr_kitti_match_slices": (c_i, [ctypes.POINTER(KittiBatch), c_f, c_f, ctypes.POINTER(KittiSlice), c_i, c_f, c_f,
+                                      c_f]),
+    "mpsr_kitti_stats_slices_workspace_bytes": (c_sz, [c_i, c_i]),
+    "mpsr_kitti_stats_slices": (c_i, [ctypes.POINTER(KittiBatch), c_f, c_f, ctypes.POINTER(KittiSlice), c_i, c_f, c_f,
+                                      ctypes.POINTER(c_i), c_i, c_f, c_f, c_f, c_sz, c_f]),
     "mpsr_lidar_project_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "mpsr_lidar_project_depths": (c_i, [c_f, c_f, ctypes.c_void_p, c_i, c_f, c_f, c_i, c_i, ctypes.c_double, c_f, c_f,
                                         c_sz, c_f]),

@@ -59,7 +59,15 @@ predictions_base_dir metrics/<split>/breakdown_<split>.csv (result['breakdown_cs
 columns' means are shares of the evaluated labels, not KITTI recall: frames and labels the dataset's filter drops are
 not in the denominator.
 
-Not built: TF summaries and metrics_to_show, both IoU settings in one pass, AP per bin.
+ap_slices: None, or a dict of options ({} for the defaults: both IoU sets, depth edges 10 .. 50 m), wherever
+result['kitti'] is computed.  With it the frames assembled for result['kitti'] also go through
+one kitti_eval.evaluate_sliced call: result['kitti_slices'] = {(iou, bin label): a result of result['kitti']'s form},
+'all' and every depth bin of every IoU set of 'ious'; with predictions_base_dir also
+kitti_reports/<split>/<step, 8 digits>_slices.txt (kitti_eval.format_sliced_report) and, in long format,
+metrics/<split>/ap_slices_<split>.csv (evaluator_utils.save_ap_slices).  result['kitti'] and result['report'] keep
+coming from `iou`.
+
+Not built: TF summaries and metrics_to_show.
 """
 import argparse
 import os
@@ -90,6 +98,9 @@ _CENTROID_FIT_OPTIONS = ('fit_viewing_angle', 'use_pixel_centres', 'cam0_shift')
 # what Evaluator(breakdown={...}) may hold, with the defaults
 _BREAKDOWN_OPTIONS = dict(depth_edges=evaluator_utils.DEFAULT_DEPTH_EDGES,
                           box_iou_edges=evaluator_utils.DEFAULT_BOX_IOU_EDGES)
+
+# what Evaluator(ap_slices={...}) may hold, with the defaults
+_AP_SLICES_OPTIONS = dict(ious=('standard', 'low'), depth_edges=evaluator_utils.DEFAULT_DEPTH_EDGES)
 
 
 def sweep_checkpoints(checkpoints, evaluated, run, ckpt_indices=None):
@@ -143,10 +154,21 @@ class Evaluator:
 
     def __init__(self, model, dataset, score_threshold=0.1, predictions_base_dir=None, batch_size=8,
                  project_3d_box=False, iou='standard', compute_metrics=True, compute_losses=True, metric_stats=False,
-                 skip_evaluated_checkpoints=True, scene_metrics=False, breakdown=None, centroid_fit=None,
-                 chunk_hook=None):
+                 skip_evaluated_checkpoints=True, scene_metrics=False, breakdown=None, ap_slices=None,
+                 centroid_fit=None, chunk_hook=None):
         if iou not in kitti_eval.MIN_OVERLAP:
             raise ValueError('iou must be one of %s' % sorted(kitti_eval.MIN_OVERLAP))
+        if ap_slices is not None:
+            unknown = set(ap_slices) - set(_AP_SLICES_OPTIONS)
+            if unknown:
+                raise ValueError('ap_slices: unknown options %s' % sorted(unknown))
+            ious = ap_slices.get('ious', _AP_SLICES_OPTIONS['ious'])
+            ap_slices = dict(ious=(ious,) if isinstance(ious, str) else tuple(ious),
+                             depth_edges=tuple(float(v) for v in ap_slices.get('depth_edges',
+                                                                               _AP_SLICES_OPTIONS['depth_edges'])))
+            kitti_eval.slice_table(**ap_slices)  # ValueError for what evaluate_sliced would refuse
+        # None, or {'ious': (...), 'depth_edges': (...)}: AP per IoU set and depth bin next to result['kitti']
+        self.ap_slices = ap_slices
         if int(batch_size) < 1:
             raise ValueError('batch_size %r' % (batch_size,))
         if not (getattr(dataset, 'is_test', False) or getattr(dataset, 'merges_mscnn', False)):
@@ -440,6 +462,17 @@ class Evaluator:
                 gt.append(kitti_eval.parse_label_file(path, detections=False))
             result['kitti'] = kitti_eval.evaluate(gt, dets, self.iou, ds.device)
             result['report'] = kitti_eval.format_report(result['kitti'], global_step)
+            if self.ap_slices is not None:
+                result['kitti_slices'] = kitti_eval.evaluate_sliced(gt, dets, device=ds.device, **self.ap_slices)
+                if self.predictions_base_dir is not None:
+                    report_dir = os.path.join(self.predictions_base_dir, 'kitti_reports', ds.data_split)
+                    os.makedirs(report_dir, exist_ok=True)
+                    path = os.path.join(report_dir, '%08d_slices.txt' % (global_step or 0))
+                    with open(path, 'w') as f:
+                        f.write(kitti_eval.format_sliced_report(result['kitti_slices'], global_step))
+                    result['kitti_slices_report'] = path
+                    result['ap_slices_csv'] = evaluator_utils.save_ap_slices(
+                        self.predictions_base_dir, ds.data_split, global_step, result['kitti_slices'])
         return result
 
     def restore_checkpoint(self, path, width_div=1):
@@ -543,6 +576,32 @@ def breakdown_options(ap, args):
     if edges and not args.breakdown:
         ap.error('--depth-edges and --box-iou-edges require --breakdown')
     return edges if args.breakdown else None
+
+
+def add_ap_slices_arguments(ap):
+    """run_evaluation's --ap-slices, --ap-depth-edges and --ap-ious."""
+    ap.add_argument('--ap-slices', action='store_true',
+                    help='also KITTI AP per IoU set and depth bin in one pass (DESIGN.md section 7.12)')
+    ap.add_argument('--ap-depth-edges', type=float, nargs='+', default=None, metavar='M',
+                    help='the AP depth bins\' edges in metres (default 10 20 30 40 50)')
+    ap.add_argument('--ap-ious', nargs='+', default=None, choices=sorted(kitti_eval.MIN_OVERLAP, reverse=True),
+                    help='the IoU sets of the AP slices (default standard low)')
+
+
+def ap_slices_options(ap, args):
+    """The Evaluator's ap_slices of a command line's --ap-slices, --ap-depth-edges and --ap-ious (None without
+    --ap-slices)."""
+    given = {k: v for k, v in (('depth_edges', args.ap_depth_edges), ('ious', args.ap_ious)) if v is not None}
+    if given and not args.ap_slices:
+        ap.error('--ap-depth-edges and --ap-ious require --ap-slices')
+    if not args.ap_slices:
+        return None
+    try:
+        kitti_eval.slice_table(given.get('ious', _AP_SLICES_OPTIONS['ious']),
+                               given.get('depth_edges', _AP_SLICES_OPTIONS['depth_edges']))
+    except ValueError as e:
+        ap.error(str(e))
+    return given
 
 
 def format_centroid_fit(c):

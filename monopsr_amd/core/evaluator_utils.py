@@ -276,6 +276,37 @@ def save_breakdown(predictions_base_dir, data_split, global_step, breakdown):
     return path
 
 
+AP_SLICES_HEADER = ('step', 'iou', 'bin', 'class', 'metric', 'difficulty', 'ap11', 'ap40')
+AP_DIFFICULTIES = ('easy', 'moderate', 'hard')
+
+
+def save_ap_slices(predictions_base_dir, data_split, global_step, slices):
+    """Appends kitti_eval.evaluate_sliced's result to <predictions_base_dir>/metrics/<split>/ap_slices_<split>.csv in
+    long format: one line per (iou, bin, class, metric key, difficulty) -- step, iou, bin, class, metric, difficulty,
+    ap11, ap40 -- the slices, classes and metric keys in the dict's order.  The numbers as '{:.5f}' ('nan' stays
+    'nan', whatever its sign); into an empty file first the header; ',' between the fields and the csv module's line
+    ending.  Returns the path."""
+    out_dir = metrics_dir(predictions_base_dir, data_split)
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, 'ap_slices_%s.csv' % data_split)
+
+    def number(v):
+        v = float(v)
+        return 'nan' if v != v else '{:.5f}'.format(v)
+
+    with open(path, 'a', newline='') as f:
+        writer = csv.writer(f, delimiter=',')
+        if f.tell() == 0:
+            writer.writerow(AP_SLICES_HEADER)
+        for (iou, label), result in slices.items():
+            for cls, by_key in result.items():
+                for key, entry in by_key.items():
+                    for d, name in enumerate(AP_DIFFICULTIES):
+                        writer.writerow(['{}'.format(global_step), iou, label, cls, key, name,
+                                         number(entry['ap11'][d]), number(entry['ap40'][d])])
+    return path
+
+
 def metrics_dir(predictions_base_dir, data_split):
     return os.path.join(predictions_base_dir, 'metrics', data_split)
 

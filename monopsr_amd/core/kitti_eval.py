@@ -10,6 +10,8 @@ the summed statistics into the 41-point curves and the AP the program prints (:7
     result = evaluate_dirs(gt_label_dir, result_dir)      # like the C++ program: frames with a file in result_dir/data
     result = evaluate_predictions(predictions, classes, score_threshold, gt_label_dir)  # format_predictions output
     print(format_report(result, step))
+    results = evaluate_sliced(gt_frames, det_frames, ious=('standard', 'low'), depth_edges=(10, 20, 30, 40, 50))
+    print(format_sliced_report(results, step))            # {(iou, 'all' | depth bin): result}, one pass
 
 result: {class: {'image', 'aos', 'bev', 'heading_bev', '3d', 'heading_3d': {'curve' (3,41), 'ap11' (3,),
 'ap40' (3,)}}}, rows easy / moderate / hard, only the entries the reference evaluates.  ap11 is the printed number
@@ -175,6 +177,56 @@ def _host_offsets(frames):
     return np.concatenate([[0], np.cumsum([len(f) for f in frames])]).astype(np.int32)
 
 
+class _Batch(object):
+    """One ragged batch on the device (struct mpsr_kitti_batch) and what keeps its memory alive."""
+
+    def __init__(self, gt, dets, device):
+        import torch
+        if len(gt) != len(dets):
+            raise ValueError('evaluate: %d ground-truth frames, %d detection frames' % (len(gt), len(dets)))
+        self.nf = len(gt)
+        dof, gof = _host_offsets(dets), _host_offsets(gt)
+        pof = np.concatenate([[0], np.cumsum([len(d) * len(g) for d, g in zip(dets, gt)])]).astype(np.int64)
+        self.dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        det_rows = self.up(np.concatenate([d.rows for d in dets] + [np.zeros((0, FIELDS))]), torch.float64)
+        det_cls = self.up(np.concatenate([d.codes for d in dets] + [np.zeros(0, np.int32)]), torch.int32)
+        gt_rows = self.up(np.concatenate([g.rows for g in gt] + [np.zeros((0, FIELDS))]), torch.float64)
+        gt_cls = self.up(np.concatenate([g.codes for g in gt] + [np.zeros(0, np.int32)]), torch.int32)
+        dof_d, gof_d, pof_d = self.up(dof, torch.int32), self.up(gof, torch.int32), self.up(pof, torch.int64)
+        self.n_det, self.n_gt, self.n_pairs = int(dof[-1]), int(gof[-1]), int(pof[-1])
+        p = _lib.ptr
+        with torch.cuda.device(self.dev):
+            self.struct = _lib.KittiBatch(p(det_rows), p(det_cls), p(gt_rows), p(gt_cls), p(dof_d), p(gof_d), p(pof_d),
+                                          dof.ctypes.data, gof.ctypes.data, pof.ctypes.data, self.n_det, self.n_gt,
+                                          self.nf)
+        self.keep = (det_rows, det_cls, gt_rows, gt_cls, dof_d, gof_d, pof_d, dof, gof, pof)
+
+    def up(self, a, dt):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev, dt)
+
+
+def _pick_thresholds(ev, scores, care):
+    """getThresholds of the 27 configurations of one slice.  ev (3,3) bool [metric][class]; scores (27, n_gt) with NaN
+    where a ground truth has no true positive; care (27, n_frames).  -> ([thresholds per configuration], thr (27,41),
+    n_thr (27,))."""
+    thresholds = []
+    thr = np.zeros((N_CONFIGS, N_POINTS), np.float64)
+    n_thr = np.zeros(N_CONFIGS, np.int32)
+    for cfg in range(N_CONFIGS):
+        metric, cls = cfg // 9, (cfg // 3) % 3
+        t = np.zeros(0)
+        if ev[metric, cls]:
+            v = scores[cfg]
+            t = get_thresholds(v[~np.isnan(v)], int(care[cfg].sum()))
+            if len(t) > N_POINTS:
+                raise RuntimeError('getThresholds gave %d thresholds (> %d)' % (len(t), N_POINTS))
+        thresholds.append(t)
+        thr[cfg, :len(t)] = t
+        n_thr[cfg] = len(t)
+    return thresholds, thr, n_thr
+
+
 def _kernel_pass(gt, dets, iou, device):
     """Overlaps, matching pass, thresholds (host), statistics pass.  Returns (thresholds per configuration, counts
     (27,41,3), similarity (27,41,2), eval flags, compute_aos)."""
@@ -184,50 +236,23 @@ def _kernel_pass(gt, dets, iou, device):
     if iou not in MIN_OVERLAP:
         raise ValueError('iou must be one of %s' % sorted(MIN_OVERLAP))
     ev, compute_aos = _eval_flags(dets)
-    nf = len(gt)
-    dof, gof = _host_offsets(dets), _host_offsets(gt)
-    pof = np.concatenate([[0], np.cumsum([len(d) * len(g) for d, g in zip(dets, gt)])]).astype(np.int64)
-    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-
-    def up(a, dt):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev, dt)
-
-    det_rows = up(np.concatenate([d.rows for d in dets] + [np.zeros((0, FIELDS))]), torch.float64)
-    det_cls = up(np.concatenate([d.codes for d in dets] + [np.zeros(0, np.int32)]), torch.int32)
-    gt_rows = up(np.concatenate([g.rows for g in gt] + [np.zeros((0, FIELDS))]), torch.float64)
-    gt_cls = up(np.concatenate([g.codes for g in gt] + [np.zeros(0, np.int32)]), torch.int32)
-    dof_d, gof_d, pof_d = up(dof, torch.int32), up(gof, torch.int32), up(pof, torch.int64)
-    n_det, n_gt, n_pairs = int(dof[-1]), int(gof[-1]), int(pof[-1])
+    b = _Batch(gt, dets, device)
+    nf, dev, batch = b.nf, b.dev, b.struct
     p = _lib.ptr
     with torch.cuda.device(dev):
-        batch = _lib.KittiBatch(p(det_rows), p(det_cls), p(gt_rows), p(gt_cls), p(dof_d), p(gof_d), p(pof_d),
-                                dof.ctypes.data, gof.ctypes.data, pof.ctypes.data, n_det, n_gt, nf)
         mo = np.array([MIN_OVERLAP[iou]] * 3, np.float64).reshape(9)
         mo_c = mo.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         lib, s = _lib.lib(), _lib.stream()
-        overlaps = torch.empty((6, n_pairs), dtype=torch.float64, device=dev)
-        tp_scores = torch.empty((N_CONFIGS, n_gt), dtype=torch.float64, device=dev)
+        overlaps = torch.empty((6, b.n_pairs), dtype=torch.float64, device=dev)
+        tp_scores = torch.empty((N_CONFIGS, b.n_gt), dtype=torch.float64, device=dev)
         n_care = torch.empty((N_CONFIGS, nf), dtype=torch.int32, device=dev)
         _lib.check(lib.mpsr_kitti_overlaps(ctypes.byref(batch), p(overlaps), s))
         _lib.check(lib.mpsr_kitti_match(ctypes.byref(batch), p(overlaps), mo_c, p(tp_scores), p(n_care), s))
         scores, care = tp_scores.cpu().numpy(), n_care.cpu().numpy()
-        thresholds = []
-        thr = np.zeros((N_CONFIGS, N_POINTS), np.float64)
-        n_thr = np.zeros(N_CONFIGS, np.int32)
-        for cfg in range(N_CONFIGS):
-            metric, cls = cfg // 9, (cfg // 3) % 3
-            t = np.zeros(0)
-            if ev[metric, cls]:
-                v = scores[cfg]
-                t = get_thresholds(v[~np.isnan(v)], int(care[cfg].sum()))
-                if len(t) > N_POINTS:
-                    raise RuntimeError('getThresholds gave %d thresholds (> %d)' % (len(t), N_POINTS))
-            thresholds.append(t)
-            thr[cfg, :len(t)] = t
-            n_thr[cfg] = len(t)
+        thresholds, thr, n_thr = _pick_thresholds(ev, scores, care)
         n_active = int((n_thr > 0).sum())
         ws = torch.empty(max(1, lib.mpsr_kitti_stats_workspace_bytes(nf, n_active)), dtype=torch.uint8, device=dev)
-        thr_d = up(thr, torch.float64)
+        thr_d = b.up(thr, torch.float64)
         counts = torch.empty((N_CONFIGS, N_POINTS, 3), dtype=torch.int32, device=dev)
         sims = torch.empty((N_CONFIGS, N_POINTS, 2), dtype=torch.float64, device=dev)
         _lib.check(lib.mpsr_kitti_stats(ctypes.byref(batch), p(overlaps), mo_c, p(thr_d),
@@ -254,10 +279,8 @@ def _entry(rows):
     return {'curve': curve, 'ap11': ap11(curve), 'ap40': ap40(curve)}
 
 
-def evaluate(gt, detections, iou='standard', device=None):
-    """gt, detections: lists of Frame (one per image, in the same order).  iou: 'standard' (MIN_OVERLAP 0.7 / 0.5 /
-    0.5) or 'low' (0.5 / 0.25 / 0.25).  Returns the nested result dict described in the module docstring."""
-    thresholds, counts, sims, ev, compute_aos = _kernel_pass(gt, detections, iou, device)
+def _result(thresholds, counts, sims, ev, compute_aos):
+    """The nested result dict of one evaluation (one slice) from its 27 configurations' summed statistics."""
     result = {}
     for metric in range(3):
         for cls in range(3):
@@ -279,6 +302,132 @@ def evaluate(gt, detections, iou='standard', device=None):
             if metric != 0:
                 out['heading_' + name] = _entry(head)
     return result
+
+
+def evaluate(gt, detections, iou='standard', device=None):
+    """gt, detections: lists of Frame (one per image, in the same order).  iou: 'standard' (MIN_OVERLAP 0.7 / 0.5 /
+    0.5) or 'low' (0.5 / 0.25 / 0.25).  Returns the nested result dict described in the module docstring."""
+    return _result(*_kernel_pass(gt, detections, iou, device))
+
+
+MAX_SLICES = 32  # MPSR_KITTI_MAX_SLICES
+MAX_EDGES = 15   # evaluator_utils.MAX_EDGES: mpsr_object_pairs' depth axis
+
+
+def slice_table(ious=('standard',), depth_edges=()):
+    """The slices of evaluate_sliced, in its key order: [((iou, bin label), lo, hi)], lo = hi = None for 'all'.  Raises
+    ValueError for duplicate or unknown ious, edges that do not increase, are not finite or number more than MAX_EDGES,
+    and for more than MAX_SLICES slices.  Touches no device."""
+    from monopsr_amd.core import evaluator_utils as eu
+    ious = [ious] if isinstance(ious, str) else list(ious)
+    if not ious:
+        raise ValueError('evaluate_sliced: no iou set given')
+    for iou in ious:
+        if iou not in MIN_OVERLAP:
+            raise ValueError('evaluate_sliced: iou %r is not one of %s' % (iou, sorted(MIN_OVERLAP)))
+    if len(set(ious)) != len(ious):
+        raise ValueError('evaluate_sliced: duplicate iou sets in %r' % (ious,))
+    edges = [float(e) for e in depth_edges]
+    if len(edges) > MAX_EDGES:
+        raise ValueError('evaluate_sliced: %d depth edges, at most %d' % (len(edges), MAX_EDGES))
+    if not all(np.isfinite(e) for e in edges):
+        raise ValueError('evaluate_sliced: depth edges must be finite, got %r' % (edges,))
+    if any(b <= a for a, b in zip(edges[:-1], edges[1:])):
+        raise ValueError('evaluate_sliced: depth edges must increase, got %r' % (edges,))
+    bins = []
+    if edges:
+        bounds = [-np.inf] + edges + [np.inf]
+        labels = eu.edge_labels(edges)
+        if len(set(labels)) != len(labels):
+            raise ValueError('evaluate_sliced: depth edges %r give the same bin label twice: %r' % (edges, labels))
+        bins = list(zip(labels, bounds[:-1], bounds[1:]))
+    n = len(ious) * (1 + len(bins))
+    if n > MAX_SLICES:
+        raise ValueError('evaluate_sliced: %d iou sets x (all + %d bins) = %d slices, at most %d'
+                         % (len(ious), len(bins), n, MAX_SLICES))
+    out = []
+    for iou in ious:
+        out.append(((iou, 'all'), None, None))
+        out.extend(((iou, label), lo, hi) for label, lo, hi in bins)
+    return out
+
+
+def _in_bin(frames, lo, hi):
+    """The detections of each frame whose own z lies in lo <= z < hi (a NaN z lies in no bin)."""
+    out = []
+    for fr in frames:
+        z = fr.rows[:, TZ]
+        m = (z >= lo) & (z < hi)
+        out.append(Frame(fr.codes[m], fr.rows[m]))
+    return out
+
+
+def evaluate_sliced(gt, detections, ious=('standard',), depth_edges=(), device=None):
+    """AP of every slice in one pass.  A slice is an IoU set of `ious` and either every row
+    ('all': the bits of evaluate(gt, detections, iou)) or one of the len(depth_edges) + 1 depth bins that increasing
+    edges cut (evaluator_utils.edge_labels; a row with lo <= z < hi is in the bin, so an edge belongs to the upper bin,
+    a NaN z to none and a 2-D-only detection's z = -1000 to the first).  A bin's AP is what the C++ program prints after
+    every ground truth whose z is outside the bin has got occlusion 3 and every detection whose own z is outside it the
+    class Misc; the eval flags (which metrics a class has) come from the bin's own detections, compute_aos from all.
+    -> {(iou, bin label): result of evaluate's form}, ordered by ious, then 'all', then the bins.
+    One batch upload, one mpsr_kitti_overlaps launch, one matching launch, getThresholds per configuration on the
+    host, one statistics launch and one copy back."""
+    import torch
+    table = slice_table(ious, depth_edges)
+    if len(gt) != len(detections):
+        raise ValueError('evaluate: %d ground-truth frames, %d detection frames' % (len(gt), len(detections)))
+    n_slices = len(table)
+    _, compute_aos = _eval_flags(detections)
+    flags = {}  # per bin, shared by the IoU sets
+    for (_, label), lo, hi in table:
+        if label not in flags:
+            flags[label] = _eval_flags(detections if lo is None else _in_bin(detections, lo, hi))[0]
+    slices_h = (_lib.KittiSlice * n_slices)()
+    for k, ((iou, _), lo, hi) in enumerate(table):
+        slices_h[k].min_overlap[:] = list(MIN_OVERLAP[iou]) * 3
+        slices_h[k].depth_tested = int(lo is not None)
+        slices_h[k].lo, slices_h[k].hi = (0.0, 0.0) if lo is None else (lo, hi)
+    b = _Batch(gt, detections, device)
+    nf, dev, batch = b.nf, b.dev, b.struct
+    n_total = n_slices * N_CONFIGS
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        lib, s = _lib.lib(), _lib.stream()
+        slices_d = b.up(np.frombuffer(slices_h, np.uint8), torch.uint8)
+        overlaps = torch.empty((6, b.n_pairs), dtype=torch.float64, device=dev)
+        tp_scores = torch.empty((n_total, b.n_gt), dtype=torch.float64, device=dev)
+        n_care = torch.empty((n_total, nf), dtype=torch.int32, device=dev)
+        _lib.check(lib.mpsr_kitti_overlaps(ctypes.byref(batch), p(overlaps), s))
+        _lib.check(lib.mpsr_kitti_match_slices(ctypes.byref(batch), p(overlaps), p(slices_d), slices_h, n_slices,
+                                               p(tp_scores), p(n_care), s))
+        scores, care = tp_scores.cpu().numpy(), n_care.cpu().numpy()
+        del tp_scores
+        thresholds, thr, n_thr = [], [], []
+        for k, ((_, label), _, _) in enumerate(table):
+            t, a, n = _pick_thresholds(flags[label], scores[k * N_CONFIGS:(k + 1) * N_CONFIGS],
+                                       care[k * N_CONFIGS:(k + 1) * N_CONFIGS])
+            thresholds.append(t)
+            thr.append(a)
+            n_thr.append(n)
+        n_thr = np.ascontiguousarray(np.concatenate(n_thr), np.int32)
+        n_active = int((n_thr > 0).sum())
+        ws = torch.empty(max(1, lib.mpsr_kitti_stats_slices_workspace_bytes(nf, n_active)), dtype=torch.uint8,
+                         device=dev)
+        thr_d, n_thr_d = b.up(np.concatenate(thr), torch.float64), b.up(n_thr, torch.int32)
+        # counts and similarities in one buffer: one copy back
+        out = torch.empty(n_total * N_POINTS * (3 * 4 + 2 * 8), dtype=torch.uint8, device=dev)
+        sims = out[:n_total * N_POINTS * 16].view(torch.float64)
+        counts = out[n_total * N_POINTS * 16:].view(torch.int32)
+        _lib.check(lib.mpsr_kitti_stats_slices(ctypes.byref(batch), p(overlaps), p(slices_d), slices_h, n_slices,
+                                               p(thr_d), p(n_thr_d), n_thr.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                               int(compute_aos), p(counts), p(sims), p(ws), ws.numel(), s))
+        out_h = out.cpu().numpy()
+    sims_h = out_h[:n_total * N_POINTS * 16].view(np.float64).reshape(n_slices, N_CONFIGS, N_POINTS, 2)
+    counts_h = out_h[n_total * N_POINTS * 16:].view(np.int32).reshape(n_slices, N_CONFIGS, N_POINTS, 3)
+    results = {}
+    for k, (key, _, _) in enumerate(table):
+        results[key] = _result(thresholds[k], counts_h[k], sims_h[k], flags[key[1]], compute_aos)
+    return results
 
 
 def _atoi(s):
@@ -311,14 +460,26 @@ def _load_gt(gt_label_dir, indices):
     return gt
 
 
-def evaluate_dirs(gt_label_dir, result_dir, iou='standard', device=None):
-    """The C++ program's inputs: evaluates the frames with a file in result_dir/data/ (index = getEvalIndices') against
-    gt_label_dir/<index %06d>.txt.  Raises FileNotFoundError if a frame's ground truth is missing."""
+def _load_dirs(gt_label_dir, result_dir):
     data = os.path.join(result_dir, 'data')
     indices = _frame_indices(os.listdir(data))
     gt = _load_gt(gt_label_dir, indices)
     dets = [parse_label_file(os.path.join(data, '%06d.txt' % idx), detections=True) for idx in indices]
+    return gt, dets
+
+
+def evaluate_dirs(gt_label_dir, result_dir, iou='standard', device=None):
+    """The C++ program's inputs: evaluates the frames with a file in result_dir/data/ (index = getEvalIndices') against
+    gt_label_dir/<index %06d>.txt.  Raises FileNotFoundError if a frame's ground truth is missing."""
+    gt, dets = _load_dirs(gt_label_dir, result_dir)
     return evaluate(gt, dets, iou, device)
+
+
+def evaluate_dirs_sliced(gt_label_dir, result_dir, ious=('standard',), depth_edges=(), device=None):
+    """evaluate_sliced of evaluate_dirs' frames.  The arguments are checked before a file is read."""
+    slice_table(ious, depth_edges)
+    gt, dets = _load_dirs(gt_label_dir, result_dir)
+    return evaluate_sliced(gt, dets, ious, depth_edges, device)
 
 
 def evaluate_predictions(predictions, classes, score_threshold, gt_label_dir, project_3d_box=False, frame_info=None,
@@ -372,17 +533,53 @@ def format_report(result, step=None):
     return '\n'.join(lines) + '\n'
 
 
-def main(argv=None):
+def format_sliced_report(results, step=None):
+    """format_report of every slice of evaluate_sliced's result, each under its heading line '== <iou> <bin> =='."""
+    return ''.join('== %s %s ==\n%s' % (iou, label, format_report(result, step))
+                   for (iou, label), result in results.items())
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description='KITTI object evaluation on the GPU (the output of '
                                              'evaluate_object_3d_offline)')
     ap.add_argument('gt_dir', help='ground-truth label_2 directory')
     ap.add_argument('result_dir', help='directory holding data/<index>.txt detection files')
     ap.add_argument('--low-iou', action='store_true', help='MIN_OVERLAP 0.5 / 0.25 / 0.25 (the _low_iou program)')
+    ap.add_argument('--both-iou', action='store_true',
+                    help='both MIN_OVERLAP sets in one pass; the report of each under a heading line')
+    ap.add_argument('--depth-edges', type=float, nargs='+', default=None, metavar='M',
+                    help='also AP per depth bin: the bins\' edges in metres, increasing (an edge belongs to the bin above)')
+    return ap
+
+
+def parse_args(argv=None):
+    """The command line's arguments; --low-iou together with --both-iou and edges evaluate_sliced refuses are argument
+    errors."""
+    ap = build_parser()
     args = ap.parse_args(argv)
-    result = evaluate_dirs(args.gt_dir, args.result_dir, 'low' if args.low_iou else 'standard')
+    if args.low_iou and args.both_iou:
+        ap.error('--low-iou and --both-iou exclude each other')
+    args.ious = ('standard', 'low') if args.both_iou else ('low',) if args.low_iou else ('standard',)
+    args.sliced = args.both_iou or args.depth_edges is not None
+    if args.sliced:
+        try:
+            slice_table(args.ious, args.depth_edges or ())
+        except ValueError as e:
+            ap.error(str(e))
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     # the program prints the result directory's last component (:898-902)
     cut = args.result_dir.rfind('/')
-    sys.stdout.write(format_report(result, args.result_dir[cut + 1:] if cut >= 0 else None))
+    step = args.result_dir[cut + 1:] if cut >= 0 else None
+    if args.sliced:
+        results = evaluate_dirs_sliced(args.gt_dir, args.result_dir, args.ious, args.depth_edges or ())
+        sys.stdout.write(format_sliced_report(results, step))
+        return 0
+    result = evaluate_dirs(args.gt_dir, args.result_dir, args.ious[0])
+    sys.stdout.write(format_report(result, step))
     return 0
 
 

@@ -14,6 +14,9 @@ With --breakdown every predicted box is also set against its own label (image, B
 rates) and every per-object table is split by the label's depth (--depth-edges), its KITTI difficulty and the IoU of the
 fed 2-D box (--box-iou-edges): the overall overlap lines per checkpoint and, in long format,
 metrics/<split>/breakdown_<split>.csv.
+With --ap-slices KITTI AP is also computed per IoU set (--ap-ious, default both) and depth bin (--ap-depth-edges, default
+10 .. 50 m) in one pass over the same frames: kitti_reports/<split>/<step>_slices.txt and, in long format,
+metrics/<split>/ap_slices_<split>.csv.
 """
 import argparse
 import sys
@@ -45,6 +48,7 @@ def build_parser():
     ap.add_argument('--fit-viewing-angle', action='store_true',
                     help='--fit-centroids: fit the viewing angle as well')
     evaluator.add_breakdown_arguments(ap)
+    evaluator.add_ap_slices_arguments(ap)
     return ap
 
 
@@ -61,6 +65,9 @@ def format_result(result):
     for name, st in result.get('breakdown', {}).get('all', {}).get('object', {}).items():
         lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
             name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
+    if 'kitti_slices' in result:
+        from monopsr_amd.core import kitti_eval
+        lines.append(kitti_eval.format_sliced_report(result['kitti_slices'], None))
     if 'centroid_fit' in result:
         lines.append('centroid fit: %s\n' % evaluator.format_centroid_fit(result['centroid_fit']))
     return ''.join(lines)
@@ -71,6 +78,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     centroid_fit = evaluator.centroid_fit_options(ap, args)
     breakdown = evaluator.breakdown_options(ap, args)
+    ap_slices = evaluator.ap_slices_options(ap, args)
     from monopsr_amd.core import config_utils
     from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
     from monopsr_amd.datasets.kitti.kitti_dataset import KittiDataset
@@ -84,7 +92,7 @@ def main(argv=None):
     ev = evaluator.Evaluator(model, dataset, score_threshold=threshold, predictions_base_dir=args.predictions_dir,
                              iou='low' if args.low_iou else 'standard', metric_stats=True,
                              scene_metrics='surface' if args.surface_metrics else args.scene_metrics,
-                             centroid_fit=centroid_fit, breakdown=breakdown)
+                             centroid_fit=centroid_fit, breakdown=breakdown, ap_slices=ap_slices)
     if args.repeat:
         max_iterations = getattr(train_config, 'max_iterations', None)
         if max_iterations is None and args.max_idle is None:

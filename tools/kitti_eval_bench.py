@@ -1,7 +1,9 @@
 """KITTI evaluation timing on a seeded synthetic KITTI-val-sized set (3769 frames, ground truths with DontCare regions,
 20-50 detections per frame): `evaluate` end to end, its GPU kernels alone (event-timed around each mpsr_kitti_* call),
-and the tests' CPU restatement of the C++ evaluator on a subset of frames.
-    python tools/kitti_eval_bench.py [--frames 3769] [--cpu-frames 100] [--repeats 3]"""
+and the tests' CPU restatement of the C++ evaluator on a subset of frames.  With --slices also `evaluate_sliced` with
+both IoU sets and the default depth edges (14 slices) end to end and per pass, next to `evaluate` called once per slice on
+frames rewritten beforehand as DESIGN.md section 7.12 defines a bin.
+    python tools/kitti_eval_bench.py [--frames 3769] [--cpu-frames 100] [--repeats 3] [--slices]"""
 import argparse
 import os
 import sys
@@ -57,7 +59,8 @@ def synthetic(n_frames, seed=0):
 
 class KernelTimer(object):
     """Wraps the mpsr_kitti_* bindings so that every call is bracketed by events on the current stream."""
-    NAMES = ("mpsr_kitti_overlaps", "mpsr_kitti_match", "mpsr_kitti_stats")
+    NAMES = ("mpsr_kitti_overlaps", "mpsr_kitti_match", "mpsr_kitti_stats", "mpsr_kitti_match_slices",
+             "mpsr_kitti_stats_slices")
 
     def __init__(self):
         self.lib = _lib.lib()
@@ -89,11 +92,73 @@ class KernelTimer(object):
             setattr(self.lib, n, self.orig[n])
 
 
+def rewritten(gt, dets, lo, hi):
+    """Parsed frames as the definition of the bin lo <= z < hi rewrites their label files: a ground truth outside it
+    gets occlusion 3, a detection outside it a class nobody evaluates."""
+    out_gt, out_det = [], []
+    for g, d in zip(gt, dets):
+        rows = g.rows.copy()
+        rows[~((rows[:, ke.TZ] >= lo) & (rows[:, ke.TZ] < hi)), ke.OCCLUSION] = 3
+        out_gt.append(ke.Frame(g.codes, rows))
+        codes = d.codes.copy()
+        codes[~((d.rows[:, ke.TZ] >= lo) & (d.rows[:, ke.TZ] < hi))] = ke.OTHER
+        out_det.append(ke.Frame(codes, d.rows))
+    return out_gt, out_det
+
+
+def time_slices(gt, dets, repeats):
+    """evaluate_sliced (both IoU sets x ('all' + the default depth bins)) against one evaluate per slice."""
+    from monopsr_amd.core import evaluator_utils as eu
+    ious, edges = ("standard", "low"), eu.DEFAULT_DEPTH_EDGES
+    table = ke.slice_table(ious, edges)
+    t0 = time.perf_counter()
+    frames = {}
+    for (_, label), lo, hi in table:
+        if label not in frames:
+            frames[label] = (gt, dets) if lo is None else rewritten(gt, dets, lo, hi)
+    print("%d slices; frames rewritten per bin beforehand in %.2f s (not timed below)"
+          % (len(table), time.perf_counter() - t0))
+    sliced = ke.evaluate_sliced(gt, dets, ious, edges)  # warm-up
+    torch.cuda.synchronize()
+    timer = KernelTimer()
+    try:
+        ends, kernels = [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            sliced = ke.evaluate_sliced(gt, dets, ious, edges)
+            torch.cuda.synchronize()
+            ends.append(time.perf_counter() - t0)
+            kernels.append(timer.take())
+        k = kernels[int(np.argsort(ends)[len(ends) // 2])]
+        print("evaluate_sliced end to end: median %.1f ms of %d (min %.1f ms)"
+              % (1e3 * float(np.median(ends)), len(ends), 1e3 * min(ends)))
+        print("GPU kernels: overlaps %.2f ms, match %.2f ms, stats + frame-order sum %.2f ms (total %.2f ms)"
+              % (k["mpsr_kitti_overlaps"], k["mpsr_kitti_match_slices"], k["mpsr_kitti_stats_slices"], sum(k.values())))
+        ends, kernels = [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            single = {(iou, label): ke.evaluate(*frames[label], iou=iou) for (iou, label), _, _ in table}
+            torch.cuda.synchronize()
+            ends.append(time.perf_counter() - t0)
+            kernels.append(timer.take())
+        k = kernels[int(np.argsort(ends)[len(ends) // 2])]
+        print("evaluate, %d calls on rewritten frames: median %.1f ms of %d (min %.1f ms)"
+              % (len(table), 1e3 * float(np.median(ends)), len(ends), 1e3 * min(ends)))
+        print("GPU kernels: overlaps %.2f ms, match %.2f ms, stats + frame-order sum %.2f ms (total %.2f ms)"
+              % (k["mpsr_kitti_overlaps"], k["mpsr_kitti_match"], k["mpsr_kitti_stats"], sum(k.values())))
+    finally:
+        timer.close()
+    same = all(ke.format_report(sliced[key]) == ke.format_report(single[key]) for key in single)
+    print("the %d reports of both ways are %s" % (len(single), "equal" if same else "DIFFERENT"))
+    print(ke.format_sliced_report({key: sliced[key] for key in list(sliced)[:3]}), end="")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=3769)
     ap.add_argument("--cpu-frames", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--slices", action="store_true", help="also time evaluate_sliced against one evaluate per slice")
     args = ap.parse_args()
     t0 = time.perf_counter()
     gt_texts, det_texts = synthetic(args.frames)
@@ -122,6 +187,8 @@ def main():
     print("GPU kernels: overlaps %.2f ms, match %.2f ms, stats + frame-order sum %.2f ms (total %.2f ms)"
           % (k["mpsr_kitti_overlaps"], k["mpsr_kitti_match"], k["mpsr_kitti_stats"], sum(k.values())))
     print(ke.format_report(result, None), end="")
+    if args.slices:
+        time_slices(gt, dets, args.repeats)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import test_kitti_eval as restated
     n = min(args.cpu_frames, args.frames)
