@@ -1238,6 +1238,52 @@ int mpsr_scene_surface_score(const int *box_frame, const int *box_frame_host, co
                              int n_boxes, int map_h, int map_w, const void *workspace, size_t workspace_bytes,
                              void *scratch, size_t scratch_bytes, int *counts, double *sums, mpsr_stream_t stream);
 
+/* ---- The surfaces as meshes (additive to ABI 13) ----
+ * Runs after mpsr_scene_surface_render on the same stream, the same inputs and the same max_edge_dz and max_span_px,
+ * and reads that call's workspace (the vertex table and the keys); its own workspace is separate.
+ * A triangle t is IN THE MESH when it is DRAWN under mpsr_scene_surface_render's rule (one device function decides
+ * both) and, with visible_only != 0, the low 32 bits of at least one key of its frame equal t: it won a pixel.  A map
+ * point is a VERTEX when at least one of the (up to six) triangles it is a corner of is in the mesh; no other point
+ * appears in the output.
+ * Vertices are written frame after frame, box after box, in map-point order; faces frame after frame, box after box,
+ * in triangle-id order.  Of the V vertices: xyz (V, 3) float32, the input bits; rgb (V, 3) float32 =
+ * images[f][3 (row w + col) + c] at row = rint(u1 / u2), col = rint(u0 / u2) (u as in mpsr_scene_project, half to
+ * even), (0, 0, 0) where that pixel is outside the frame or images is null; normal (V, 3) float32; vertex_box (V)
+ * int32 = b.  Of the F faces: faces (F, 3) int32 = the corners (a, c, b) of mpsr_scene_surface_render's (a, b, c) --
+ * k = 0: (v00, v10, v01), k = 1: (v11, v01, v10); with x right, y down and z forward (c - a) x (b - a) of an unfolded
+ * grid points toward the camera -- as FRAME-LOCAL indices, the vertex's rank among its frame's vertices; face_box (F)
+ * int32 = b.  The order is never swapped by the sign of the screen area: a fold shows as a flipped normal.
+ * normal: the sum, in increasing triangle id, of (c - a) x (b - a) over the vertex's triangles in the mesh, in fp64
+ * from the float32 coordinates without contraction (differences, products, then u_y v_z - u_z v_y and so on), divided
+ * by its fp64 length sqrt((n_x n_x + n_y n_y) + n_z n_z), each component rounded once; (0, 0, 0) when the length is 0
+ * or not finite.  area_per_box (n_boxes) fp64 = the sum of 0.5 |(c - a) x (b - a)| over the box's faces: thread
+ * n % 256 adds the box's triangle n in increasing n, then mpsr_scene_surface_score's lane-ordered wave reduction and
+ * combine in wave order.
+ * vertex_box_offset / face_box_offset (n_boxes + 1) and vertex_frame_offset / face_frame_offset (n_frames + 1) int64:
+ * box b owns rows box_offset[b] .. box_offset[b + 1], frame f rows frame_offset[f] .. frame_offset[f + 1]; the last
+ * entries are V and F.  As with mpsr_scene_compact the vertex outputs hold n_boxes map_h map_w rows and the face
+ * outputs n_boxes 2 (map_h - 1)(map_w - 1) rows; rows from V and F on are not written, and the caller reads the
+ * totals from the offset tables.  One byte flag per triangle set by plain stores, counts and ranks from wave ballots,
+ * one-workgroup scans: no atomics, and two calls return the same bytes.
+ * Checked on the host before any launch: what mpsr_scene_surface_render checks (map_h or map_w < 2, the 2^32 triangle
+ * ids, max_edge_dz NaN or <= 0, max_span_px outside 1..1024, null pointers, the frame tables);
+ * n_boxes map_h map_w > INT_MAX is MPSR_ERR_INVALID_ARG; either workspace too small is MPSR_ERR_WORKSPACE.  n_boxes or
+ * n_frames 0 returns MPSR_OK with the offset tables zeroed (a null table is left alone) and nothing else written. */
+
+/* Bytes of the mesh workspace: one byte per triangle, one int32 rank per map point, two int32 counts per box.  0 for
+ * empty or refused sizes. */
+size_t mpsr_scene_surface_mesh_workspace_bytes(int n_boxes, int map_h, int map_w);
+
+int mpsr_scene_surface_mesh(const float *xyz_global, const int *box_frame, const int *box_frame_host,
+                            const double *cam_p, const int *frame_hw, const int *frame_hw_host,
+                            const long long *pixel_offset, const long long *pixel_offset_host,
+                            const float *const *images, int n_frames, int n_boxes, int map_h, int map_w,
+                            float max_edge_dz, int max_span_px, int visible_only, const void *render_workspace,
+                            size_t render_workspace_bytes, void *mesh_workspace, size_t mesh_workspace_bytes,
+                            float *xyz, float *rgb, float *normal, int *vertex_box, int *faces, int *face_box,
+                            double *area_per_box, long long *vertex_box_offset, long long *vertex_frame_offset,
+                            long long *face_box_offset, long long *face_frame_offset, mpsr_stream_t stream);
+
 /* ---- Fitting a centroid to its 2-D box (additive to ABI 13) ----
  * The reference's inference-time projection alignment (core/instances/instance_metrics.py np_proj_error and
  * scipy_proj_error*, datasets/kitti/instance_utils.py proj_points and get_exp_proj_uv_map).  Per box: local (h w, 3)

@@ -254,6 +254,10 @@ SIGNATURES = {
                                          c_f, c_f, c_f]),
     "mpsr_scene_surface_score": (c_i, [c_f, ctypes.c_void_p, c_f, c_f, c_f, c_f, c_f, c_i, ctypes.c_longlong, c_i, c_i,
                                        c_i, c_f, c_sz, c_f, c_sz, c_f, c_f, c_f]),
+    "mpsr_scene_surface_mesh_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "mpsr_scene_surface_mesh": (c_i, [c_f, c_f, ctypes.c_void_p, c_f, c_f, ctypes.c_void_p, c_f, ctypes.c_void_p, c_f,
+                                      c_i, c_i, c_i, c_i, ctypes.c_float, c_i, c_i, c_f, c_sz, c_f, c_sz] + [c_f] * 11
+                                + [c_f]),
     "mpsr_proj_points": (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
                                c_f]),
     "mpsr_proj_fit": (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_double,

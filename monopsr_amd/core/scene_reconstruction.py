@@ -25,6 +25,10 @@ reported next to it.
 render_instance_surfaces lifts that limit: it joins the cells of a box's map into triangles and
 rasterises them through a z-buffer of its own, so that the depth map and the instance image are dense, and scores them
 the same way (SurfaceResult, SurfaceScores, SURFACE_METRIC_NAMES).  reconstruct_frames(..., surfaces={...}) renders both.
+
+extract_instance_meshes returns the triangles render_instance_surfaces draws as meshes: indexed
+faces over the map points they use, with colours, normals and per-box areas; write_mesh_ply writes one frame's as a PLY
+file with faces.
 """
 import ctypes
 import os
@@ -129,13 +133,15 @@ class SceneResult(object):
     frame_offset[f] .. frame_offset[f+1]), depth_maps / instance_maps: lists of (H_f, W_f) float32 / uint8,
     kept_per_box / visible_per_box (B,) int32.  frame_offset_host and box_frame_host are their host copies.  scores: a
     SceneScores when the call was given ground truth, else None.  surfaces: the SurfaceResult of the same chunk when
-    reconstruct_frames was asked for it, else None."""
+    reconstruct_frames was asked for it, else None.  meshes: the MeshResult of the same chunk when reconstruct_frames
+    was asked for it, else None."""
     __slots__ = ('xyz', 'rgb', 'box', 'pixel', 'frame_offset', 'depth_maps', 'instance_maps', 'kept_per_box',
-                 'visible_per_box', 'frame_offset_host', 'box_frame_host', 'scores', 'surfaces')
+                 'visible_per_box', 'frame_offset_host', 'box_frame_host', 'scores', 'surfaces', 'meshes')
 
     def __init__(self, **kw):
         kw.setdefault('scores', None)
         kw.setdefault('surfaces', None)
+        kw.setdefault('meshes', None)
         for k in self.__slots__:
             setattr(self, k, kw[k])
 
@@ -370,7 +376,9 @@ def reconstruct_frames(model, samples, outs, min_score=None, visible_only=False,
     project_instance_points takes it (box_gt_id over the frames' first num_objs rows, frame after frame).
     surfaces: None, or a dict of render_instance_surfaces' options max_edge_dz and max_span_px ({} for the defaults):
     the same global maps, masks and keep flags are also rendered as surfaces, with the same ground truth, into
-    result.surfaces.  -> SceneResult."""
+    result.surfaces.  With 'mesh': True in that dict the drawn triangles are also returned as meshes coloured from
+    rgb_image (extract_instance_meshes of the same rendering; 'mesh_visible_only': only the triangles that win a pixel)
+    in result.meshes.  -> SceneResult."""
     import torch
     from monopsr_amd.core import constants
     from monopsr_amd.datasets.kitti import instance_utils
@@ -399,11 +407,16 @@ def reconstruct_frames(model, samples, outs, min_score=None, visible_only=False,
                                          valid_mask=mask, keep=keep, visible_only=visible_only,
                                          ground_truth=ground_truth)
         if surfaces is not None:
-            unknown = set(surfaces) - {'max_edge_dz', 'max_span_px'}
+            unknown = set(surfaces) - {'max_edge_dz', 'max_span_px', 'mesh', 'mesh_visible_only'}
             if unknown:
                 raise ValueError('surfaces: unknown options %s' % sorted(unknown))
-            result.surfaces = render_instance_surfaces(glob, box_frame, cam_p, shapes, valid_mask=mask, keep=keep,
-                                                       ground_truth=ground_truth, **surfaces)
+            run = _surface_run(glob, box_frame, cam_p, shapes, mask, keep,
+                               surfaces.get('max_edge_dz', SURFACE_MAX_EDGE_DZ),
+                               surfaces.get('max_span_px', SURFACE_MAX_SPAN_PX), None)
+            result.surfaces = _surfaces_of(run, ground_truth, False)
+            if surfaces.get('mesh'):  # from the same rendering: one z-buffer serves the maps and the meshes
+                result.meshes = _meshes_of(run, [s['rgb_image'] for s in samples],
+                                           surfaces.get('mesh_visible_only', False))
         return result
 
 
@@ -457,6 +470,66 @@ class SurfaceResult(object):
         return FrameSurface(self.depth_maps[f], self.instance_maps[f], None if self.tri_maps is None else self.tri_maps[f])
 
 
+class _SurfaceRun(object):
+    """The checked inputs of a chunk of surfaces on the device and, after render(), the workspace that
+    mpsr_scene_surface_render has filled: what render_instance_surfaces and extract_instance_meshes share."""
+    __slots__ = ('dev', 'nb', 'mh', 'mw', 'nf', 'total', 'hw', 'bf', 'offs', 'cam', 'xyz_in', 'mask', 'keep',
+                 'max_edge_dz', 'max_span_px', 'hw_d', 'bf_d', 'offs_d', 'ws', 'stream')
+
+    @property
+    def empty(self):
+        """Nothing to launch?"""
+        return self.nf == 0 or self.nb == 0 or self.total == 0
+
+    def render(self):
+        """The device tables, the workspace and mpsr_scene_surface_render (once; not for an empty chunk)."""
+        import torch
+        if self.ws is not None:
+            return
+        lib = _lib.lib()
+        self.hw_d, self.bf_d, self.offs_d = _device_tables(self.hw, self.bf, self.offs, self.dev)
+        self.ws = _empty((lib.mpsr_scene_surface_workspace_bytes(self.nf, self.total, self.nb, self.mh, self.mw),),
+                         torch.uint8, self.dev)
+        self.stream = _lib.stream()
+        _lib.check(lib.mpsr_scene_surface_render(
+            _lib.ptr(self.xyz_in), _lib.ptr(self.mask), _lib.ptr(self.bf_d), _host(self.bf), _lib.ptr(self.keep),
+            _lib.ptr(self.cam), _lib.ptr(self.hw_d), _host(self.hw), _lib.ptr(self.offs_d), _host(self.offs), self.nf,
+            self.nb, self.mh, self.mw, self.max_edge_dz, self.max_span_px, _lib.ptr(self.ws), self.ws.numel(),
+            self.stream))
+
+
+def _surface_run(xyz_global_maps, box_frame, cam_p, frame_shapes, valid_mask, keep, max_edge_dz, max_span_px, device):
+    """The arguments render_instance_surfaces and extract_instance_meshes share, checked and moved to the device.
+    -> _SurfaceRun, nothing launched yet."""
+    import torch
+    if not torch.is_tensor(xyz_global_maps) or not xyz_global_maps.is_cuda:
+        raise _lib.MpsrError('expected xyz_global_maps on the GPU; monopsr_amd has no CPU path')
+    if xyz_global_maps.dim() != 4 or xyz_global_maps.shape[-1] != 3:
+        raise _lib.InvalidArgumentError('xyz_global_maps must be (B, Hm, Wm, 3), got %s' % (tuple(xyz_global_maps.shape),))
+    run = _SurfaceRun()
+    run.dev = dev = xyz_global_maps.device if device is None else torch.device(device)
+    run.nb, run.mh, run.mw = nb, mh, mw = tuple(int(v) for v in xyz_global_maps.shape[:3])
+    if mh < 2 or mw < 2:
+        raise _lib.InvalidArgumentError('a map of %d x %d has no cell (2 x 2 or more)' % (mh, mw))
+    run.max_edge_dz, run.max_span_px = max_edge_dz, max_span_px = float(max_edge_dz), int(max_span_px)
+    if not max_edge_dz > 0.0:
+        raise _lib.InvalidArgumentError('max_edge_dz %r must be greater than 0 (inf: no limit)' % (max_edge_dz,))
+    if not 1 <= max_span_px <= 1024:
+        raise _lib.InvalidArgumentError('max_span_px %r is outside 1..1024' % (max_span_px,))
+    run.hw, run.bf, run.offs = _frame_tables(frame_shapes, box_frame, nb)
+    run.nf = len(run.hw)
+    if nb * (mh - 1) * (mw - 1) * 2 >= 2 ** 32:
+        raise _lib.InvalidArgumentError('%d boxes of %d x %d cells: the triangle id does not fit 32 bits'
+                                        % (nb, mh - 1, mw - 1))
+    run.total = int(run.offs[-1])
+    run.hw_d = run.bf_d = run.offs_d = run.ws = run.stream = None
+    with torch.cuda.device(dev):
+        run.cam = _cameras(cam_p, run.nf, dev)
+        run.xyz_in = xyz_global_maps.detach().to(dev).to(torch.float32).contiguous()
+        run.mask, run.keep = _mask_and_keep(valid_mask, keep, nb, mh * mw, dev)
+    return run
+
+
 def render_instance_surfaces(xyz_global_maps, box_frame, cam_p, frame_shapes, valid_mask=None, keep=None,
                              max_edge_dz=SURFACE_MAX_EDGE_DZ, max_span_px=SURFACE_MAX_SPAN_PX, ground_truth=None,
                              want_tri=False, device=None):
@@ -469,32 +542,18 @@ def render_instance_surfaces(xyz_global_maps, box_frame, cam_p, frame_shapes, va
     max_span_px: nor is one whose pixel extent exceeds this in either direction (1..1024).  want_tri: also return the
     winning triangle id per pixel.  device: where to run (default: the maps' device).  Nothing is copied to the host.
     -> SurfaceResult."""
+    return _surfaces_of(_surface_run(xyz_global_maps, box_frame, cam_p, frame_shapes, valid_mask, keep, max_edge_dz,
+                                     max_span_px, device), ground_truth, want_tri)
+
+
+def _surfaces_of(run, ground_truth, want_tri):
+    """render_instance_surfaces of a _SurfaceRun."""
     import torch
-    if not torch.is_tensor(xyz_global_maps) or not xyz_global_maps.is_cuda:
-        raise _lib.MpsrError('expected xyz_global_maps on the GPU; monopsr_amd has no CPU path')
-    if xyz_global_maps.dim() != 4 or xyz_global_maps.shape[-1] != 3:
-        raise _lib.InvalidArgumentError('xyz_global_maps must be (B, Hm, Wm, 3), got %s' % (tuple(xyz_global_maps.shape),))
-    dev = xyz_global_maps.device if device is None else torch.device(device)
-    nb, mh, mw = (int(v) for v in xyz_global_maps.shape[:3])
-    if mh < 2 or mw < 2:
-        raise _lib.InvalidArgumentError('a map of %d x %d has no cell (2 x 2 or more)' % (mh, mw))
-    max_edge_dz, max_span_px = float(max_edge_dz), int(max_span_px)
-    if not max_edge_dz > 0.0:
-        raise _lib.InvalidArgumentError('max_edge_dz %r must be greater than 0 (inf: no limit)' % (max_edge_dz,))
-    if not 1 <= max_span_px <= 1024:
-        raise _lib.InvalidArgumentError('max_span_px %r is outside 1..1024' % (max_span_px,))
-    hw, bf, offs = _frame_tables(frame_shapes, box_frame, nb)
-    nf = len(hw)
-    if nb * (mh - 1) * (mw - 1) * 2 >= 2 ** 32:
-        raise _lib.InvalidArgumentError('%d boxes of %d x %d cells: the triangle id does not fit 32 bits'
-                                        % (nb, mh - 1, mw - 1))
-    total = int(offs[-1])
+    dev, nb, mh, mw, nf, total, hw, bf, offs = (run.dev, run.nb, run.mh, run.mw, run.nf, run.total, run.hw, run.bf,
+                                                run.offs)
     lib = _lib.lib()
     i32, f32 = torch.int32, torch.float32
     with torch.cuda.device(dev):
-        cam = _cameras(cam_p, nf, dev)
-        xyz_in = xyz_global_maps.detach().to(dev).to(f32).contiguous()
-        mask, keep_d = _mask_and_keep(valid_mask, keep, nb, mh * mw, dev)
         scores = gt = None
         if ground_truth is not None:
             gt = _ground_truth_tables(ground_truth, hw, nb, dev)
@@ -502,20 +561,15 @@ def render_instance_surfaces(xyz_global_maps, box_frame, cam_p, frame_shapes, va
         depth = _empty((total,), f32, dev)
         inst = _empty((total,), torch.uint8, dev)
         tri = _empty((total,), i32, dev) if want_tri else None
-        if nf == 0 or nb == 0 or total == 0:  # nothing to launch: empty maps
+        if run.empty:  # nothing to launch: empty maps
             _fill_empty(depth, inst, scores)
             if tri is not None:
                 tri.fill_(-1)
             tris = torch.zeros((nb,), dtype=i32, device=dev)
             pixels = torch.zeros((nb,), dtype=i32, device=dev)
         else:
-            hw_d, bf_d, offs_d = _device_tables(hw, bf, offs, dev)
-            ws = _empty((lib.mpsr_scene_surface_workspace_bytes(nf, total, nb, mh, mw),), torch.uint8, dev)
-            stream = _lib.stream()
-            _lib.check(lib.mpsr_scene_surface_render(
-                _lib.ptr(xyz_in), _lib.ptr(mask), _lib.ptr(bf_d), _host(bf), _lib.ptr(keep_d), _lib.ptr(cam),
-                _lib.ptr(hw_d), _host(hw), _lib.ptr(offs_d), _host(offs), nf, nb, mh, mw, max_edge_dz, max_span_px,
-                _lib.ptr(ws), ws.numel(), stream))
+            run.render()
+            bf_d, hw_d, offs_d, ws, stream = run.bf_d, run.hw_d, run.offs_d, run.ws, run.stream
             _lib.check(lib.mpsr_scene_surface_resolve(_lib.ptr(bf_d), _host(bf), nf, total, nb, mh, mw, _lib.ptr(ws),
                                                       ws.numel(), _lib.ptr(depth), _lib.ptr(inst), _lib.ptr(tri), stream))
             if scores is None:  # without ground truth: the two per-box counts alone
@@ -532,6 +586,113 @@ def render_instance_surfaces(xyz_global_maps, box_frame, cam_p, frame_shapes, va
     return SurfaceResult(depth_maps=_frame_views(depth, hw, offs), instance_maps=_frame_views(inst, hw, offs),
                          tri_maps=None if tri is None else _frame_views(tri, hw, offs),
                          tris_per_box=tris, pixels_per_box=pixels, scores=scores)
+
+
+# ---- meshes
+
+
+class FrameMesh(object):
+    """One frame of a MeshResult, a mesh of its own: xyz, rgb, normal (v,3) float32, box (v,) int32 and face_box (t,)
+    int32 = the ordinal within the frame (the value of the instance image), faces (t,3) int32 indices into this
+    frame's vertices, area_per_box (n,) float64 of the frame's boxes."""
+    __slots__ = ('xyz', 'rgb', 'normal', 'box', 'faces', 'face_box', 'area_per_box')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+class MeshResult(object):
+    """What extract_instance_meshes returns, device tensors: xyz, rgb, normal (V,3) float32, vertex_box (V,) int32
+    (index into the call's boxes), faces (T,3) int32 = FRAME-LOCAL vertex indices in the order (a, c, b) (counter-
+    clockwise seen from the camera), face_box (T,) int32, area_per_box (B,) float64 (square metres),
+    vertex_box_offset / face_box_offset (B+1,) and vertex_frame_offset / face_frame_offset (F+1,) int64: box b owns
+    rows box_offset[b] .. box_offset[b+1], frame f rows frame_offset[f] .. frame_offset[f+1].  *_host are the host
+    copies of the two frame tables and of box_frame."""
+    __slots__ = ('xyz', 'rgb', 'normal', 'vertex_box', 'faces', 'face_box', 'area_per_box', 'vertex_box_offset',
+                 'vertex_frame_offset', 'face_box_offset', 'face_frame_offset', 'vertex_frame_offset_host',
+                 'face_frame_offset_host', 'box_frame_host')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    @property
+    def num_frames(self):
+        return len(self.vertex_frame_offset_host) - 1
+
+    def frame(self, f):
+        v0, v1 = int(self.vertex_frame_offset_host[f]), int(self.vertex_frame_offset_host[f + 1])
+        t0, t1 = int(self.face_frame_offset_host[f]), int(self.face_frame_offset_host[f + 1])
+        b0, b1 = (int(v) for v in np.searchsorted(self.box_frame_host, [f, f + 1]))
+        return FrameMesh(xyz=self.xyz[v0:v1], rgb=self.rgb[v0:v1], normal=self.normal[v0:v1],
+                         box=self.vertex_box[v0:v1] - b0, faces=self.faces[t0:t1], face_box=self.face_box[t0:t1] - b0,
+                         area_per_box=self.area_per_box[b0:b1])
+
+
+def extract_instance_meshes(xyz_global_maps, box_frame, cam_p, frame_shapes, valid_mask=None, keep=None, images=None,
+                            max_edge_dz=SURFACE_MAX_EDGE_DZ, max_span_px=SURFACE_MAX_SPAN_PX, visible_only=False,
+                            device=None):
+    """The direct wrapper of mpsr_scene_surface_render followed by mpsr_scene_surface_mesh: the triangles
+    render_instance_surfaces draws, as indexed faces over the map points they use.
+
+    The arguments of render_instance_surfaces; images None or F CUDA tensors (h_f, w_f, 3) float32 as
+    project_instance_points takes them: a vertex has the colour of the pixel it projects to, (0, 0, 0) outside the
+    frame or without images.  visible_only: only the triangles that win at least one pixel of the z-buffer.  One copy
+    of the two (F + 1) frame offset tables to the host tells how many vertices and faces there are.  -> MeshResult."""
+    return _meshes_of(_surface_run(xyz_global_maps, box_frame, cam_p, frame_shapes, valid_mask, keep, max_edge_dz,
+                                   max_span_px, device), images, visible_only)
+
+
+def _meshes_of(run, images, visible_only):
+    """extract_instance_meshes of a _SurfaceRun."""
+    import torch
+    dev, nb, mh, mw, nf, hw = run.dev, run.nb, run.mh, run.mw, run.nf, run.hw
+    if images is not None and len(images) != nf:
+        raise _lib.InvalidArgumentError('%d images for %d frames' % (len(images), nf))
+    if nb * mh * mw >= 2 ** 31:
+        raise _lib.InvalidArgumentError('%d boxes of %d x %d points: a vertex index does not fit 31 bits' % (nb, mh, mw))
+    lib = _lib.lib()
+    i32, i64, f32 = torch.int32, torch.int64, torch.float32
+    with torch.cuda.device(dev):
+        table, imgs = None, []
+        if images is not None:
+            for f, im in enumerate(images):
+                if not torch.is_tensor(im) or tuple(im.shape) != (int(hw[f, 0]), int(hw[f, 1]), 3):
+                    raise _lib.InvalidArgumentError('image %d must be a (%d, %d, 3) tensor' % (f, hw[f, 0], hw[f, 1]))
+                imgs.append(im.detach().to(dev).to(f32).contiguous())  # (kept alive until the launches are queued)
+            table = torch.from_numpy(np.asarray([_lib.ptr(im) for im in imgs] or [0], np.uint64).view(np.int64)).to(dev)
+        v_cap, t_cap = nb * mh * mw, nb * 2 * (mh - 1) * (mw - 1)
+        xyz, rgb, normal = (_empty((v_cap, 3), f32, dev) for _ in range(3))
+        vertex_box = _empty((v_cap,), i32, dev)
+        faces, face_box = _empty((t_cap, 3), i32, dev), _empty((t_cap,), i32, dev)
+        area = _empty((nb,), torch.float64, dev)
+        # one buffer for the four tables: [vertex frames | face frames | vertex boxes | face boxes], so that ONE copy
+        # brings both frame tables to the host
+        offsets = _empty((2 * (nf + 1) + 2 * (nb + 1),), i64, dev)
+        v_frame, t_frame = offsets[:nf + 1], offsets[nf + 1:2 * (nf + 1)]
+        v_box, t_box = offsets[2 * (nf + 1):2 * (nf + 1) + nb + 1], offsets[2 * (nf + 1) + nb + 1:]
+        if run.empty:  # nothing to launch: no vertex, no face
+            offsets.zero_()
+            area.zero_()
+            host = np.zeros(2 * (nf + 1), np.int64)
+        else:
+            run.render()
+            ws = _empty((lib.mpsr_scene_surface_mesh_workspace_bytes(nb, mh, mw),), torch.uint8, dev)
+            _lib.check(lib.mpsr_scene_surface_mesh(
+                _lib.ptr(run.xyz_in), _lib.ptr(run.bf_d), _host(run.bf), _lib.ptr(run.cam), _lib.ptr(run.hw_d),
+                _host(run.hw), _lib.ptr(run.offs_d), _host(run.offs), _lib.ptr(table), nf, nb, mh, mw, run.max_edge_dz,
+                run.max_span_px, int(bool(visible_only)), _lib.ptr(run.ws), run.ws.numel(), _lib.ptr(ws), ws.numel(),
+                _lib.ptr(xyz), _lib.ptr(rgb), _lib.ptr(normal), _lib.ptr(vertex_box), _lib.ptr(faces),
+                _lib.ptr(face_box), _lib.ptr(area), v_box.data_ptr(), v_frame.data_ptr(), t_box.data_ptr(),
+                t_frame.data_ptr(), run.stream))
+            host = offsets[:2 * (nf + 1)].cpu().numpy()  # the one copy to the host: V, T and where each frame's are
+        v_host, t_host = host[:nf + 1], host[nf + 1:]
+        nv, nt = int(v_host[-1]), int(t_host[-1])
+    return MeshResult(xyz=xyz[:nv], rgb=rgb[:nv], normal=normal[:nv], vertex_box=vertex_box[:nv], faces=faces[:nt],
+                      face_box=face_box[:nt], area_per_box=area, vertex_box_offset=v_box, vertex_frame_offset=v_frame,
+                      face_box_offset=t_box, face_frame_offset=t_frame, vertex_frame_offset_host=v_host,
+                      face_frame_offset_host=t_host, box_frame_host=run.bf)
 
 
 SURFACE_DIRS = ('depth_surface', 'instances_surface')
@@ -656,3 +817,97 @@ def save_empty_frame(out_dirs, name, image_shape):
     ply = os.path.join(out_dirs['points'], name + '.ply')
     write_ply(ply, np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8), np.zeros(0, np.int32))
     return (ply,) + _save_maps(out_dirs, SCENE_DIRS[1:], name, *_empty_maps(image_shape))
+
+
+# ---- mesh files
+
+_MESH_VERTEX_DTYPE = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4'),
+                               ('red', 'u1'), ('green', 'u1'), ('blue', 'u1'), ('box', '<i4')])
+_MESH_FACE_DTYPE = np.dtype([('n', 'u1'), ('v', '<i4', (3,))])
+_MESH_HEADER = ('ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n'
+                'property float z\nproperty float nx\nproperty float ny\nproperty float nz\nproperty uchar red\n'
+                'property uchar green\nproperty uchar blue\nproperty int box\nelement face %d\n'
+                'property list uchar int vertex_indices\nend_header\n')
+
+
+def write_mesh_ply(path, xyz, faces, rgb=None, normal=None, box=None):
+    """Binary little-endian PLY of n vertices (float x y z, float nx ny nz, uchar red green blue, int box) and t
+    triangles (list uchar int vertex_indices): what MeshLab and CloudCompare open.  xyz (n,3); faces (t,3) ints in
+    [0, n); rgb (n,3) float (colours_to_uint8) or uint8, None: 0; normal (n,3), None: 0; box (n,) int, None: 0.  n and
+    t may be 0."""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    faces = np.asarray(faces).reshape(-1, 3)
+    n = len(xyz)
+    if faces.size and (int(faces.min()) < 0 or int(faces.max()) >= n):
+        raise ValueError('faces index vertices outside [0, %d)' % n)
+    v = np.zeros(n, _MESH_VERTEX_DTYPE)
+    v['x'], v['y'], v['z'] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if normal is not None:
+        normal = np.asarray(normal, np.float32).reshape(n, 3)
+        v['nx'], v['ny'], v['nz'] = normal[:, 0], normal[:, 1], normal[:, 2]
+    if rgb is not None:
+        rgb = np.asarray(rgb)
+        c = (rgb if rgb.dtype == np.uint8 else colours_to_uint8(rgb)).reshape(n, 3)
+        v['red'], v['green'], v['blue'] = c[:, 0], c[:, 1], c[:, 2]
+    if box is not None:
+        v['box'] = np.asarray(box).reshape(n)
+    t = np.zeros(len(faces), _MESH_FACE_DTYPE)
+    t['n'] = 3
+    t['v'] = faces
+    with open(path, 'wb') as f:
+        f.write((_MESH_HEADER % (n, len(faces))).encode('ascii'))
+        f.write(v.tobytes())
+        f.write(t.tobytes())
+
+
+def read_mesh_ply(path):
+    """A file of write_mesh_ply -> (xyz (n,3) float32, faces (t,3) int32, rgb (n,3) uint8, normal (n,3) float32, box
+    (n,) int32)."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    end = data.find(b'end_header\n')
+    if end < 0 or not data.startswith(b'ply\n'):
+        raise ValueError('%s is not a PLY file' % path)
+    header = data[:end + len(b'end_header\n')].decode('ascii')
+    count = {}
+    for line in header.splitlines():
+        if line.startswith('element '):
+            count[line.split()[1]] = int(line.split()[2])
+    if set(count) != {'vertex', 'face'} or header != _MESH_HEADER % (count['vertex'], count['face']):
+        raise ValueError('%s: not the header write_mesh_ply writes' % path)
+    n, t = count['vertex'], count['face']
+    body = data[len(header):]
+    want = n * _MESH_VERTEX_DTYPE.itemsize + t * _MESH_FACE_DTYPE.itemsize
+    if len(body) != want:
+        raise ValueError('%s: %d bytes of vertices and faces, expected %d' % (path, len(body), want))
+    v = np.frombuffer(body, _MESH_VERTEX_DTYPE, n)
+    faces = np.frombuffer(body, _MESH_FACE_DTYPE, t, n * _MESH_VERTEX_DTYPE.itemsize)
+    if t and not bool((faces['n'] == 3).all()):
+        raise ValueError('%s: a face is not a triangle' % path)
+    return (np.stack([v['x'], v['y'], v['z']], 1).astype(np.float32).reshape(n, 3),
+            faces['v'].astype(np.int32).reshape(t, 3), np.stack([v['red'], v['green'], v['blue']], 1).reshape(n, 3),
+            np.stack([v['nx'], v['ny'], v['nz']], 1).astype(np.float32).reshape(n, 3), v['box'].astype(np.int32))
+
+
+MESH_DIRS = ('mesh',)
+
+
+def mesh_output_dirs(base):
+    """{'mesh': <base>/mesh}, created."""
+    return _output_dirs(base, MESH_DIRS)
+
+
+def save_mesh_frame(out_dirs, name, frame_mesh):
+    """mesh/<name>.ply of a FrameMesh.  -> the path."""
+    fm = frame_mesh
+    host = lambda t: t.detach().cpu().numpy()
+    ply = os.path.join(out_dirs['mesh'], name + '.ply')
+    write_mesh_ply(ply, host(fm.xyz), host(fm.faces), host(fm.rgb), host(fm.normal), host(fm.box))
+    return ply
+
+
+def save_empty_mesh_frame(out_dirs, name):
+    """The file of a frame without a box: 0 vertices, 0 faces.  -> the path."""
+    ply = os.path.join(out_dirs['mesh'], name + '.ply')
+    write_mesh_ply(ply, np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
+    return ply

@@ -376,21 +376,26 @@ __global__ void __launch_bounds__(kThreads) score_kernel(const unsigned long lon
     }
 }
 
-// A z-buffer's workspace begins [keys: one uint64 per pixel] [frame_box: n_frames + 1 ints], whatever is drawn into it;
-// take() lays the next region behind them, each aligned to 256 bytes.
-struct ZLayout {
-    size_t keys, frame_box, total = 0;
+// A workspace is a row of regions, each aligned to 256 bytes: take() lays the next one behind the others.
+struct Regions {
+    size_t total = 0;
 
-    ZLayout(int n_frames, long long total_pixels)
-    {
-        keys = take((size_t)total_pixels * sizeof(unsigned long long));
-        frame_box = take(((size_t)n_frames + 1) * sizeof(int));
-    }
     size_t take(size_t bytes)
     {
         const size_t at = total;
         total += mpsr::align_up(bytes, 256);
         return at;
+    }
+};
+
+// A z-buffer's workspace begins [keys: one uint64 per pixel] [frame_box: n_frames + 1 ints], whatever is drawn into it.
+struct ZLayout : Regions {
+    size_t keys, frame_box;
+
+    ZLayout(int n_frames, long long total_pixels)
+    {
+        keys = take((size_t)total_pixels * sizeof(unsigned long long));
+        frame_box = take(((size_t)n_frames + 1) * sizeof(int));
     }
 };
 
@@ -705,6 +710,40 @@ __global__ void __launch_bounds__(kThreads) surface_vertex_kernel(const float *_
     }
 }
 
+// Triangle n of a box (n = 2 (i cells_w + j) + k): its corners (a, b, c) as map points of the box.
+// k = 0: (v00, v01, v10); k = 1: (v11, v10, v01)
+__device__ __forceinline__ void triangle_corners(long long n, int cells_w, int map_w, long long *ia, long long *ib,
+                                                 long long *ic)
+{
+    const long long cell = n >> 1;
+    const long long v00 = (cell / cells_w) * map_w + cell % cells_w;
+    const bool k = n & 1;
+    *ia = k ? v00 + map_w + 1 : v00;
+    *ib = k ? v00 + map_w : v00 + 1;
+    *ic = k ? v00 + 1 : v00 + map_w;
+}
+
+// The one rule for which triangle is DRAWN; the renderer and the mesh's selection both ask it.
+// (ia, ib, ic): the corners as indices into vert and xyz.  p: their screen coordinates, z: their float32 depths, *A:
+// the doubled screen area, ext = c0, c1, r0, r1: the unclamped pixel extent; z, A and ext only where all three
+// vertices are valid.
+__device__ __forceinline__ bool triangle_drawn(const float *xyz, const int2 *vert, long long ia, long long ib,
+                                               long long ic, float max_edge_dz, int max_span_px, int2 *p, float *z,
+                                               long long *A, int *ext)
+{
+    const int2 pa = vert[ia], pb = vert[ib], pc = vert[ic];
+    p[0] = pa, p[1] = pb, p[2] = pc;
+    if (pa.x == kNoVertex || pb.x == kNoVertex || pc.x == kNoVertex) return false;
+    const float za = xyz[3 * ia + 2], zb = xyz[3 * ib + 2], zc = xyz[3 * ic + 2];
+    z[0] = za, z[1] = zb, z[2] = zc;
+    const float dz = fmaxf(fmaxf(za, zb), zc) - fminf(fminf(za, zb), zc);
+    *A = (long long)(pb.x - pa.x) * (pc.y - pa.y) - (long long)(pb.y - pa.y) * (pc.x - pa.x);
+    const int c0 = ceil_div256(min(min(pa.x, pb.x), pc.x)), c1 = floor_div256(max(max(pa.x, pb.x), pc.x));
+    const int r0 = ceil_div256(min(min(pa.y, pb.y), pc.y)), r1 = floor_div256(max(max(pa.y, pb.y), pc.y));
+    ext[0] = c0, ext[1] = c1, ext[2] = r0, ext[3] = r1;
+    return !(dz > max_edge_dz) && *A != 0 && c1 - c0 + 1 <= max_span_px && r1 - r0 + 1 <= max_span_px;
+}
+
 __global__ void __launch_bounds__(kThreads) surface_triangle_kernel(const float *__restrict__ xyz,
                                                                     const int2 *__restrict__ vert,
                                                                     const int *__restrict__ box_frame,
@@ -716,8 +755,8 @@ __global__ void __launch_bounds__(kThreads) surface_triangle_kernel(const float 
                                                                     int *__restrict__ box_tris,
                                                                     int *__restrict__ box_rect)
 {
-    const int cells_w = map_w - 1, cells_h = map_h - 1;
-    const long long points_per_box = (long long)map_h * map_w;
+    const int cells_w = map_w - 1;
+    const long long points_per_box = (long long)map_h * map_w, per_box = 2LL * (map_h - 1) * cells_w;
     // every lane of a wave makes the same number of rounds, so that the wave can combine its per-box bookkeeping
     const long long stride = (long long)gridDim.x * blockDim.x;
     const long long first = (long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63);
@@ -727,58 +766,53 @@ __global__ void __launch_bounds__(kThreads) surface_triangle_kernel(const float 
         int b = -1, drawn = 0;
         int lo_c = INT_MAX, lo_r = INT_MAX, hi_c = INT_MIN, hi_r = INT_MIN;  // the clamped extent, empty
         if (live) {
-            const int k = (int)(t & 1);
-            const long long cell = t >> 1;
-            const int j = (int)(cell % cells_w);
-            const long long rest = cell / cells_w;
-            const int i = (int)(rest % cells_h);
-            b = (int)(rest / cells_h);
-            const long long v00 = (long long)b * points_per_box + (long long)i * map_w + j;
-            // k = 0: (v00, v01, v10); k = 1: (v11, v10, v01)
-            long long ia = k ? v00 + map_w + 1 : v00, ib = k ? v00 + map_w : v00 + 1, ic = k ? v00 + 1 : v00 + map_w;
-            int2 pa = vert[ia], pb = vert[ib], pc = vert[ic];
-            if (pa.x != kNoVertex && pb.x != kNoVertex && pc.x != kNoVertex) {
-                float za = xyz[3 * ia + 2], zb = xyz[3 * ib + 2], zc = xyz[3 * ic + 2];
-                const float dz = fmaxf(fmaxf(za, zb), zc) - fminf(fminf(za, zb), zc);
-                long long A = (long long)(pb.x - pa.x) * (pc.y - pa.y) - (long long)(pb.y - pa.y) * (pc.x - pa.x);
-                const int c0 = ceil_div256(min(min(pa.x, pb.x), pc.x)), c1 = floor_div256(max(max(pa.x, pb.x), pc.x));
-                const int r0 = ceil_div256(min(min(pa.y, pb.y), pc.y)), r1 = floor_div256(max(max(pa.y, pb.y), pc.y));
-                if (!(dz > max_edge_dz) && A != 0 && c1 - c0 + 1 <= max_span_px && r1 - r0 + 1 <= max_span_px) {
-                    drawn = 1;
-                    if (A < 0) {  // the other facing: swap the second and the third vertex
-                        const int2 p = pb;
-                        pb = pc;
-                        pc = p;
-                        const float zz = zb;
-                        zb = zc;
-                        zc = zz;
-                        A = -A;
-                    }
-                    const int f = box_frame[b];
-                    const int h = frame_hw[2 * f], w = frame_hw[2 * f + 1];
-                    const int cc0 = max(c0, 0), cc1 = min(c1, w - 1), rr0 = max(r0, 0), rr1 = min(r1, h - 1);
-                    if (cc0 <= cc1 && rr0 <= rr1) {
-                        lo_c = cc0, hi_c = cc1, lo_r = rr0, hi_r = rr1;
-                        unsigned long long *fkeys = keys + pixel_offset[f];
-                        const long long bcx = pc.x - pb.x, bcy = pc.y - pb.y, cax = pa.x - pc.x, cay = pa.y - pc.y;
-                        const long long abx = pb.x - pa.x, aby = pb.y - pa.y;
-                        const bool own0 = owns(bcx, bcy), own1 = owns(cax, cay), own2 = owns(abx, aby);
-                        const double wa = 1.0 / (double)za, wb = 1.0 / (double)zb, wc = 1.0 / (double)zc;
-                        for (int row = rr0; row <= rr1; ++row) {
-                            const long long sy = (long long)row * kSubPixel;
-                            for (int col = cc0; col <= cc1; ++col) {
-                                const long long sx = (long long)col * kSubPixel;
-                                const long long e0 = bcx * (sy - pb.y) - bcy * (sx - pb.x);
-                                const long long e1 = cax * (sy - pc.y) - cay * (sx - pc.x);
-                                const long long e2 = abx * (sy - pa.y) - aby * (sx - pa.x);
-                                if ((e0 > 0 || (e0 == 0 && own0)) && (e1 > 0 || (e1 == 0 && own1)) &&
-                                    (e2 > 0 || (e2 == 0 && own2))) {
-                                    const double q = ((double)e0 * wa + (double)e1 * wb) + (double)e2 * wc;
-                                    const float zf = (float)((double)A / q);
-                                    atomicMin(fkeys + (long long)row * w + col,
-                                              ((unsigned long long)__float_as_uint(zf) << 32) |
-                                                  (unsigned long long)(unsigned)t);
-                                }
+            b = (int)(t / per_box);
+            long long ia, ib, ic, A;
+            triangle_corners(t - b * per_box, cells_w, map_w, &ia, &ib, &ic);
+            const long long i0 = (long long)b * points_per_box;
+            int2 p[3];
+            float z[3];
+            int ext[4];
+            if (triangle_drawn(xyz, vert, i0 + ia, i0 + ib, i0 + ic, max_edge_dz, max_span_px, p, z, &A, ext)) {
+                const int2 pa = p[0];
+                int2 pb = p[1], pc = p[2];
+                const float za = z[0];
+                float zb = z[1], zc = z[2];
+                const int c0 = ext[0], c1 = ext[1], r0 = ext[2], r1 = ext[3];
+                drawn = 1;
+                if (A < 0) {  // the other facing: swap the second and the third vertex
+                    const int2 pp = pb;
+                    pb = pc;
+                    pc = pp;
+                    const float zz = zb;
+                    zb = zc;
+                    zc = zz;
+                    A = -A;
+                }
+                const int f = box_frame[b];
+                const int h = frame_hw[2 * f], w = frame_hw[2 * f + 1];
+                const int cc0 = max(c0, 0), cc1 = min(c1, w - 1), rr0 = max(r0, 0), rr1 = min(r1, h - 1);
+                if (cc0 <= cc1 && rr0 <= rr1) {
+                    lo_c = cc0, hi_c = cc1, lo_r = rr0, hi_r = rr1;
+                    unsigned long long *fkeys = keys + pixel_offset[f];
+                    const long long bcx = pc.x - pb.x, bcy = pc.y - pb.y, cax = pa.x - pc.x, cay = pa.y - pc.y;
+                    const long long abx = pb.x - pa.x, aby = pb.y - pa.y;
+                    const bool own0 = owns(bcx, bcy), own1 = owns(cax, cay), own2 = owns(abx, aby);
+                    const double wa = 1.0 / (double)za, wb = 1.0 / (double)zb, wc = 1.0 / (double)zc;
+                    for (int row = rr0; row <= rr1; ++row) {
+                        const long long sy = (long long)row * kSubPixel;
+                        for (int col = cc0; col <= cc1; ++col) {
+                            const long long sx = (long long)col * kSubPixel;
+                            const long long e0 = bcx * (sy - pb.y) - bcy * (sx - pb.x);
+                            const long long e1 = cax * (sy - pc.y) - cay * (sx - pc.x);
+                            const long long e2 = abx * (sy - pa.y) - aby * (sx - pa.x);
+                            if ((e0 > 0 || (e0 == 0 && own0)) && (e1 > 0 || (e1 == 0 && own1)) &&
+                                (e2 > 0 || (e2 == 0 && own2))) {
+                                const double q = ((double)e0 * wa + (double)e1 * wb) + (double)e2 * wc;
+                                const float zf = (float)((double)A / q);
+                                atomicMin(fkeys + (long long)row * w + col,
+                                          ((unsigned long long)__float_as_uint(zf) << 32) |
+                                              (unsigned long long)(unsigned)t);
                             }
                         }
                     }
@@ -992,6 +1026,353 @@ extern "C" int mpsr_scene_surface_score(const int *box_frame, const int *box_fra
                        reinterpret_cast<const int *>(ws + L.box_tris), reinterpret_cast<const int *>(ws + L.box_rect),
                        box_frame, box_gt_id, gt_depth, gt_instance, frame_hw, pixel_offset,
                        static_cast<const int *>(scratch), (unsigned)tris_per_box(map_h, map_w), counts, sums);
+    MPSR_CHECK_LAUNCH(who);
+    return MPSR_OK;
+}
+
+// ---- Meshes: the drawn triangles of the surfaces as indexed, coloured faces.  Runs after
+// mpsr_scene_surface_render on the same inputs, reads its vertex table and keys, and has a workspace of its own.
+// mesh_win_kernel, one thread per pixel, flags the triangle that won it (a byte per triangle; equal values race
+// benignly); mesh_select_kernel, one thread per triangle, asks triangle_drawn and, with visible_only, the flag.  A map
+// point is a vertex when one of its (up to six) triangles is selected: every point GATHERS over its own triangles.
+// mesh_count_kernel, one workgroup per box, counts vertices and faces and sums the area (block_tally); scan_kernel
+// gives the offsets of both streams; mesh_vertex_kernel and mesh_face_kernel, one workgroup per box each, write at
+// ranks from wave ballots as write_kernel does.  No atomics at all: two calls return the same bytes.
+
+namespace {
+
+// the triangles of a box that have map point (i, j) as a corner, in increasing id; -1 where the cell is outside the map
+__device__ __forceinline__ void incident_triangles(int i, int j, int cells_h, int cells_w, long long *n)
+{
+    auto cell = [&](int ci, int cj) -> long long {
+        return ci >= 0 && ci < cells_h && cj >= 0 && cj < cells_w ? 2 * ((long long)ci * cells_w + cj) : -1;
+    };
+    const long long c00 = cell(i - 1, j - 1), c01 = cell(i - 1, j), c10 = cell(i, j - 1), c11 = cell(i, j);
+    n[0] = c00 < 0 ? -1 : c00 + 1;  // its v11
+    n[1] = c01;                     // its v10, twice
+    n[2] = c01 < 0 ? -1 : c01 + 1;
+    n[3] = c10;                     // its v01, twice
+    n[4] = c10 < 0 ? -1 : c10 + 1;
+    n[5] = c11;                     // its v00
+}
+
+__device__ __forceinline__ bool point_used(const unsigned char *sel, int p, int map_w, int cells_h, int cells_w)
+{
+    long long n[6];
+    incident_triangles(p / map_w, p % map_w, cells_h, cells_w, n);
+    bool used = false;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) used = used || (n[k] >= 0 && sel[n[k]] != 0);
+    return used;
+}
+
+// o = (c - a) x (b - a) of triangle n of the box whose points start at q, fp64 from the float32 coordinates
+__device__ __forceinline__ void face_cross(const float *q, long long n, int cells_w, int map_w, double *o)
+{
+    long long ia, ib, ic;
+    triangle_corners(n, cells_w, map_w, &ia, &ib, &ic);
+    const float *a = q + 3 * ia, *b = q + 3 * ib, *c = q + 3 * ic;
+    const double ux = (double)c[0] - (double)a[0], uy = (double)c[1] - (double)a[1], uz = (double)c[2] - (double)a[2];
+    const double vx = (double)b[0] - (double)a[0], vy = (double)b[1] - (double)a[1], vz = (double)b[2] - (double)a[2];
+    o[0] = uy * vz - uz * vy;
+    o[1] = uz * vx - ux * vz;
+    o[2] = ux * vy - uy * vx;
+}
+
+__device__ __forceinline__ double length3(const double *o) { return sqrt((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]); }
+
+__global__ void __launch_bounds__(kThreads) mesh_win_kernel(const unsigned long long *__restrict__ keys,
+                                                            long long total_pixels, long long n_tris,
+                                                            unsigned char *__restrict__ sel)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total_pixels;
+         i += (long long)gridDim.x * blockDim.x) {
+        const unsigned long long key = keys[i];
+        if (key != kEmptyKey && (long long)(unsigned)key < n_tris) sel[(unsigned)key] = 1;
+    }
+}
+
+// sel[t] = is triangle t in the mesh; with visible_only sel comes in as mesh_win_kernel's flags
+__global__ void __launch_bounds__(kThreads) mesh_select_kernel(const float *__restrict__ xyz,
+                                                               const int2 *__restrict__ vert, long long n_tris,
+                                                               int map_h, int map_w, float max_edge_dz,
+                                                               int max_span_px, int visible_only, unsigned char *sel)
+{
+    const int cells_w = map_w - 1;
+    const long long points_per_box = (long long)map_h * map_w, per_box = 2LL * (map_h - 1) * cells_w;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n_tris;
+         t += (long long)gridDim.x * blockDim.x) {
+        const long long b = t / per_box, i0 = b * points_per_box;
+        long long ia, ib, ic, A;
+        triangle_corners(t - b * per_box, cells_w, map_w, &ia, &ib, &ic);
+        int2 p[3];
+        float z[3];
+        int ext[4];
+        bool in = triangle_drawn(xyz, vert, i0 + ia, i0 + ib, i0 + ic, max_edge_dz, max_span_px, p, z, &A, ext);
+        if (visible_only) in = in && sel[t] != 0;
+        sel[t] = in ? 1 : 0;
+    }
+}
+
+// one workgroup per box: vertices[b], faces[b] and area[b] = the sum of 0.5 |(c - a) x (b - a)| over its faces, thread
+// n % 256 adding triangle n in slice order, then block_tally
+__global__ void __launch_bounds__(kThreads) mesh_count_kernel(const float *__restrict__ xyz,
+                                                              const unsigned char *__restrict__ sel, int map_h,
+                                                              int map_w, int *__restrict__ vertices,
+                                                              int *__restrict__ faces, double *__restrict__ area)
+{
+    const int b = blockIdx.x, cells_h = map_h - 1, cells_w = map_w - 1;
+    const int points_per_box = map_h * map_w;
+    const long long per_box = 2LL * cells_h * cells_w;
+    const unsigned char *bsel = sel + b * per_box;
+    const float *q = xyz + 3 * (long long)b * points_per_box;
+    int n[2] = {0, 0};  // vertices, faces
+    double s[1] = {0.0};
+    for (int p0 = 0; p0 < points_per_box; p0 += kThreads) {
+        const int p = p0 + threadIdx.x;
+        n[0] += __popcll(__ballot(p < points_per_box && point_used(bsel, p, map_w, cells_h, cells_w)));
+    }
+    for (long long t0 = 0; t0 < per_box; t0 += kThreads) {
+        const long long t = t0 + threadIdx.x;
+        const bool take = t < per_box && bsel[t] != 0;
+        if (take) {
+            double o[3];
+            face_cross(q, t, cells_w, map_w, o);
+            s[0] += 0.5 * length3(o);
+        }
+        n[1] += __popcll(__ballot(take));
+    }
+    block_tally<2, 1>(n, s);
+    if (threadIdx.x == 0) {
+        vertices[b] = n[0];
+        faces[b] = n[1];
+        area[b] = s[0];
+    }
+}
+
+// one workgroup per box: its vertices, in map-point order, to box_offset[b] + rank; rank[point] = the vertex's rank
+// within its FRAME (-1: no vertex), which the faces index
+__global__ void __launch_bounds__(kThreads) mesh_vertex_kernel(const float *__restrict__ xyz_in,
+                                                               const unsigned char *__restrict__ sel,
+                                                               const int *__restrict__ box_frame,
+                                                               const double *__restrict__ cam_p,
+                                                               const int *__restrict__ frame_hw,
+                                                               const float *const *__restrict__ images,
+                                                               const long long *__restrict__ box_offset,
+                                                               const long long *__restrict__ frame_offset, int map_h,
+                                                               int map_w, int *__restrict__ rank,
+                                                               float *__restrict__ xyz, float *__restrict__ rgb,
+                                                               float *__restrict__ normal, int *__restrict__ box)
+{
+    __shared__ int wave_n[kWaves];
+    const int b = blockIdx.x, f = box_frame[b], cells_h = map_h - 1, cells_w = map_w - 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int points_per_box = map_h * map_w;
+    const unsigned char *bsel = sel + b * (2LL * cells_h * cells_w);
+    const long long i0 = (long long)b * points_per_box;
+    const float *q0 = xyz_in + 3 * i0;
+    const float *image = images ? images[f] : nullptr;
+    const int h = frame_hw[2 * f], w = frame_hw[2 * f + 1];
+    const long long in_frame = frame_offset[f];
+    long long base = box_offset[b];
+    for (int p0 = 0; p0 < points_per_box; p0 += kThreads) {
+        const int p = p0 + threadIdx.x;
+        long long n[6];
+        bool on[6];
+        bool take = false;
+        if (p < points_per_box) {
+            incident_triangles(p / map_w, p % map_w, cells_h, cells_w, n);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                on[k] = n[k] >= 0 && bsel[n[k]] != 0;
+                take = take || on[k];
+            }
+        }
+        const unsigned long long mask = __ballot(take);
+        if (lane == 0) wave_n[wave] = __popcll(mask);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int v = 0; v < kWaves; ++v) {
+            before += v < wave ? wave_n[v] : 0;
+            all += wave_n[v];
+        }
+        if (take) {
+            const long long o = base + before + __popcll(mask & ((1ULL << lane) - 1ULL));
+            rank[i0 + p] = (int)(o - in_frame);
+            const float *q = q0 + 3 * (long long)p;
+            xyz[3 * o] = q[0];
+            xyz[3 * o + 1] = q[1];
+            xyz[3 * o + 2] = q[2];
+            // the colour: the image at the point's pixel, mpsr_scene_project's; 0 outside the frame
+            float c[3] = {0.0f, 0.0f, 0.0f};
+            if (image) {
+                double u[3];
+                rows3(cam_p + 12 * f, (double)q[0], (double)q[1], (double)q[2], u);
+                const double col = rint(u[0] / u[2]), row = rint(u[1] / u[2]);
+                if (u[2] > 0.0 && col >= 0.0 && col < (double)w && row >= 0.0 && row < (double)h) {
+                    const float *px = image + 3 * ((long long)(int)row * w + (int)col);
+                    c[0] = px[0], c[1] = px[1], c[2] = px[2];
+                }
+            }
+            rgb[3 * o] = c[0];
+            rgb[3 * o + 1] = c[1];
+            rgb[3 * o + 2] = c[2];
+            // the normal: the faces' cross products added in increasing triangle id
+            double s[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                if (on[k]) {
+                    double e[3];
+                    face_cross(q0, n[k], cells_w, map_w, e);
+                    s[0] += e[0];
+                    s[1] += e[1];
+                    s[2] += e[2];
+                }
+            const double len = length3(s);
+            const bool unit = len > 0.0 && isfinite(len);  // (NaN fails the comparison)
+            normal[3 * o] = unit ? (float)(s[0] / len) : 0.0f;
+            normal[3 * o + 1] = unit ? (float)(s[1] / len) : 0.0f;
+            normal[3 * o + 2] = unit ? (float)(s[2] / len) : 0.0f;
+            box[o] = b;
+        } else if (p < points_per_box) {
+            rank[i0 + p] = -1;
+        }
+        base += all;
+        __syncthreads();  // wave_n is rewritten by the next slice
+    }
+}
+
+// one workgroup per box: its faces, in triangle-id order, to box_offset[b] + rank, as (a, c, b) of the vertices' ranks
+__global__ void __launch_bounds__(kThreads) mesh_face_kernel(const unsigned char *__restrict__ sel,
+                                                             const int *__restrict__ rank,
+                                                             const long long *__restrict__ box_offset, int map_h,
+                                                             int map_w, int *__restrict__ faces,
+                                                             int *__restrict__ face_box)
+{
+    __shared__ int wave_n[kWaves];
+    const int b = blockIdx.x, cells_w = map_w - 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long per_box = 2LL * (map_h - 1) * cells_w;
+    const unsigned char *bsel = sel + b * per_box;
+    const int *brank = rank + (long long)b * map_h * map_w;
+    long long base = box_offset[b];
+    for (long long t0 = 0; t0 < per_box; t0 += kThreads) {
+        const long long t = t0 + threadIdx.x;
+        const bool take = t < per_box && bsel[t] != 0;
+        const unsigned long long mask = __ballot(take);
+        if (lane == 0) wave_n[wave] = __popcll(mask);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int v = 0; v < kWaves; ++v) {
+            before += v < wave ? wave_n[v] : 0;
+            all += wave_n[v];
+        }
+        if (take) {
+            const long long o = base + before + __popcll(mask & ((1ULL << lane) - 1ULL));
+            long long ia, ib, ic;
+            triangle_corners(t, cells_w, map_w, &ia, &ib, &ic);
+            faces[3 * o] = brank[ia];
+            faces[3 * o + 1] = brank[ic];
+            faces[3 * o + 2] = brank[ib];
+            face_box[o] = b;
+        }
+        base += all;
+        __syncthreads();  // wave_n is rewritten by the next slice
+    }
+}
+
+// the mesh's workspace: [sel: one byte per triangle] [rank: one int per map point] [vertices, faces: n_boxes ints each]
+struct MeshLayout : Regions {
+    size_t sel, rank, vertices, faces;
+
+    MeshLayout(int n_boxes, int map_h, int map_w)
+    {
+        sel = take((size_t)n_boxes * tris_per_box(map_h, map_w));
+        rank = take((size_t)n_boxes * map_h * map_w * sizeof(int));
+        vertices = take((size_t)n_boxes * sizeof(int));
+        faces = take((size_t)n_boxes * sizeof(int));
+    }
+};
+
+}  // namespace
+
+extern "C" size_t mpsr_scene_surface_mesh_workspace_bytes(int n_boxes, int map_h, int map_w)
+{
+    if (n_boxes <= 0 || map_h < 2 || map_w < 2 || (long long)n_boxes * map_h * map_w > INT_MAX) return 0;
+    if (n_boxes * tris_per_box(map_h, map_w) >= (1LL << 32)) return 0;
+    return MeshLayout(n_boxes, map_h, map_w).total;
+}
+
+extern "C" int mpsr_scene_surface_mesh(const float *xyz_global, const int *box_frame, const int *box_frame_host,
+                                       const double *cam_p, const int *frame_hw, const int *frame_hw_host,
+                                       const long long *pixel_offset, const long long *pixel_offset_host,
+                                       const float *const *images, int n_frames, int n_boxes, int map_h, int map_w,
+                                       float max_edge_dz, int max_span_px, int visible_only,
+                                       const void *render_workspace, size_t render_workspace_bytes,
+                                       void *mesh_workspace, size_t mesh_workspace_bytes, float *xyz, float *rgb,
+                                       float *normal, int *vertex_box, int *faces, int *face_box,
+                                       double *area_per_box, long long *vertex_box_offset,
+                                       long long *vertex_frame_offset, long long *face_box_offset,
+                                       long long *face_frame_offset, mpsr_stream_t stream)
+{
+    const char *who = "scene_surface_mesh";
+    bool empty;
+    int st = check_surface_sizes(who, n_frames, 0, n_boxes, map_h, map_w, &empty);
+    if (st) return st;
+    MPSR_REQUIRE(max_span_px >= 1 && max_span_px <= kMaxSpan, "%s: max_span_px %d is outside 1..%d", who, max_span_px,
+                 kMaxSpan);
+    MPSR_REQUIRE(max_edge_dz > 0.0f, "%s: max_edge_dz %g must be greater than 0 (+inf: no limit)", who,
+                 (double)max_edge_dz);  // NaN fails the comparison
+    hipStream_t s = mpsr::as_stream(stream);
+    if (empty) {  // no vertex and no face: zeroed offsets are all there is to write (a null table is left alone)
+        long long *const tables[4] = {vertex_box_offset, face_box_offset, vertex_frame_offset, face_frame_offset};
+        for (int k = 0; k < 4; ++k) {
+            const size_t rows = (size_t)(k < 2 ? n_boxes : n_frames) + 1;
+            if (tables[k]) MPSR_CHECK_HIP(hipMemsetAsync(tables[k], 0, rows * sizeof(long long), s));
+        }
+        return MPSR_OK;
+    }
+    MPSR_REQUIRE((long long)n_boxes * map_h * map_w <= INT_MAX,
+                 "%s: %d boxes of %d x %d points: a vertex index does not fit 31 bits", who, n_boxes, map_h, map_w);
+    long long total_pixels;
+    st = check_render_args(who, xyz_global, box_frame, box_frame_host, cam_p, frame_hw, frame_hw_host, pixel_offset,
+                           pixel_offset_host, n_frames, n_boxes, &total_pixels);
+    if (st) return st;
+    MPSR_REQUIRE(xyz && rgb && normal && vertex_box && faces && face_box && area_per_box, "%s: an output is null", who);
+    MPSR_REQUIRE(vertex_box_offset && vertex_frame_offset && face_box_offset && face_frame_offset,
+                 "%s: an offset table is null", who);
+    const SurfaceLayout R(n_frames, total_pixels, n_boxes, map_h, map_w);
+    st = check_workspace(who, render_workspace, render_workspace_bytes, R.total);
+    if (st) return st;
+    const MeshLayout L(n_boxes, map_h, map_w);
+    st = check_workspace(who, mesh_workspace, mesh_workspace_bytes, L.total);
+    if (st) return st;
+    const char *rws = static_cast<const char *>(render_workspace);
+    const unsigned long long *keys = reinterpret_cast<const unsigned long long *>(rws + R.keys);
+    const int2 *vert = reinterpret_cast<const int2 *>(rws + R.vert);
+    char *ws = static_cast<char *>(mesh_workspace);
+    unsigned char *sel = reinterpret_cast<unsigned char *>(ws + L.sel);
+    int *rank = reinterpret_cast<int *>(ws + L.rank);
+    int *n_vertices = reinterpret_cast<int *>(ws + L.vertices), *n_faces = reinterpret_cast<int *>(ws + L.faces);
+    const long long n_tris = n_boxes * tris_per_box(map_h, map_w);
+    if (visible_only) {
+        MPSR_CHECK_HIP(hipMemsetAsync(sel, 0, (size_t)n_tris, s));
+        hipLaunchKernelGGL(mesh_win_kernel, dim3(grid_for(total_pixels)), dim3(kThreads), 0, s, keys, total_pixels,
+                           n_tris, sel);
+    }
+    hipLaunchKernelGGL(mesh_select_kernel, dim3(grid_for(n_tris)), dim3(kThreads), 0, s, xyz_global, vert, n_tris,
+                       map_h, map_w, max_edge_dz, max_span_px, visible_only, sel);
+    hipLaunchKernelGGL(mesh_count_kernel, dim3(n_boxes), dim3(kThreads), 0, s, xyz_global, sel, map_h, map_w,
+                       n_vertices, n_faces, area_per_box);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kThreads), 0, s, n_vertices, n_boxes, box_frame, n_frames,
+                       vertex_box_offset, vertex_frame_offset);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kThreads), 0, s, n_faces, n_boxes, box_frame, n_frames,
+                       face_box_offset, face_frame_offset);
+    hipLaunchKernelGGL(mesh_vertex_kernel, dim3(n_boxes), dim3(kThreads), 0, s, xyz_global, sel, box_frame, cam_p,
+                       frame_hw, images, vertex_box_offset, vertex_frame_offset, map_h, map_w, rank, xyz, rgb, normal,
+                       vertex_box);
+    hipLaunchKernelGGL(mesh_face_kernel, dim3(n_boxes), dim3(kThreads), 0, s, sel, rank, face_box_offset, map_h,
+                       map_w, faces, face_box);
     MPSR_CHECK_LAUNCH(who);
     return MPSR_OK;
 }

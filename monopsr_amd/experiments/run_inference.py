@@ -4,13 +4,14 @@ core/scene_reconstruction.py).
 
     python -m monopsr_amd.experiments.run_inference CONFIG CHECKPOINT --mscnn-dir DIR --output-dir DIR
         [--data-split val|test] [--width-div N] [--no-scenes] [--min-score S] [--visible-only]
-        [--surfaces [--max-edge-dz M] [--max-span-px N]]
+        [--surfaces [--max-edge-dz M] [--max-span-px N]] [--meshes [--mesh-visible-only]]
 
 Under --output-dir: kitti_predictions_3d/<split>/<threshold>/<step>/data/<name>.txt as run_evaluation writes them, and
 scenes/<split>/<step>/points/<name>.ply, depth/<name>.png, instances/<name>.png.  One network pass serves both: the
 scenes are written from the Evaluator's chunks through its chunk_hook.  With --surfaces the instance maps are also
 rendered as surfaces: depth_surface/<name>.png and instances_surface/<name>.png beside the three,
-in the formats of depth/ and instances/.  Split 'test' reads <dataset_dir>/testing and has
+in the formats of depth/ and instances/.  With --meshes (which implies --surfaces) the drawn triangles are also written as
+a coloured mesh per frame, mesh/<name>.ply with faces.  Split 'test' reads <dataset_dir>/testing and has
 no labels; any other split reads the config's data_split_dir, and the AP report is printed when it has a label_2.
 """
 import argparse
@@ -39,6 +40,10 @@ def build_parser():
                     help='--surfaces: a triangle whose depths span more than this many metres is not drawn')
     ap.add_argument('--max-span-px', type=int, default=scene_reconstruction.SURFACE_MAX_SPAN_PX,
                     help='--surfaces: nor is a triangle that spans more than this many pixels')
+    ap.add_argument('--meshes', action='store_true',
+                    help='also write the surfaces as coloured meshes, mesh/<name>.ply with faces (implies --surfaces)')
+    ap.add_argument('--mesh-visible-only', action='store_true',
+                    help='--meshes: only the triangles that win at least one pixel (drop what another surface hides)')
     ap.add_argument('--fit-centroids', action='store_true',
                     help='fit every predicted centroid to its 2-D box first: labels and scenes hold the fitted boxes')
     ap.add_argument('--fit-viewing-angle', action='store_true',
@@ -53,19 +58,23 @@ def scene_dir(output_dir, data_split, global_step):
 class SceneWriter(object):
     """An Evaluator chunk_hook: reconstruct_frames of every chunk, save_frame of every frame.  `base` is the directory
     that takes points/, depth/ and instances/; names collects the frames written.  surfaces: None, or the dict of
-    options reconstruct_frames takes: depth_surface/ and instances_surface/ are written as well."""
+    options reconstruct_frames takes: depth_surface/ and instances_surface/ are written as well, and with 'mesh' in it
+    mesh/."""
 
     def __init__(self, model, base, min_score=None, visible_only=False, surfaces=None):
         self.model, self.base, self.min_score, self.visible_only = model, base, min_score, bool(visible_only)
         self.surfaces = surfaces
+        self.meshes = bool(surfaces and surfaces.get('mesh'))
         self.names = []
-        self._dirs = self._surface_dirs = None
+        self._dirs = self._surface_dirs = self._mesh_dirs = None
 
     def _make_dirs(self):
         if self._dirs is None:
             self._dirs = scene_reconstruction.scene_output_dirs(self.base)
             if self.surfaces is not None:
                 self._surface_dirs = scene_reconstruction.surface_output_dirs(self.base)
+            if self.meshes:
+                self._mesh_dirs = scene_reconstruction.mesh_output_dirs(self.base)
 
     def __call__(self, rows, samples, outs):
         self._make_dirs()
@@ -75,6 +84,8 @@ class SceneWriter(object):
             scene_reconstruction.save_frame(self._dirs, s['sample_name'], scene.frame(f))
             if self.surfaces is not None:
                 scene_reconstruction.save_surface_frame(self._surface_dirs, s['sample_name'], scene.surfaces.frame(f))
+            if self.meshes:
+                scene_reconstruction.save_mesh_frame(self._mesh_dirs, s['sample_name'], scene.meshes.frame(f))
             self.names.append(s['sample_name'])
 
     def finish(self, dataset):
@@ -89,12 +100,33 @@ class SceneWriter(object):
                 scene_reconstruction.save_empty_frame(self._dirs, name, shape)
                 if self.surfaces is not None:
                     scene_reconstruction.save_empty_surface_frame(self._surface_dirs, name, shape)
+                if self.meshes:
+                    scene_reconstruction.save_empty_mesh_frame(self._mesh_dirs, name)
                 self.names.append(name)
+
+
+def parse_args(ap, argv=None):
+    """The parsed command line; --meshes implies --surfaces."""
+    args = ap.parse_args(argv)
+    if args.mesh_visible_only and not args.meshes:
+        ap.error('--mesh-visible-only needs --meshes')
+    args.surfaces = args.surfaces or args.meshes
+    return args
+
+
+def surface_options(args):
+    """-> the `surfaces` of reconstruct_frames the command line asks for (None: no surfaces)."""
+    if not args.surfaces:
+        return None
+    options = dict(max_edge_dz=args.max_edge_dz, max_span_px=args.max_span_px)
+    if args.meshes:
+        options.update(mesh=True, mesh_visible_only=args.mesh_visible_only)
+    return options
 
 
 def main(argv=None):
     ap = build_parser()
-    args = ap.parse_args(argv)
+    args = parse_args(ap, argv)
     centroid_fit = evaluator.centroid_fit_options(ap, args)
     from monopsr_amd.core import config_utils
     from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
@@ -119,7 +151,7 @@ def main(argv=None):
     if not args.no_scenes:
         writer = SceneWriter(model, scene_dir(args.output_dir, dataset.data_split, step),
                              ev.score_threshold if args.min_score is None else args.min_score, args.visible_only,
-                             dict(max_edge_dz=args.max_edge_dz, max_span_px=args.max_span_px) if args.surfaces else None)
+                             surface_options(args))
         ev.chunk_hook = writer
     result = ev.run_once(step)
     if writer is not None:
