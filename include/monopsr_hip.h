@@ -1319,6 +1319,41 @@ int mpsr_proj_fit(const float *local, const float *x0, const float *boxes_2d, co
                   int cam0_shift, int round_box_2d, int use_pixel_centres, double xatol, double fatol, int max_iter,
                   float *x, double *err, double *err0, int *iters, int *evals, int *status, mpsr_stream_t stream);
 
+/* ---- Shape scores over valid points (additive to ABI 13) ----
+ * n boxes, each with a cloud a (n, P, 3) and a cloud b (n, Q, 3), float32; mask_a (n, P) and mask_b (n, Q) float32 or
+ * null.  By convention a is the prediction and b the ground truth.
+ * Valid point: its mask entry is > 0 (a null mask is all ones, a NaN entry is not valid) and its three coordinates
+ * are finite.
+ * Nearest distance: for a valid a_i, d_a[i] = the minimum over the valid b_j of the float32 squared distance in
+ * mpsr_nn_distance_fwd's arithmetic: float differences, float products, (dx dx + dy dy) + dz dz, nothing contracted;
+ * d_b[j] the same in the other direction.  An overflow to +inf propagates.  With null masks and finite clouds d_a
+ * and d_b are mpsr_nn_distance_fwd's dist1 and dist2, bit for bit.
+ * thresholds: a HOST array of T <= MPSR_SHAPE_MAX_THRESHOLDS finite distances > 0, strictly increasing.
+ * counts (n, 2 + 2T) int32: n_a, n_b (the valid points), then within_a[t] = the number of valid a_i with
+ * (double) d_a[i] <= thresholds[t] * thresholds[t] (an fp64 product and an fp64 compare), then within_b[t].
+ * sums (n, 6) fp64: sum of sqrt((double) d_a), sum of (double) d_a, the same two for b, max d_a, max d_b.
+ * table (n, 5 + 3T) float32, computed in fp64 from counts and sums and rounded once: accuracy = sum sqrt d_a / n_a,
+ * completeness = sum sqrt d_b / n_b, chamfer_l1 = (accuracy + completeness) / 2, chamfer_sq = sum d_a / n_a +
+ * sum d_b / n_b, hausdorff = sqrt(max(max d_a, max d_b)), then per threshold precision = within_a / n_a, recall =
+ * within_b / n_b, fscore = 2 p r / (p + r) (0 when p + r == 0).
+ * dist_a (n, P) and dist_b (n, Q) float32, or null: every point's d, NaN at the points that are not valid.
+ * Empty side (n_a == 0 or n_b == 0, P == 0 or Q == 0 included): the box's six sums and its table row are NaN, its
+ * within counts 0, its dist rows NaN; n_a and n_b are still reported.
+ * Every output element is written on every call; n == 0 is a no-op that returns MPSR_OK.  workspace: 8-byte aligned,
+ * mpsr_shape_scores_workspace_bytes(n, P, Q, T) bytes (0 for n == 0 and for refused sizes), overwritten.
+ * MPSR_ERR_INVALID_ARG before any launch: negative sizes, a null cloud or output pointer with a non-empty size, T
+ * outside [0, MPSR_SHAPE_MAX_THRESHOLDS], thresholds that are not finite, not > 0 or not strictly increasing,
+ * n max(P, Q) >= 2^31.  MPSR_ERR_WORKSPACE: a workspace that is too small.
+ * One workgroup per (box, direction, slab of 1024 queries) leaves integer counts and fp64 partial sums in the
+ * workspace; a second kernel adds them in slab order.  fp64 sums in a fixed order, no floating-point atomics: two
+ * calls on the same inputs return the same bytes.  Cost to know: a box with an empty side is still searched, and with
+ * dist_a / dist_b given its rows are then rewritten with NaN by one thread, P + Q single stores. */
+#define MPSR_SHAPE_MAX_THRESHOLDS 8
+size_t mpsr_shape_scores_workspace_bytes(int n, int P, int Q, int T);
+int mpsr_shape_scores(const float *a, const float *mask_a, int P, const float *b, const float *mask_b, int Q, int n,
+                      const double *thresholds, int T, void *workspace, size_t workspace_bytes, int *counts,
+                      double *sums, float *table, float *dist_a, float *dist_b, mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -262,6 +262,10 @@ SIGNATURES = {
                                c_f]),
     "mpsr_proj_fit": (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_double,
                             ctypes.c_double, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
+    "mpsr_shape_scores_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    # thresholds: a host array
+    "mpsr_shape_scores": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, ctypes.POINTER(ctypes.c_double), c_i, c_f, c_sz,
+                                c_f, c_f, c_f, c_f, c_f, c_f]),
 }
 
 

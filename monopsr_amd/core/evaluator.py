@@ -67,6 +67,19 @@ kitti_reports/<split>/<step, 8 digits>_slices.txt (kitti_eval.format_sliced_repo
 metrics/<split>/ap_slices_<split>.csv (evaluator_utils.save_ap_slices).  result['kitti'] and result['report'] keep
 coming from `iou`.
 
+shape_metrics: None, or a dict of options ({} for the defaults), 'val' mode only: 'thresholds'
+(default distance_metrics.DEFAULT_SHAPE_THRESHOLDS: 0.05, 0.1 and 0.2 m, an assumption of this package) and 'placed'
+(default False).  With it every chunk's predicted instance maps are scored against the ground-truth maps over the valid
+points only, after the optional centroid fit (core/distance_metrics.py chunk_shape_scores, one mpsr_shape_scores launch
+per chunk): accuracy, completeness, Chamfer-L1, squared Chamfer and Hausdorff in metres, precision / recall / F-score
+at every threshold, in the object's own frame.  With 'placed' the same once more in the camera frame, of the maps placed
+with the predicted (or fitted) centroid and viewing angle against gt_inst_xyz_maps_global: the number that shows what
+centroid_fit does in 3-D.  The per-object tables stay on the card, and one mpsr_metric_stats launch per table at the end
+takes their statistics with NAN_RULE_ENTRY: result['shape_stats'] and result['placed_stats'] (the names carry the
+prefixes 'shape_' and 'placed_'), with predictions_base_dir one line each in metrics/<split>/shape_metrics_<split>.csv
+and placed_metrics_<split>.csv (save_scene_stats' format), and with breakdown the kinds 'shape' and 'placed'.  METRIC_EMD
+and METRIC_CHAMFER, the reference's two shape numbers over all 48 x 48 points, are not changed by it.
+
 Not built: TF summaries and metrics_to_show.
 """
 import argparse
@@ -98,6 +111,9 @@ _CENTROID_FIT_OPTIONS = ('fit_viewing_angle', 'use_pixel_centres', 'cam0_shift')
 # what Evaluator(breakdown={...}) may hold, with the defaults
 _BREAKDOWN_OPTIONS = dict(depth_edges=evaluator_utils.DEFAULT_DEPTH_EDGES,
                           box_iou_edges=evaluator_utils.DEFAULT_BOX_IOU_EDGES)
+
+# what Evaluator(shape_metrics={...}) may hold
+_SHAPE_METRICS_OPTIONS = ('thresholds', 'placed')
 
 # what Evaluator(ap_slices={...}) may hold, with the defaults
 _AP_SLICES_OPTIONS = dict(ious=('standard', 'low'), depth_edges=evaluator_utils.DEFAULT_DEPTH_EDGES)
@@ -155,7 +171,7 @@ class Evaluator:
     def __init__(self, model, dataset, score_threshold=0.1, predictions_base_dir=None, batch_size=8,
                  project_3d_box=False, iou='standard', compute_metrics=True, compute_losses=True, metric_stats=False,
                  skip_evaluated_checkpoints=True, scene_metrics=False, breakdown=None, ap_slices=None,
-                 centroid_fit=None, chunk_hook=None):
+                 shape_metrics=None, centroid_fit=None, chunk_hook=None):
         if iou not in kitti_eval.MIN_OVERLAP:
             raise ValueError('iou must be one of %s' % sorted(kitti_eval.MIN_OVERLAP))
         if ap_slices is not None:
@@ -194,6 +210,25 @@ class Evaluator:
                          for k, default in _BREAKDOWN_OPTIONS.items()}
         # None, or {'depth_edges': (...), 'box_iou_edges': (...)}: the per-object overlap table and the binned statistics
         self.breakdown = breakdown
+        if shape_metrics is not None:
+            from monopsr_amd.core import distance_metrics
+            if getattr(dataset, 'train_val_test', None) != 'val':
+                raise ValueError("shape_metrics scores the predicted maps against the ground-truth maps: it needs a "
+                                 "'val'-mode dataset, got %r" % (getattr(dataset, 'train_val_test', None),))
+            unknown = set(shape_metrics) - set(_SHAPE_METRICS_OPTIONS)
+            if unknown:
+                raise ValueError('shape_metrics: unknown options %s' % sorted(unknown))
+            shape_metrics = dict(
+                thresholds=distance_metrics.check_thresholds(
+                    shape_metrics.get('thresholds', distance_metrics.DEFAULT_SHAPE_THRESHOLDS)),
+                placed=bool(shape_metrics.get('placed', False)))
+        # None, or {'thresholds': (...), 'placed': bool}: the shape scores over valid points
+        self.shape_metrics = shape_metrics
+        # after a run_once with shape_metrics: (table (n, 5 + 3T) float32 in distance_metrics.shape_metric_names' order,
+        # counts (n, 2 + 2T) int32, sums (n,6) float64, frame (n,) int32) on the device, one row per object in the order
+        # of the pass; placed_table the same in the camera frame (None without 'placed')
+        self.shape_table = None
+        self.placed_table = None
         # after a run_once with breakdown: (table (n,9) float32 in evaluator_utils.PAIR_COLUMNS' order, overlaps (n,4)
         # float64, bins (n,3) int32 in evaluator_utils.BREAKDOWN_AXES' order, frame (n,) int32) on the device
         self.pair_table = None
@@ -235,7 +270,9 @@ class Evaluator:
         same form; the metric table (N, 10) float32 in METRIC_COLUMNS' order, or None; with scene_metrics the scene
         scores (table (N,6) float32, counts (N,6) int32, sums (N,3) float64), else None; with scene_metrics='surface'
         the surface scores in the same form (counts (N,5)), else None; with breakdown the pair table (table (N,9) float32,
-        overlaps (N,4) float64, bins (N,3) int32), else None), all on the device."""
+        overlaps (N,4) float64, bins (N,3) int32), else None; with shape_metrics the shape scores (table (N, 5 + 3T)
+        float32, counts (N, 2 + 2T) int32, sums (N,6) float64), else None; with its 'placed' the same in the camera
+        frame, else None), all on the device."""
         ds, model = self.dataset, self.model
         dev = ds.device
         # the frames in split order, whatever the epoch's shuffle made of sample_list
@@ -249,6 +286,7 @@ class Evaluator:
         table = []
         scene_parts, surface_parts, pair_parts = [], [], []
         self._fits = []
+        shape_parts, placed_parts = [], []
         if with_losses or with_table:
             # the 'val'-mode graph of the same net: method by method, with the ground truth and the offsets
             from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
@@ -265,6 +303,13 @@ class Evaluator:
                     from monopsr_amd.core.instances import instance_metrics
                     outs, fit = instance_metrics.fit_centroids(model, samples, outs, **self.centroid_fit)
                     self._fits.append(fit)
+                if self.shape_metrics is not None:
+                    from monopsr_amd.core import distance_metrics
+                    for parts, scores in zip((shape_parts, placed_parts),
+                                             distance_metrics.chunk_shape_scores(model, samples, outs,
+                                                                                 **self.shape_metrics)):
+                        if scores is not None:
+                            parts.append((scores.table, scores.counts, scores.sums))
                 if self.chunk_hook is not None:
                     self.chunk_hook(rows, samples, outs)
                 if self.scene_metrics:
@@ -332,7 +377,9 @@ class Evaluator:
                 torch.cat(table).contiguous() if with_table else None,
                 tuple(torch.cat(part).contiguous() for part in zip(*scene_parts)) if self.scene_metrics else None,
                 tuple(torch.cat(part).contiguous() for part in zip(*surface_parts)) if self.surface_metrics else None,
-                tuple(torch.cat(part).contiguous() for part in zip(*pair_parts)) if pair_parts else None)
+                tuple(torch.cat(part).contiguous() for part in zip(*pair_parts)) if pair_parts else None,
+                tuple(torch.cat(part).contiguous() for part in zip(*shape_parts)) if shape_parts else None,
+                tuple(torch.cat(part).contiguous() for part in zip(*placed_parts)) if placed_parts else None)
 
     def _rows_to_host(self, b3, b2, frame):
         """One launch, one compaction, one copy: -> (rows (m,14) float64, class index (m,), frame (m,)) of the kept
@@ -356,7 +403,7 @@ class Evaluator:
 
     def run_once(self, global_step=None):
         ds = self.dataset
-        b3, b2, frame, sums, loss_names, loss_sums, table, scene, surface, pairs = self._predict()
+        b3, b2, frame, sums, loss_names, loss_sums, table, scene, surface, pairs, shape, placed = self._predict()
         rows, cls, frame_h = self._rows_to_host(b3, b2, frame)
         names = ds.sample_names
         per_frame = {}
@@ -397,9 +444,16 @@ class Evaluator:
             result['metrics_csv'] = evaluator_utils.save_metric_stats(self.predictions_base_dir, ds.data_split,
                                                                       global_step, result['metric_stats'])
         from monopsr_amd.core.scene_reconstruction import SCENE_METRIC_NAMES, SURFACE_METRIC_NAMES
+        shape_names, placed_names = (), ()
+        if self.shape_metrics is not None:
+            from monopsr_amd.core import distance_metrics
+            shape_names = distance_metrics.shape_metric_names(self.shape_metrics['thresholds'], 'shape_')
+            placed_names = distance_metrics.shape_metric_names(self.shape_metrics['thresholds'], 'placed_')
         for kind, metric_names, parts, save in (
                 ('scene', SCENE_METRIC_NAMES, scene, evaluator_utils.save_scene_stats),
-                ('surface', SURFACE_METRIC_NAMES, surface, evaluator_utils.save_surface_stats)):
+                ('surface', SURFACE_METRIC_NAMES, surface, evaluator_utils.save_surface_stats),
+                ('shape', shape_names, shape, evaluator_utils.save_shape_stats),
+                ('placed', placed_names, placed, evaluator_utils.save_placed_stats)):
             if parts is None:
                 continue
             setattr(self, kind + '_table', parts + (frame,))
@@ -418,7 +472,8 @@ class Evaluator:
             if table is not None:
                 kept.append(('metrics', METRIC_NAMES, table, COLUMN_METRIC))
             for kind, metric_names, parts in (('scene', SCENE_METRIC_NAMES, scene),
-                                              ('surface', SURFACE_METRIC_NAMES, surface)):
+                                              ('surface', SURFACE_METRIC_NAMES, surface),
+                                              ('shape', shape_names, shape), ('placed', placed_names, placed)):
                 if parts is not None:
                     kept.append((kind, metric_names, parts[0], range(len(metric_names))))
             # one launch per table, one copy for all of them
@@ -576,6 +631,35 @@ def breakdown_options(ap, args):
     if edges and not args.breakdown:
         ap.error('--depth-edges and --box-iou-edges require --breakdown')
     return edges if args.breakdown else None
+
+
+def add_shape_metrics_arguments(ap):
+    """run_evaluation's --shape-metrics, --shape-thresholds and --shape-placed."""
+    ap.add_argument('--shape-metrics', action='store_true',
+                    help='also score every predicted instance map against the ground-truth map over the valid points: '
+                         'accuracy, completeness, Chamfer-L1, Hausdorff, F-score (DESIGN.md section 7.14)')
+    ap.add_argument('--shape-thresholds', type=float, nargs='+', default=None, metavar='M',
+                    help='the distance thresholds of precision / recall / F-score in metres (default 0.05 0.1 0.2)')
+    ap.add_argument('--shape-placed', action='store_true',
+                    help='--shape-metrics: also in the camera frame, the maps placed with the predicted (or fitted) '
+                         'centroid')
+
+
+def shape_metrics_options(ap, args):
+    """The Evaluator's shape_metrics of a command line's --shape-metrics, --shape-thresholds and --shape-placed (None
+    without --shape-metrics)."""
+    if (args.shape_thresholds is not None or args.shape_placed) and not args.shape_metrics:
+        ap.error('--shape-thresholds and --shape-placed require --shape-metrics')
+    if not args.shape_metrics:
+        return None
+    options = dict(placed=args.shape_placed)
+    if args.shape_thresholds is not None:
+        from monopsr_amd.core import distance_metrics
+        try:
+            options['thresholds'] = distance_metrics.check_thresholds(args.shape_thresholds)
+        except ValueError as e:
+            ap.error('--shape-thresholds: %s' % e)
+    return options
 
 
 def add_ap_slices_arguments(ap):

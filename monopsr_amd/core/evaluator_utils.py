@@ -341,7 +341,8 @@ def save_metric_stats(predictions_base_dir, data_split, global_step, metric_stat
 
 
 def _save_prefixed_stats(prefix, predictions_base_dir, data_split, global_step, names, stats):
-    """save_scene_stats ('scene_') and save_surface_stats ('surface_'): <prefix>metrics_<split>.csv."""
+    """save_scene_stats ('scene_'), save_surface_stats ('surface_'), save_shape_stats ('shape_') and save_placed_stats
+    ('placed_'): <prefix>metrics_<split>.csv."""
     out_dir = metrics_dir(predictions_base_dir, data_split)
     os.makedirs(out_dir, exist_ok=True)
     path = os.path.join(out_dir, '%smetrics_%s.csv' % (prefix, data_split))
@@ -375,6 +376,18 @@ def save_surface_stats(predictions_base_dir, data_split, global_step, names, sur
     step is right-justified to 8, the other fields to 22; counts as integers, means and stds as '{:.5f}'.  Returns the
     path."""
     return _save_prefixed_stats('surface_', predictions_base_dir, data_split, global_step, names, surface_stats)
+
+
+def save_shape_stats(predictions_base_dir, data_split, global_step, names, shape_stats):
+    """Appends one line per call to <predictions_base_dir>/metrics/<split>/shape_metrics_<split>.csv, in the format of
+    save_scene_stats: the step, then count, mean and std of every metric of `names` (distance_metrics.shape_metric_names
+    with the prefix 'shape_', which the header leaves off).  Returns the path."""
+    return _save_prefixed_stats('shape_', predictions_base_dir, data_split, global_step, names, shape_stats)
+
+
+def save_placed_stats(predictions_base_dir, data_split, global_step, names, placed_stats):
+    """save_shape_stats for the scores in the camera frame: placed_metrics_<split>.csv, the prefix 'placed_'."""
+    return _save_prefixed_stats('placed_', predictions_base_dir, data_split, global_step, names, placed_stats)
 
 
 def kitti_label_rows(box_3d, box_2d, classes, score_threshold, image_boxes=None, keep=None):

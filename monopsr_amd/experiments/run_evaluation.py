@@ -17,6 +17,11 @@ metrics/<split>/breakdown_<split>.csv.
 With --ap-slices KITTI AP is also computed per IoU set (--ap-ious, default both) and depth bin (--ap-depth-edges, default
 10 .. 50 m) in one pass over the same frames: kitti_reports/<split>/<step>_slices.txt and, in long format,
 metrics/<split>/ap_slices_<split>.csv.
+With --shape-metrics every predicted instance map is also scored against the ground-truth map over the valid points
+only (accuracy, completeness, Chamfer-L1, squared Chamfer and Hausdorff in metres, precision / recall / F-score at
+--shape-thresholds, default 0.05 0.1 0.2 m): one line per metric and checkpoint after the report and
+metrics/<split>/shape_metrics_<split>.csv; with --shape-placed the same in the camera frame, the maps placed with the
+predicted (or, with --fit-centroids, fitted) centroid: placed_metrics_<split>.csv.
 """
 import argparse
 import sys
@@ -49,17 +54,20 @@ def build_parser():
                     help='--fit-centroids: fit the viewing angle as well')
     evaluator.add_breakdown_arguments(ap)
     evaluator.add_ap_slices_arguments(ap)
+    evaluator.add_shape_metrics_arguments(ap)
     return ap
 
 
 def format_result(result):
     """The report of one checkpoint and a line of its four statistics per metric (the scene metrics and then the
-    surface metrics, where the result has them, in their own order after the others)."""
+    surface metrics and then the shape and placed metrics, where the result has them, in their own order after the
+    others)."""
     lines = [result['report'] or '']
     for name, st in sorted(result.get('metric_stats', {}).items()):
         lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
             name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
-    for name, st in list(result.get('scene_stats', {}).items()) + list(result.get('surface_stats', {}).items()):
+    for name, st in (list(result.get('scene_stats', {}).items()) + list(result.get('surface_stats', {}).items()) +
+                     list(result.get('shape_stats', {}).items()) + list(result.get('placed_stats', {}).items())):
         lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
             name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
     for name, st in result.get('breakdown', {}).get('all', {}).get('object', {}).items():
@@ -79,6 +87,7 @@ def main(argv=None):
     centroid_fit = evaluator.centroid_fit_options(ap, args)
     breakdown = evaluator.breakdown_options(ap, args)
     ap_slices = evaluator.ap_slices_options(ap, args)
+    shape_metrics = evaluator.shape_metrics_options(ap, args)
     from monopsr_amd.core import config_utils
     from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
     from monopsr_amd.datasets.kitti.kitti_dataset import KittiDataset
@@ -92,7 +101,8 @@ def main(argv=None):
     ev = evaluator.Evaluator(model, dataset, score_threshold=threshold, predictions_base_dir=args.predictions_dir,
                              iou='low' if args.low_iou else 'standard', metric_stats=True,
                              scene_metrics='surface' if args.surface_metrics else args.scene_metrics,
-                             centroid_fit=centroid_fit, breakdown=breakdown, ap_slices=ap_slices)
+                             centroid_fit=centroid_fit, breakdown=breakdown, ap_slices=ap_slices,
+                             shape_metrics=shape_metrics)
     if args.repeat:
         max_iterations = getattr(train_config, 'max_iterations', None)
         if max_iterations is None and args.max_idle is None:
