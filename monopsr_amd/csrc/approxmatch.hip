@@ -1426,12 +1426,8 @@ extern "C" int mpsr_approx_match_ex(int b, int n, int m, const float *xyz1, cons
                 float *state = match + (block - S);  // cloud 0's state; cloud c's is c * block words further
                 if (int rc = run_passes<false>(b, n, m, xyz1, xyz2, state, L, s, block)) return rc;
                 if (int rc = launch_emit<false>(grid, s, n, m, xyz1, xyz2, state, match, block, row0)) return rc;
-                MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(emd_emit_tail_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(emd_emit_tail_kernel, dim3(b), dim3(256), lds, s, n, m, xyz1, xyz2, (void *)state,
-                                   match, block, row0);
-                MPSR_CHECK_LAUNCH("emd_emit_tail_kernel");
-                return MPSR_OK;
+                return mpsr::launch_dynamic_lds("emd_emit_tail_kernel", emd_emit_tail_kernel, dim3(b), dim3(256), lds, s, n, m,
+                                                xyz1, xyz2, (void *)state, match, block, row0);
             }
         }
     }

@@ -41,6 +41,19 @@ inline hipStream_t as_stream(mpsr_stream_t s) { return reinterpret_cast<hipStrea
         if (!(cond)) return ::mpsr::fail(MPSR_ERR_INVALID_ARG, __VA_ARGS__);       \
     } while (0)
 
+// Launch of a kernel whose dynamic LDS exceeds the default limit: raises the kernel's limit (on every call: the attribute
+// belongs to the current device; cheap and idempotent), launches, checks the launch.  `what` names the kernel in errors.
+template <typename... P, typename... A>
+inline int launch_dynamic_lds(const char *what, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s,
+                              const A &...args)
+{
+    MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds_bytes));
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, args...);
+    MPSR_CHECK_LAUNCH(what);
+    return MPSR_OK;
+}
+
 // sets the per-call overrides (t_call_math / t_call_wino_policy, internal.h) for one entry-point call (0 = inherit,
 // otherwise enum value + 1)
 struct CallOptsGuard {

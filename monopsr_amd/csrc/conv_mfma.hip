@@ -1123,10 +1123,11 @@ int conv2d_winograd_choice(int B, int H, int W, int C, int N, int KH, int KW, in
     return 0;
 }
 
-// Shared by the network-level entry points (network.hip).
+// Shared by the network-level entry points (network.hip).  `ex` (internal.h): its filter-cache slot reaches the three
+// Winograd branches, its tail job the pointwise branch; every other branch ignores it.
 int conv2d(const float *x, int B, int H, int W, int C, const float *w, const float *bias, const float *residual,
            float *y, int N, int KH, int KW, int dilation, int relu, int split_k, float *ws, size_t ws_floats,
-           hipStream_t stream)
+           hipStream_t stream, LayerExtras *ex)
 {
     MPSR_REQUIRE(B >= 0 && H > 0 && W > 0 && C > 0 && N > 0, "conv2d: bad shape (B=%d H=%d W=%d C=%d N=%d)", B, H, W,
                  C, N);
@@ -1154,17 +1155,17 @@ int conv2d(const float *x, int B, int H, int W, int C, const float *w, const flo
     // Winograd F(3x3,3x3) tile with an all-zero halo -- 25 products where the border-class implicit GEMM executes 49
     // (winograd3.hip).  fp32 mode only (the bf16x3 implicit GEMM is faster than fp32 Winograd there).
     if (!residual && conv2d_takes_winograd3(B, H, W, C, N, KH, KW, dilation, split_k, ws, ws_floats))
-        return conv3x3_winograd3(x, B, H, W, C, w, bias, relu, y, N, dilation, ws, ws_floats, stream);
+        return conv3x3_winograd3(x, B, H, W, C, w, bias, relu, y, N, dilation, ws, ws_floats, stream, nullptr, ex);
     // the big dense 3x3 layers (map decoder) go to a Winograd kernel when the caller leaves the schedule to the
     // library: F(4x4,3x3) (winograd4.hip, 4x fewer multiply-adds) where the map divides into 4x4 blocks, else
     // F(2x2,3x3) (winograd.hip, 2.25x fewer)
     {
         const int wc = conv2d_winograd_choice(B, H, W, C, N, KH, KW, dilation, residual != nullptr, split_k, ws, ws_floats);
-        if (wc == 2) return conv3x3_winograd4(x, B, H, W, C, w, bias, relu, y, N, ws, ws_floats, stream, 0, 0, nullptr, 0);
-        if (wc == 1) return conv3x3_winograd(x, B, H, W, C, w, bias, relu, y, N, ws, ws_floats, stream, dilation);
+        if (wc == 2) return conv3x3_winograd4(x, B, H, W, C, w, bias, relu, y, N, ws, ws_floats, stream, 0, 0, nullptr, 0, ex);
+        if (wc == 1) return conv3x3_winograd(x, B, H, W, C, w, bias, relu, y, N, ws, ws_floats, stream, dilation, ex);
     }
     if (conv2d_takes_pointwise(M64, C, N, KH, KW, split_k))
-        return conv1x1_pointwise(x, M64, C, w, bias, residual, relu, y, N, stream);
+        return conv1x1_pointwise(x, M64, C, w, bias, residual, relu, y, N, stream, ex);
     if (conv2d_takes_fc_rows(H, W, M64, C, N, KH, KW, split_k))
         return fc_rows(x, M64, C, w, bias, residual, relu, y, N, stream);
     // ... and with a K too long for that kernel's single workgroup per tile (img_fc, K = 18432) at few rows: its K-split form

@@ -609,28 +609,16 @@ int conv3x3_narrow(const float *x, int B, int H, int W, int C, const float *w, c
         const long long xb = (long long)B * H * W * C * 4;
         if (conv3x3_narrow_takes_mfma(x, B, H, W, C, N, w)) {
             const dim3 grid(ceil_div(H, kNarrowRows), B);
-#define MPSR_NARROW(KB_)                                                                                              \
-    if (in_c8) {                                                                                                      \
-        MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_narrow_mfma_kernel<KB_, true>),       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                     \
-        hipLaunchKernelGGL((conv3x3_narrow_mfma_kernel<KB_, true>), grid, dim3(256), lds, s, x, H, W, w, bias, relu,   \
-                           N, y, (unsigned)xb);                                                                        \
-    } else {                                                                                                          \
-        MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_narrow_mfma_kernel<KB_, false>),      \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                     \
-        hipLaunchKernelGGL((conv3x3_narrow_mfma_kernel<KB_, false>), grid, dim3(256), lds, s, x, H, W, w, bias, relu,  \
-                           N, y, (unsigned)xb);                                                                        \
-    }
+            decltype(&conv3x3_narrow_mfma_kernel<4, true>) kern = nullptr;
             switch (C / 8) {
-                case 4: MPSR_NARROW(4); break;
-                case 8: MPSR_NARROW(8); break;
-                case 12: MPSR_NARROW(12); break;
-                case 16: MPSR_NARROW(16); break;
+                case 4: kern = in_c8 ? conv3x3_narrow_mfma_kernel<4, true> : conv3x3_narrow_mfma_kernel<4, false>; break;
+                case 8: kern = in_c8 ? conv3x3_narrow_mfma_kernel<8, true> : conv3x3_narrow_mfma_kernel<8, false>; break;
+                case 12: kern = in_c8 ? conv3x3_narrow_mfma_kernel<12, true> : conv3x3_narrow_mfma_kernel<12, false>; break;
+                case 16: kern = in_c8 ? conv3x3_narrow_mfma_kernel<16, true> : conv3x3_narrow_mfma_kernel<16, false>; break;
                 default: goto direct;
             }
-#undef MPSR_NARROW
-            MPSR_CHECK_LAUNCH("conv3x3_narrow_mfma_kernel");
-            return MPSR_OK;
+            return launch_dynamic_lds("conv3x3_narrow_mfma_kernel", kern, grid, dim3(256), lds, s, x, H, W, w, bias, relu, N, y,
+                                      (unsigned)xb);
         }
     }
 direct:

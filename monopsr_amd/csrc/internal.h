@@ -22,10 +22,75 @@ char *error_buffer();
 extern thread_local int t_call_math;
 extern thread_local int t_call_wino_policy;
 
+// ---- per-layer arguments of the convolution launchers
+// What a network-level entry point (network.hip) knows about one layer beyond its tensors, passed down through conv2d()
+// as `LayerExtras *` (nullptr: nothing): a launcher without the argument, or a caller that passes none, sees none of it.
+//
+// A filter-transform job that a 1x1 layer's launch carries behind its own tiles (wino3_filter.h): the filters of the
+// 3x3 layer that follows.
+struct FilterTailJob {
+    const float *w = nullptr;  // nullptr: no job
+    float *u = nullptr;
+    int N = 0, C = 0;
+    int form = 0;  // 0: F(3x3,3x3), 25 positions (wino3_filter_one); 1: the sixteen-product form (wino3z_filter_one)
+};
+// The slice of the caller's filter cache (mpsr_net_opts.filter_cache) that belongs to a 3x3 layer: the Winograd launchers
+// and conv3x3_upsampled then keep the transformed filters in `u` instead of their scratch and skip the transform when the
+// slice already holds them.
+struct FilterCacheSlot {
+    const float *w = nullptr;
+    float *u = nullptr;  // nullptr: no slice
+    size_t floats = 0;
+    bool ready = false;  // the caller vouches for the slices (mpsr_net_opts.filter_cache_valid)
+    int *tag = nullptr;  // caller's note of what the slice holds (mpsr_net_opts.filter_cache_tags), or nullptr
+    // true when the slice already holds form `kind` of this layer's filters; notes `kind` for the next call either way
+    // (the consumer is about to write it if not)
+    bool holds(int kind) const
+    {
+        const bool ok = ready && (!tag || *tag == kind);
+        if (tag) *tag = kind;
+        return ok;
+    }
+};
+enum { FILTER_FORM_WINO4 = 1, FILTER_FORM_WINO3 = 2, FILTER_FORM_UPCONV = 3, FILTER_FORM_WINO3Z = 4, FILTER_FORM_WINO2 = 5 };
+struct LayerExtras {
+    // 3x3 layers (conv2d()'s three Winograd branches, conv3x3_upsampled)
+    FilterCacheSlot cache;
+    const float *filters_at = nullptr;  // an earlier launch's tail job already wrote the form this call reads there
+    // 1x1 layers (conv2d()'s conv1x1_pointwise branch)
+    FilterTailJob tail;       // in: a job to append to this launch
+    bool tail_taken = false;  // out: the launch carried it
+};
+// Where a 3x3 layer's transformed filters live: `need` floats of form `form` (FILTER_FORM_*) of the filters `w`.
+//   u:     the cache slice if `ex` offers one for `w` that is large enough (its tag then notes `form`), else `ws`
+//   ready: `u` already holds them -- a slice the caller vouches for, tagged `form`, or the address a tail job wrote
+//   rest:  what is left of `ws` for other scratch: behind the filters when they live there, else all of it
+// (whether `ws` itself holds `need` floats is the caller's check)
+struct FilterPlace {
+    float *u;
+    bool ready;
+    float *rest;
+    size_t rest_floats;
+};
+inline FilterPlace place_filters(const LayerExtras *ex, const float *w, size_t need, int form, float *ws, size_t ws_floats)
+{
+    FilterPlace f{ws, false, ws, ws_floats};
+    if (ex && ex->cache.w == w && ex->cache.u && ex->cache.floats >= need) {
+        f.u = ex->cache.u;
+        f.ready = ex->cache.holds(form);
+    } else {
+        const size_t off = (need + 63) / 64 * 64;
+        f.rest = ws ? ws + off : nullptr;
+        f.rest_floats = ws && ws_floats > off ? ws_floats - off : 0;
+    }
+    if (ex && ex->filters_at && ex->filters_at == f.u) f.ready = true;
+    return f;
+}
+
 // ---- conv_mfma.hip
 int conv2d(const float *x, int B, int H, int W, int C, const float *w, const float *bias, const float *residual,
            float *y, int N, int KH, int KW, int dilation, int relu, int split_k, float *ws, size_t ws_floats,
-           hipStream_t stream);
+           hipStream_t stream, LayerExtras *ex = nullptr);
 size_t conv_scratch_floats(long long M, int N);
 bool conv2d_takes_winograd4(int B, int H, int W, int C, int N, const float *ws, size_t ws_floats);
 bool conv2d_takes_winograd3(int B, int H, int W, int C, int N, int KH, int KW, int dilation, int split_k, const float *ws,
@@ -46,7 +111,7 @@ size_t winograd_scratch_floats(int C, int N);
 bool winograd_applies(int H, int W, int C, int N);
 bool winograd_applies_dilated(int H, int W, int C, int N, int dilation);
 int conv3x3_winograd(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu, float *y,
-                     int N, float *ws, size_t ws_floats, hipStream_t s, int dilation);
+                     int N, float *ws, size_t ws_floats, hipStream_t s, int dilation, LayerExtras *ex = nullptr);
 extern std::atomic<int> g_wino_waves;  // mpsr_debug_set_wino_waves
 
 // ---- winograd4.hip
@@ -54,7 +119,7 @@ size_t winograd4_scratch_floats(int C, int N);
 bool winograd4_applies(int H, int W, int C, int N);
 int conv3x3_winograd4(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu,
                       float *y, int N, float *ws, size_t ws_floats, hipStream_t s, int in_c8, int out_c8, float *part,
-                      size_t part_floats);
+                      size_t part_floats, LayerExtras *ex = nullptr);
 size_t winograd4_split_floats(int B, int H, int W, int N);
 extern std::atomic<int> g_wino4_split;  // mpsr_debug_set_wino4_split
 
@@ -66,37 +131,7 @@ int winograd3_form(int B, int H, int W, int C, int N, int dilation);
 int winograd3_filter_form(int B, int H, int W, int C, int N, int dilation);
 int conv3x3_winograd3(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu,
                       float *y, int N, int dilation, float *ws, size_t ws_floats, hipStream_t s,
-                      const float *mask = nullptr);
-// A filter-transform job handed from a network-level entry point (network.hip) to the next pointwise launch on this
-// thread, and the note that it was done, for conv3x3_winograd3 to find.
-struct FilterTailJob {
-    const float *w = nullptr;
-    float *u = nullptr;
-    int N = 0, C = 0;
-    int form = 0;  // 0: F(3x3,3x3), 25 positions (wino3_filter_one); 1: the sixteen-product form (wino3z_filter_one)
-};
-extern thread_local FilterTailJob g_filter_tail_job;    // pending: consumed by conv1x1_pointwise
-extern thread_local FilterTailJob g_filter_tail_done;   // done by the last pointwise launch: consumed by conv3x3_winograd3
-// Where the transformed filters of the layer about to run live when the caller keeps them across calls
-// (mpsr_net_opts.filter_cache): set by the network entry points (network.hip) right before the layer, consumed by
-// conv3x3_winograd3 / conv3x3_winograd4, which then use `u` instead of their scratch and skip the transform if `ready`.
-struct FilterCacheSlot {
-    const float *w = nullptr;
-    float *u = nullptr;
-    size_t floats = 0;
-    bool ready = false;
-    int *tag = nullptr;  // caller's note of what the slice holds (mpsr_net_opts.filter_cache_tags), or nullptr
-    // true when the slice already holds form `kind` of this layer's filters; notes `kind` for the next call either way
-    // (the consumer is about to write it if not)
-    bool holds(int kind)
-    {
-        const bool ok = ready && (!tag || *tag == kind);
-        if (tag) *tag = kind;
-        return ok;
-    }
-};
-enum { FILTER_FORM_WINO4 = 1, FILTER_FORM_WINO3 = 2, FILTER_FORM_UPCONV = 3, FILTER_FORM_WINO3Z = 4, FILTER_FORM_WINO2 = 5 };
-extern thread_local FilterCacheSlot g_filter_cache_slot;
+                      const float *mask = nullptr, LayerExtras *ex = nullptr);
 
 // ---- winograd3w.hip: the layer of winograd3.hip with one wave owning all 25 positions of its tile block
 bool winograd3w_applies(int B, int H, int W, int C, int N, int dilation);
@@ -133,7 +168,7 @@ bool pointwise_applies(long long M, int K, int N);
 bool pointwise_masked_applies(long long M, int K, int N);
 int pointwise_override();
 int conv1x1_pointwise(const float *x, long long M, int K, const float *w, const float *bias, const float *residual,
-                      int relu, float *y, int N, hipStream_t s);
+                      int relu, float *y, int N, hipStream_t s, LayerExtras *ex = nullptr);
 int conv1x1_pointwise_masked(const float *x, long long M, int K, const float *w, const float *bias, const float *residual,
                              const unsigned *mask, float *y, int N, hipStream_t s);
 int conv1x1_pointwise_emit(const float *x, long long M, int K, const float *w, const float *bias, const float *residual,
@@ -164,6 +199,6 @@ size_t upconv_z_floats(long long Msrc, int N);
 size_t upconv_weight_floats(int C, int N);
 int conv3x3_upsampled(const float *x, int B, int h, int w, int C, int OH, int OW, int align_corners, const float *g,
                       const float *bias, int relu, float *y, int N, int out_c8, float *z, size_t z_floats, float *ws,
-                      size_t ws_floats, hipStream_t s);
+                      size_t ws_floats, hipStream_t s, LayerExtras *ex = nullptr);
 
 }  // namespace mpsr

@@ -40,10 +40,10 @@ struct Arena {
 inline size_t fbytes(size_t n) { return mpsr::align_up(n * sizeof(float), 256); }
 
 int run_layer(const float *blob, const mpsr_layer &L, const float *x, int B, int H, int W, const float *residual,
-              float *y, int split_k, float *ws, size_t ws_floats, hipStream_t s)
+              float *y, int split_k, float *ws, size_t ws_floats, hipStream_t s, mpsr::LayerExtras *ex = nullptr)
 {
     return mpsr::conv2d(x, B, H, W, L.cin, blob + L.w_off, L.b_off >= 0 ? blob + L.b_off : nullptr, residual, y, L.cout,
-                        L.kh, L.kw, L.dilation, L.relu, split_k, ws, ws_floats, s);
+                        L.kh, L.kw, L.dilation, L.relu, split_k, ws, ws_floats, s, ex);
 }
 
 constexpr int kTrunkUnits[3] = {3, 4, 23};
@@ -56,7 +56,7 @@ inline size_t cache_floats_of(const mpsr_layer &L)
 }
 
 // Walks the caller's filter cache (mpsr_net_opts) layer by layer in execution order: every 3x3 layer owns a fixed slice,
-// offered to the Winograd entry points through g_filter_cache_slot right before the layer runs.
+// passed to the layer's launcher as the slot of its LayerExtras.
 struct FilterCache {
     float *base = nullptr;
     size_t floats = 0, used = 0;
@@ -80,16 +80,18 @@ struct FilterCache {
         used += need;
         return r;
     }
-    void offer(const float *w, float *slice, const mpsr_layer &L, int layer_index) const
+    // the extras of layer L (filters `w`, record `layer_index`) with its slice from take(), or none
+    mpsr::LayerExtras offer(const float *w, float *slice, const mpsr_layer &L, int layer_index) const
     {
-        mpsr::g_filter_cache_slot = mpsr::FilterCacheSlot();
+        mpsr::LayerExtras ex;
         if (slice) {
-            mpsr::g_filter_cache_slot.w = w;
-            mpsr::g_filter_cache_slot.u = slice;
-            mpsr::g_filter_cache_slot.floats = cache_floats_of(L);
-            mpsr::g_filter_cache_slot.ready = valid;
-            mpsr::g_filter_cache_slot.tag = tags ? tags + layer_index : nullptr;
+            ex.cache.w = w;
+            ex.cache.u = slice;
+            ex.cache.floats = cache_floats_of(L);
+            ex.cache.ready = valid;
+            ex.cache.tag = tags ? tags + layer_index : nullptr;
         }
+        return ex;
     }
 };
 
@@ -175,14 +177,6 @@ extern "C" int mpsr_trunk_fwd_ex(const float *img, int B, int H, int W, const fl
                           workspace_bytes);
 
     int rc;
-    struct TailJobGuard {  // no filter-transform job (wino3_filter.h) outlives this call, whichever way it returns
-        ~TailJobGuard()
-        {
-            mpsr::g_filter_tail_job = mpsr::FilterTailJob();
-            mpsr::g_filter_tail_done = mpsr::FilterTailJob();
-            mpsr::g_filter_cache_slot = mpsr::FilterCacheSlot();
-        }
-    } tail_job_guard;
     FilterCache cache(opts);
     if ((rc = mpsr_im2col_root(img, B, H, W, cols, root.cin, stream))) return rc;
     if ((rc = run_layer(blob, root, cols, B, d.OH, d.OW, nullptr, rootout, 0, sk, skn, s))) return rc;
@@ -214,21 +208,21 @@ extern "C" int mpsr_trunk_fwd_ex(const float *img, int B, int H, int W, const fl
             const int c2i = (int)(&c2 - layers);
             const int fform = mpsr::winograd3_filter_form(B, d.PH, d.PW, c2.cin, c2.cout, c2.dilation);
             const bool cached_u = uslice && cache.valid && (!cache.tags || cache.tags[c2i] == fform);
+            mpsr::LayerExtras ex1, ex2 = cache.offer(blob + c2.w_off, uslice, c2, c2i);
             if (!cached_u &&
                 mpsr::conv2d_takes_pointwise((long long)B * d.PH * d.PW, c1.cin, c1.cout, 1, 1, 0) &&
                 mpsr::conv2d_takes_winograd3(B, d.PH, d.PW, c2.cin, c2.cout, c2.kh, c2.kw, c2.dilation, 0, sk, skn)) {
-                mpsr::g_filter_tail_job.w = blob + c2.w_off;
-                mpsr::g_filter_tail_job.u = uslice ? uslice : sk;
-                mpsr::g_filter_tail_job.N = c2.cout;
-                mpsr::g_filter_tail_job.C = c2.cin;
-                mpsr::g_filter_tail_job.form = fform == mpsr::FILTER_FORM_WINO3Z ? 1 : 0;
+                ex1.tail.w = blob + c2.w_off;
+                ex1.tail.u = uslice ? uslice : sk;
+                ex1.tail.N = c2.cout;
+                ex1.tail.C = c2.cin;
+                ex1.tail.form = fform == mpsr::FILTER_FORM_WINO3Z ? 1 : 0;
             }
-            if ((rc = run_layer(blob, c1, cur, B, d.PH, d.PW, nullptr, t1, 0, sk, skn, s))) return rc;
-            mpsr::g_filter_tail_job = mpsr::FilterTailJob();  // (not taken: conv2 transforms its filters itself)
-            cache.offer(blob + c2.w_off, uslice, c2, c2i);
-            rc = run_layer(blob, c2, t1, B, d.PH, d.PW, nullptr, t2, 0, sk, skn, s);
-            mpsr::g_filter_cache_slot = mpsr::FilterCacheSlot();
-            if (rc) return rc;
+            if ((rc = run_layer(blob, c1, cur, B, d.PH, d.PW, nullptr, t1, 0, sk, skn, s, &ex1))) return rc;
+            // (conv2 takes the job's word only where that is the address it reads: a slice too small for the layer
+            // sends it back to `sk`, where it transforms the filters itself)
+            if (ex1.tail_taken) ex2.filters_at = ex1.tail.u;
+            if ((rc = run_layer(blob, c2, t1, B, d.PH, d.PW, nullptr, t2, 0, sk, skn, s, &ex2))) return rc;
             if ((rc = run_layer(blob, c3, t2, B, d.PH, d.PW, residual, dst, 0, sk, skn, s))) return rc;
             cur = dst;
             cur_c = c3.cout;
@@ -388,9 +382,6 @@ extern "C" int mpsr_squash_decoder_fwd_ex(const float *crop_feat, const float *f
     if ((rc = mpsr_max_pool(sq, B, fh, fw, csq, 2, 2, 0, feat_box3d, stream))) return rc;
     // features_for_box_3d is complete: the caller's FC heads may start on another stream
     if (opts && opts->ready_event) MPSR_CHECK_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(opts->ready_event), s));
-    struct SlotGuard {
-        ~SlotGuard() { mpsr::g_filter_cache_slot = mpsr::FilterCacheSlot(); }
-    } slot_guard;
     FilterCache cache(opts);
     // Channel-blocked internal tensors ([C/8][H][W][8], "C8") when all four 3x3 layers run on the F(4x4,3x3) kernel: a
     // K step of that kernel then reads whole 128-byte lines instead of 32 bytes of every pixel's line (NHWC re-fetched
@@ -401,16 +392,16 @@ extern "C" int mpsr_squash_decoder_fwd_ex(const float *crop_feat, const float *f
     const bool xyz_c8 = ch.xyz_c8, up1 = ch.up1, up2 = ch.up2, c8 = ch.c8;
     if (c8) {
         auto wino = [&](const mpsr_layer &Lr, const float *x, int H, int W, float *y, int in_c8, int out_c8) {
-            cache.offer(blob + Lr.w_off, cache.take(Lr), Lr, (int)(&Lr - L));
+            mpsr::LayerExtras ex = cache.offer(blob + Lr.w_off, cache.take(Lr), Lr, (int)(&Lr - L));
             return mpsr::conv3x3_winograd4(x, B, H, W, Lr.cin, blob + Lr.w_off, Lr.b_off >= 0 ? blob + Lr.b_off : nullptr,
-                                           Lr.relu, y, Lr.cout, sk, skn, s, in_c8, out_c8, partb, partn);
+                                           Lr.relu, y, Lr.cout, sk, skn, s, in_c8, out_c8, partb, partn, &ex);
         };
         // upsampling + 3x3 convolution in one: x (NHWC, source size) -> y (channel-blocked, output size); z = r1 / r2
         auto upconv = [&](const mpsr_layer &Lr, const float *x, int h, int w, int H, int W, float *y, float *z, size_t zn) {
-            cache.offer(blob + Lr.w_off, cache.take(Lr), Lr, (int)(&Lr - L));
+            mpsr::LayerExtras ex = cache.offer(blob + Lr.w_off, cache.take(Lr), Lr, (int)(&Lr - L));
             return mpsr::conv3x3_upsampled(x, B, h, w, Lr.cin, H, W, 1, blob + Lr.w_off,
                                            Lr.b_off >= 0 ? blob + Lr.b_off : nullptr, Lr.relu, y, Lr.cout, 1, z, zn, sk,
-                                           skn, s);
+                                           skn, s, &ex);
         };
         if (up1) {
             if ((rc = upconv(L[2], sq, fh, fw, hh, hw, a, r1, r1n))) return rc;
@@ -439,13 +430,14 @@ extern "C" int mpsr_squash_decoder_fwd_ex(const float *crop_feat, const float *f
     // NHWC chain (small batches, maps that do not divide into 4x4 blocks, MPSR_WINOGRAD_OFF, the bf16x3 mode): conv2d
     // per layer; the two upsampled convolutions keep their tap GEMM + gather (NHWC output) where it applies
     auto cached = [&](const mpsr_layer &Lr, const float *x, int H, int W, float *y) {
-        cache.offer(blob + Lr.w_off, cache.take(Lr), Lr, (int)(&Lr - L));
-        return run_layer(blob, Lr, x, B, H, W, nullptr, y, 0, sk, skn, s);
+        mpsr::LayerExtras ex = cache.offer(blob + Lr.w_off, cache.take(Lr), Lr, (int)(&Lr - L));
+        return run_layer(blob, Lr, x, B, H, W, nullptr, y, 0, sk, skn, s, &ex);
     };
     auto upconv_nhwc = [&](const mpsr_layer &Lr, const float *x, int h, int w, int H, int W, float *y, float *z, size_t zn) {
-        cache.offer(blob + Lr.w_off, cache.take(Lr), Lr, (int)(&Lr - L));
+        mpsr::LayerExtras ex = cache.offer(blob + Lr.w_off, cache.take(Lr), Lr, (int)(&Lr - L));
         return mpsr::conv3x3_upsampled(x, B, h, w, Lr.cin, H, W, 1, blob + Lr.w_off,
-                                       Lr.b_off >= 0 ? blob + Lr.b_off : nullptr, Lr.relu, y, Lr.cout, 0, z, zn, sk, skn, s);
+                                       Lr.b_off >= 0 ? blob + Lr.b_off : nullptr, Lr.relu, y, Lr.cout, 0, z, zn, sk, skn, s,
+                                       &ex);
     };
     if (up1) {
         if ((rc = upconv_nhwc(L[2], sq, fh, fw, hh, hw, a, r1, r1n))) return rc;

@@ -552,13 +552,13 @@ bool pointwise_masked_applies(long long M, int K, int N)
 }
 
 static int pointwise_launch(const float *x, long long M, int K, const float *w, const float *bias, const float *residual,
-                            int relu, const unsigned *mask, unsigned *emit, float *y, int N, hipStream_t s);
+                            int relu, const unsigned *mask, unsigned *emit, float *y, int N, hipStream_t s, LayerExtras *ex);
 
 int conv1x1_pointwise(const float *x, long long M, int K, const float *w, const float *bias,
-                             const float *residual, int relu, float *y, int N, hipStream_t s)
+                             const float *residual, int relu, float *y, int N, hipStream_t s, LayerExtras *ex)
 {
     MPSR_REQUIRE(pointwise_applies(M, K, N), "conv1x1_pointwise: unsupported shape (M=%lld K=%d N=%d)", M, K, N);
-    return pointwise_launch(x, M, K, w, bias, residual, relu, nullptr, nullptr, y, N, s);
+    return pointwise_launch(x, M, K, w, bias, residual, relu, nullptr, nullptr, y, N, s, ex);
 }
 
 // conv1x1_pointwise that also writes the ReLU bit mask of its result (bits of rows >= M unspecified)
@@ -567,7 +567,7 @@ int conv1x1_pointwise_emit(const float *x, long long M, int K, const float *w, c
 {
     MPSR_REQUIRE(pointwise_masked_applies(M, K, N), "conv1x1_pointwise_emit: unsupported shape (M=%lld K=%d N=%d)", M, K, N);
     MPSR_REQUIRE(bits, "conv1x1_pointwise_emit: null mask");
-    return pointwise_launch(x, M, K, w, bias, residual, relu, nullptr, bits, y, N, s);
+    return pointwise_launch(x, M, K, w, bias, residual, relu, nullptr, bits, y, N, s, nullptr);
 }
 
 // y[m][n] = keep(m, n) ? sum_k x[m][k] w[n][k] + bias[n] + residual[m][n] : 0, keep = bit (m & 31) of
@@ -577,11 +577,11 @@ int conv1x1_pointwise_masked(const float *x, long long M, int K, const float *w,
 {
     MPSR_REQUIRE(pointwise_masked_applies(M, K, N), "conv1x1_pointwise_masked: unsupported shape (M=%lld K=%d N=%d)", M, K, N);
     MPSR_REQUIRE(mask, "conv1x1_pointwise_masked: null mask");
-    return pointwise_launch(x, M, K, w, bias, residual, 0, mask, nullptr, y, N, s);
+    return pointwise_launch(x, M, K, w, bias, residual, 0, mask, nullptr, y, N, s, nullptr);
 }
 
 static int pointwise_launch(const float *x, long long M, int K, const float *w, const float *bias, const float *residual,
-                            int relu, const unsigned *mask, unsigned *emit, float *y, int N, hipStream_t s)
+                            int relu, const unsigned *mask, unsigned *emit, float *y, int N, hipStream_t s, LayerExtras *ex)
 {
     using namespace pws;
     PwsParams p;
@@ -611,36 +611,17 @@ static int pointwise_launch(const float *x, long long M, int K, const float *w, 
     int grid = g_pws_per_cu.load() * cus / unit * unit;
     if (grid < unit) grid = unit;
     if (grid > p.ntiles) grid = p.ntiles;
-    // a pending filter-transform job rides on this launch
-    p.fw = g_filter_tail_job.w; p.fu = g_filter_tail_job.u; p.fN = g_filter_tail_job.N; p.fC = g_filter_tail_job.C;
-    p.fform = g_filter_tail_job.form;
-    if (p.fw) g_filter_tail_done = g_filter_tail_job;
-    g_filter_tail_job = FilterTailJob();
-    const size_t lds_bytes = (size_t)LDS_B;
-#define MPSR_PW(...)                                                                                                  \
-    do {                                                                                                              \
-        MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pw_conv_kernel<__VA_ARGS__>),               \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));              \
-        hipLaunchKernelGGL((pw_conv_kernel<__VA_ARGS__>), dim3(grid), dim3(256), lds_bytes, s, p);                    \
-    } while (0)
-    if (mask || emit) {
-        if (mask && residual) MPSR_PW(true, true, true);
-        else if (mask) MPSR_PW(false, true, true);
-        else if (residual) MPSR_PW(true, true, false, true);
-        else MPSR_PW(false, true, false, true);
-        MPSR_CHECK_LAUNCH("pw_conv_kernel");
-        return MPSR_OK;
-    }
-    if (K / KS >= 8) {
-        if (residual) MPSR_PW(true, true);
-        else MPSR_PW(false, true);
-    } else {
-        if (residual) MPSR_PW(true, false);
-        else MPSR_PW(false, false);
-    }
-#undef MPSR_PW
-    MPSR_CHECK_LAUNCH("pw_conv_kernel");
-    return MPSR_OK;
+    // the caller's filter-transform job rides on this launch
+    const FilterTailJob job = ex ? ex->tail : FilterTailJob();
+    p.fw = job.w; p.fu = job.u; p.fN = job.N; p.fC = job.C; p.fform = job.form;
+    if (ex) ex->tail_taken = job.w != nullptr;
+    // instantiation <RES, LONG, MASK, EMIT>: masked and emitting launches are LONG ones
+    const int pick = (residual ? 1 : 0) | (mask ? 4 : emit ? 6 : K / KS >= 8 ? 2 : 0);
+    void (*const kernels[8])(const PwsParams) = {
+        pw_conv_kernel<false, false>, pw_conv_kernel<true, false>, pw_conv_kernel<false, true>, pw_conv_kernel<true, true>,
+        pw_conv_kernel<false, true, true>, pw_conv_kernel<true, true, true>,
+        pw_conv_kernel<false, true, false, true>, pw_conv_kernel<true, true, false, true>};
+    return launch_dynamic_lds("pw_conv_kernel", kernels[pick], dim3(grid), dim3(256), (size_t)LDS_B, s, p);
 }
 
 

@@ -242,11 +242,7 @@ int thin_wgrad(const float *x, const float *dy, int B, int H, int W, int C, floa
     const long long units = (long long)B * p.strips;
     const int grid = (int)std::min<long long>(512, (units + nsub - 1) / nsub);
     const size_t ldsb = std::max(kWinBytes, kPartBytes);
-    MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(thin_wgrad_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
-    hipLaunchKernelGGL(thin_wgrad_kernel, dim3(grid), dim3(TWAVES * 64), ldsb, s, p);
-    MPSR_CHECK_LAUNCH("thin_wgrad_kernel");
-    return MPSR_OK;
+    return launch_dynamic_lds("thin_wgrad_kernel", thin_wgrad_kernel, dim3(grid), dim3(TWAVES * 64), ldsb, s, p);
 }
 
 bool thin_input_conv_applies(int B, int H, int W, int C, int N, int KH, int KW, int dilation)
@@ -264,11 +260,7 @@ int thin_input_conv(const float *x, int B, int H, int W, const float *w, const f
     p.strips = (H + TROWS - 1) / TROWS;
     const long long units = (long long)B * p.strips * (N >> 6);
     const int grid = (int)std::min<long long>(2048, (units + TWAVES - 1) / TWAVES);
-    MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(thin_input_conv_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWinBytes));
-    hipLaunchKernelGGL(thin_input_conv_kernel, dim3(grid), dim3(TWAVES * 64), kWinBytes, s, p);
-    MPSR_CHECK_LAUNCH("thin_input_conv_kernel");
-    return MPSR_OK;
+    return launch_dynamic_lds("thin_input_conv_kernel", thin_input_conv_kernel, dim3(grid), dim3(TWAVES * 64), kWinBytes, s, p);
 }
 
 }  // namespace mpsr

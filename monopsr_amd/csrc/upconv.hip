@@ -570,7 +570,7 @@ bool upconv_applies(int B, int h, int w, int C, int OH, int OW, int N, int align
 
 int conv3x3_upsampled(const float *x, int B, int h, int w, int C, int OH, int OW, int align_corners, const float *g,
                       const float *bias, int relu, float *y, int N, int out_c8, float *z, size_t z_floats, float *ws,
-                      size_t ws_floats, hipStream_t s)
+                      size_t ws_floats, hipStream_t s, LayerExtras *ex)
 {
     MPSR_REQUIRE(upconv_applies(B, h, w, C, OH, OW, N, align_corners), "conv3x3_upsampled: unsupported shape (B=%d %dx%dx%d -> %dx%dx%d)",
                  B, h, w, C, OH, OW, N);
@@ -578,19 +578,14 @@ int conv3x3_upsampled(const float *x, int B, int h, int w, int C, int OH, int OW
     if (!z || z_floats < upconv_z_floats(M, N))
         return fail(MPSR_ERR_WORKSPACE, "conv3x3_upsampled: z scratch holds %zu floats, needs %zu", z_floats,
                     upconv_z_floats(M, N));
-    // re-ordered filter rows: the caller's filter cache (mpsr_net_opts) if the network entry point offered a slot
-    float *wp = ws;
-    bool ready = false;
-    if (g_filter_cache_slot.w == g && g_filter_cache_slot.u && g_filter_cache_slot.floats >= upconv_weight_floats(C, N)) {
-        wp = g_filter_cache_slot.u;
-        ready = g_filter_cache_slot.holds(FILTER_FORM_UPCONV);
-    } else if (!ws || ws_floats < upconv_weight_floats(C, N)) {
-        g_filter_cache_slot = FilterCacheSlot();
+    // re-ordered filter rows: in the caller's filter cache if it has a slice for this layer, else in `ws`, which must
+    // then hold them
+    const FilterPlace f = place_filters(ex, g, upconv_weight_floats(C, N), FILTER_FORM_UPCONV, ws, ws_floats);
+    float *wp = f.u;
+    if (wp == ws && (!ws || ws_floats < upconv_weight_floats(C, N)))
         return fail(MPSR_ERR_WORKSPACE, "conv3x3_upsampled: scratch holds %zu floats, needs %zu", ws_floats,
                     upconv_weight_floats(C, N));
-    }
-    g_filter_cache_slot = FilterCacheSlot();
-    if (!ready) {
+    if (!f.ready) {
         const long long total = (long long)9 * N * (C / 4);
         hipLaunchKernelGGL(upconv_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, N, C, wp);
         MPSR_CHECK_LAUNCH("upconv_weights_kernel");
@@ -631,22 +626,10 @@ int conv3x3_upsampled(const float *x, int B, int h, int w, int C, int OH, int OW
         p.y = y + (size_t)b0 * OH * OW * N;
         p.B = nb;
         const dim3 grid((unsigned)(8 * ceil_div(nb, 8) * (N / 8)));
-#define MPSR_UPC(...)                                                                                                 \
-    do {                                                                                                              \
-        MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(upconv_gather_kernel<__VA_ARGS__>),         \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                    \
-        hipLaunchKernelGGL((upconv_gather_kernel<__VA_ARGS__>), grid, dim3(threads), lds, s, p);                      \
-    } while (0)
         const bool wide = p.stg * w > kPf * (threads / 18);
-        if (out_c8) {
-            if (wide) MPSR_UPC(true, true);
-            else MPSR_UPC(true, false);
-        } else {
-            if (wide) MPSR_UPC(false, true);
-            else MPSR_UPC(false, false);
-        }
-#undef MPSR_UPC
-        MPSR_CHECK_LAUNCH("upconv_gather_kernel");
+        const auto kern = out_c8 ? (wide ? upconv_gather_kernel<true, true> : upconv_gather_kernel<true, false>)
+                                 : (wide ? upconv_gather_kernel<false, true> : upconv_gather_kernel<false, false>);
+        if (int rc = launch_dynamic_lds("upconv_gather_kernel", kern, grid, dim3(threads), lds, s, p)) return rc;
     }
     return MPSR_OK;
 }
@@ -749,10 +732,9 @@ int conv3x3_upsampled_bwd(const float *x, const float *dy, int B, int h, int w, 
     p.rows_max = gather_t_rows(h, OH, p.hscale);
     p.cap = gather_t_cap(p.rows_max);
     const size_t lds = gather_t_lds_bytes(p.rows_max, h, w, OW);
-    MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(upconv_gather_t_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(upconv_gather_t_kernel, dim3((unsigned)(N / 32), (unsigned)B), dim3(256), lds, s, p);
-    MPSR_CHECK_LAUNCH("upconv_gather_t_kernel");
+    if (int rc = launch_dynamic_lds("upconv_gather_t_kernel", upconv_gather_t_kernel, dim3((unsigned)(N / 32), (unsigned)B),
+                                    dim3(256), lds, s, p))
+        return rc;
     // weight gradient of the tap GEMM, folded back into (N, 9 C)
     MPSR_CHECK_HIP(hipMemsetAsync(dwp, 0, (size_t)9 * N * C * sizeof(float), s));
     if (int rc = mpsr_conv2d_wgrad_f32(x, dz, B, h, w, C, 9 * N, 1, 1, 1, dwp, nullptr, reinterpret_cast<mpsr_stream_t>(s))) return rc;
@@ -819,7 +801,6 @@ extern "C" int mpsr_conv3x3_upsampled_f32(const float *x, int B, int h, int w, i
     if (ws_floats < zf + mpsr::upconv_weight_floats(C, N))
         return mpsr::fail(MPSR_ERR_WORKSPACE, "conv3x3_upsampled: scratch holds %zu floats, needs %zu", ws_floats,
                           zf + mpsr::upconv_weight_floats(C, N));
-    mpsr::g_filter_cache_slot = mpsr::FilterCacheSlot();
     return mpsr::conv3x3_upsampled(x, B, h, w, C, OH, OW, align_corners, weights, bias, relu, y, N, 0, ws, zf, ws + zf,
                                    ws_floats - zf, mpsr::as_stream(stream));
 }

@@ -1,7 +1,8 @@
 // The filter transform of the F(3x3,3x3) atrous kernel (winograd3.hip) as a device function: winograd3.hip's own
 // launch uses it, and the persistent pointwise kernel (pointwise.hip) runs it as a tail job -- the filters of the 3x3
 // layer that FOLLOWS a 1x1 layer are transformed by that layer's workgroups when they have finished their tiles,
-// instead of by a 6-us launch of their own in front of every one of block3's 23 atrous layers.
+// instead of by a 6-us launch of their own in front of every one of block3's 23 atrous layers.  The job is an argument
+// of the 1x1 layer's launch (LayerExtras::tail, internal.h), and so is the word to the 3x3 layer that it was done.
 #pragma once
 #include <hip/hip_runtime.h>
 

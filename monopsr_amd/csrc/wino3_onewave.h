@@ -333,10 +333,7 @@ inline int wino3_onewave_launch(Wino3OneKernel kern, const char *name, const Win
 {
     using namespace w3one;
     const size_t ldsb = (size_t)2 * Form::NP * MT * KC * sizeof(float);  // two A buffers
-    MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), ldsb, s, p);
-    MPSR_CHECK_LAUNCH(name);
-    return MPSR_OK;
+    return launch_dynamic_lds(name, kern, dim3((unsigned)blocks), dim3(256), ldsb, s, p);
 }
 
 }  // namespace mpsr

@@ -631,28 +631,18 @@ bool winograd_applies_dilated(int H, int W, int C, int N, int dilation)
 std::atomic<int> g_wino_waves{8};  // 4: the one-wave-per-SIMD kernel, 8: the two-waves-per-SIMD variant
 
 int conv3x3_winograd(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu, float *y,
-                     int N, float *ws, size_t ws_floats, hipStream_t s, int dilation)
+                     int N, float *ws, size_t ws_floats, hipStream_t s, int dilation, LayerExtras *ex)
 {
     MPSR_REQUIRE(winograd_applies_dilated(H, W, C, N, dilation),
                  "conv3x3_winograd: needs H, W multiples of 2 x dilation and C %% %d == 0", KC);
     if (ws_floats < winograd_scratch_floats(C, N) || !ws)
         return fail(MPSR_ERR_WORKSPACE, "conv3x3_winograd: scratch holds %zu floats, needs %zu", ws_floats,
                     winograd_scratch_floats(C, N));
-    // (per call: the attribute belongs to the current device; cheap and idempotent)
-    MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(g_wino_waves.load() == 8
-                                                                          ? reinterpret_cast<const void *>(wino_conv8_kernel<false>)
-                                                                          : reinterpret_cast<const void *>(wino_conv_kernel)),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsFloats * sizeof(float))));
-    // the caller's filter cache (mpsr_net_opts), if the network entry point offered a slot for this layer: the
-    // full-image trunk's atrous layers run here (F(2x2,3x3) on their pixel sub-grids), 27 filter transforms per call
-    float *u = ws;
-    bool ready = false;
-    if (g_filter_cache_slot.w == w && g_filter_cache_slot.u && g_filter_cache_slot.floats >= winograd_scratch_floats(C, N)) {
-        u = g_filter_cache_slot.u;
-        ready = g_filter_cache_slot.holds(FILTER_FORM_WINO2);
-    }
-    g_filter_cache_slot = FilterCacheSlot();
-    if (!ready) {
+    // (in the caller's filter cache, if it has a slice for this layer: the full-image trunk's atrous layers run here --
+    // F(2x2,3x3) on their pixel sub-grids --, 27 filter transforms per call)
+    const FilterPlace f = place_filters(ex, w, winograd_scratch_floats(C, N), FILTER_FORM_WINO2, ws, ws_floats);
+    float *u = f.u;
+    if (!f.ready) {
         const long long total = (long long)N * C;
         hipLaunchKernelGGL(wino_filter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, N, C, u);
         MPSR_CHECK_LAUNCH("wino_filter_kernel");
@@ -672,34 +662,26 @@ int conv3x3_winograd(const float *x, int B, int H, int W, int C, const float *w,
     const long long blocks = 8LL * ceil_div(p.mblocks, 8) * p.nblocks;
     if (blocks > 0x7fffffffLL) return fail(MPSR_ERR_UNSUPPORTED, "conv3x3_winograd: grid too large");
     // launches too small to fill the chip (the full-image trunk's atrous layers at ONE image: 96 workgroups) are cut
-    // along K like the sixteen-product kernel's (winograd3z.hip): partial outputs behind the transformed filters in `ws`
+    // along K like the sixteen-product kernel's (winograd3z.hip): partial outputs in what the filters leave of `ws`
     p.part = nullptr; p.nslices = 1; p.steps = p.cblocks;
     p.yfloats = (size_t)B * H * W * N;
+    const size_t lds = kLdsFloats * sizeof(float);
     if (g_wino_waves.load() == 8) {
-        float *part = ws;
-        size_t part_floats = ws_floats;
-        if (u == ws) {
-            const size_t off = align_up(winograd_scratch_floats(C, N), 64);
-            part = ws + off;
-            part_floats = ws_floats > off ? ws_floats - off : 0;
-        }
+        float *part = f.rest;
+        const size_t part_floats = f.rest_floats;
         const bool splittable = N % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)part & 15) == 0 &&
                                 (!bias || ((uintptr_t)bias & 15) == 0);
         const int slices = winograd_slices(blocks, 256, p.cblocks, 2, splittable ? part_floats : 0, p.yfloats);
         if (slices > 1) {
             p.part = part; p.nslices = slices; p.steps = p.cblocks / slices;
-            MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(wino_conv8_kernel<true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsFloats * sizeof(float))));
-            hipLaunchKernelGGL(wino_conv8_kernel<true>, dim3((unsigned)(blocks * slices)), dim3(512),
-                               kLdsFloats * sizeof(float), s, p);
-            MPSR_CHECK_LAUNCH("wino_conv8_kernel");
+            if (int rc = launch_dynamic_lds("wino_conv8_kernel", wino_conv8_kernel<true>, dim3((unsigned)(blocks * slices)),
+                                            dim3(512), lds, s, p))
+                return rc;
             return winograd_finish_slices(part, bias, y, p.yfloats, slices, N, relu, s);
         }
-        hipLaunchKernelGGL(wino_conv8_kernel<false>, dim3((unsigned)blocks), dim3(512), kLdsFloats * sizeof(float), s, p);
-    } else
-        hipLaunchKernelGGL(wino_conv_kernel, dim3((unsigned)blocks), dim3(256), kLdsFloats * sizeof(float), s, p);
-    MPSR_CHECK_LAUNCH("wino_conv_kernel");
-    return MPSR_OK;
+        return launch_dynamic_lds("wino_conv_kernel", wino_conv8_kernel<false>, dim3((unsigned)blocks), dim3(512), lds, s, p);
+    }
+    return launch_dynamic_lds("wino_conv_kernel", wino_conv_kernel, dim3((unsigned)blocks), dim3(256), lds, s, p);
 }
 
 }  // namespace mpsr

@@ -427,10 +427,6 @@ int winograd3_filter_form(int B, int H, int W, int C, int N, int dilation)
     return winograd3_form(B, H, W, C, N, dilation) == 2 ? FILTER_FORM_WINO3Z : FILTER_FORM_WINO3;
 }
 
-thread_local FilterTailJob g_filter_tail_job;
-thread_local FilterTailJob g_filter_tail_done;
-thread_local FilterCacheSlot g_filter_cache_slot;
-
 size_t winograd3_scratch_floats(int C, int N) { return (size_t)f3::NP * N * C; }
 
 // 3x3, dilation d, H = W = 3 d th (the sub-grids are 3 th x 3 th: th x th tiles of 3x3; th = 1: ResNet-101 block3 at
@@ -454,7 +450,8 @@ double winograd3_executed_flops(int B, int H, int C, int N, int dilation)
 }
 
 int conv3x3_winograd3(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu,
-                      float *y, int N, int dilation, float *ws, size_t ws_floats, hipStream_t s, const float *mask)
+                      float *y, int N, int dilation, float *ws, size_t ws_floats, hipStream_t s, const float *mask,
+                      LayerExtras *ex)
 {
     using namespace f3;
     MPSR_REQUIRE(winograd3_applies(H, W, C, dilation),
@@ -466,23 +463,12 @@ int conv3x3_winograd3(const float *x, int B, int H, int W, int C, const float *w
     MPSR_REQUIRE(xbytes < 0x7ff00000LL && winograd3_scratch_floats(C, N) * 4 < 0x7ff00000ULL,
                  "conv3x3_winograd3: tensor exceeds the 2 GiB this kernel's offsets address; split the batch");
     const int th = H / (3 * dilation);
-    const void *kern = th > 1 ? reinterpret_cast<const void *>(wino3h_conv_kernel) : reinterpret_cast<const void *>(wino3_conv_kernel);
-    MPSR_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDSF * sizeof(float))));
     const int form = winograd3_form(B, H, W, C, N, dilation);
-    const int fform = form == 2 ? FILTER_FORM_WINO3Z : FILTER_FORM_WINO3;
-    // the caller's filter cache (mpsr_net_opts), if the network entry point offered a slot for this layer
-    float *u = ws;
-    bool ready = false;
-    if (g_filter_cache_slot.w == w && g_filter_cache_slot.u && g_filter_cache_slot.floats >= winograd3_scratch_floats(C, N)) {
-        u = g_filter_cache_slot.u;
-        ready = g_filter_cache_slot.holds(fform);
-    }
-    g_filter_cache_slot = FilterCacheSlot();
-    // (or the filters were transformed into `u` by the tail job of the preceding pointwise launch)
-    ready = ready || (g_filter_tail_done.w == w && g_filter_tail_done.u == u && g_filter_tail_done.N == N &&
-                      g_filter_tail_done.C == C && g_filter_tail_done.form == (form == 2 ? 1 : 0));
-    g_filter_tail_done = FilterTailJob();
-    if (!ready) {
+    // (ready: also when the tail job of the preceding 1x1 layer's launch wrote them, LayerExtras::filters_at)
+    const FilterPlace f = place_filters(ex, w, winograd3_scratch_floats(C, N), form == 2 ? FILTER_FORM_WINO3Z : FILTER_FORM_WINO3,
+                                        ws, ws_floats);
+    float *u = f.u;
+    if (!f.ready) {
         if (form == 2) {
             if (int rc = launch_winograd3z_filter(w, N, C, u, s)) return rc;
         } else {
@@ -493,18 +479,8 @@ int conv3x3_winograd3(const float *x, int B, int H, int W, int C, const float *w
     }
     // one tile per sub-grid and enough of them to give every CU a workgroup of four one-per-SIMD waves: the forms without
     // the epilogue exchange (winograd3z.hip: sixteen products; winograd3w.hip: F(3x3,3x3), identical bits to this file's)
-    if (form == 2) {
-        // scratch for the K-split form of small launches (winograd3z.hip): what `ws` holds behind the transformed filters
-        // (all of it when they live in the caller's cache)
-        float *part = ws;
-        size_t part_floats = ws_floats;
-        if (u == ws) {
-            const size_t off = align_up(winograd3_scratch_floats(C, N), 64);
-            part = ws + off;
-            part_floats = ws_floats > off ? ws_floats - off : 0;
-        }
-        return launch_winograd3z(x, B, H, W, C, u, bias, relu, y, N, dilation, s, mask, part, part_floats);
-    }
+    // (scratch for the K-split form of small launches, winograd3z.hip: what the filters leave of `ws`)
+    if (form == 2) return launch_winograd3z(x, B, H, W, C, u, bias, relu, y, N, dilation, s, mask, f.rest, f.rest_floats);
     if (form == 1) return launch_winograd3w(x, B, H, W, C, u, bias, relu, y, N, dilation, s, mask);
     Wino3Params p;
     p.x = x; p.u = u; p.bias = bias; p.y = y; p.mask = mask;
@@ -519,10 +495,8 @@ int conv3x3_winograd3(const float *x, int B, int H, int W, int C, const float *w
     p.ubytes = (unsigned)(winograd3_scratch_floats(C, N) * 4);
     const long long blocks = 8LL * ceil_div(p.mblocks, 8) * p.nblocks;
     if (blocks > 0x7fffffffLL) return fail(MPSR_ERR_UNSUPPORTED, "conv3x3_winograd3: grid too large");
-    if (th > 1) hipLaunchKernelGGL(wino3h_conv_kernel, dim3((unsigned)blocks), dim3(512), LDSF * sizeof(float), s, p);
-    else hipLaunchKernelGGL(wino3_conv_kernel, dim3((unsigned)blocks), dim3(512), LDSF * sizeof(float), s, p);
-    MPSR_CHECK_LAUNCH("wino3_conv_kernel");
-    return MPSR_OK;
+    return launch_dynamic_lds("wino3_conv_kernel", th > 1 ? wino3h_conv_kernel : wino3_conv_kernel, dim3((unsigned)blocks),
+                              dim3(512), LDSF * sizeof(float), s, p);
 }
 
 }  // namespace mpsr

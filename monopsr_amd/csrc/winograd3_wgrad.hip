@@ -308,12 +308,8 @@ int conv3x3_wgrad_winograd3(const float *x, const float *dy, int B, int H, int W
     const WgradSlices sl = winograd3_wgrad_slices(B, dilation, C, N);
     p.steps = sl.steps;
     p.nslices = sl.nslices;
-    MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(wino3_wgrad_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDSF * sizeof(float))));
     const unsigned grid = (unsigned)(((p.nslices + 7) / 8) * 8 * blocks);
-    hipLaunchKernelGGL(wino3_wgrad_kernel, dim3(grid), dim3(256), LDSF * sizeof(float), s, p);
-    MPSR_CHECK_LAUNCH("wino3_wgrad_kernel");
-    return MPSR_OK;
+    return launch_dynamic_lds("wino3_wgrad_kernel", wino3_wgrad_kernel, dim3(grid), dim3(256), LDSF * sizeof(float), s, p);
 }
 
 }  // namespace mpsr

@@ -855,7 +855,7 @@ size_t winograd4_split_floats(int B, int H, int W, int N)
 
 int conv3x3_winograd4(const float *x, int B, int H, int W, int C, const float *w, const float *bias, int relu,
                       float *y, int N, float *ws, size_t ws_floats, hipStream_t s, int in_c8, int out_c8, float *part,
-                      size_t part_floats)
+                      size_t part_floats, LayerExtras *ex)
 {
     using namespace f4;
     MPSR_REQUIRE(winograd4_applies(H, W, C, N), "conv3x3_winograd4: needs H, W multiples of 4 and C %% 16 == 0");
@@ -866,28 +866,18 @@ int conv3x3_winograd4(const float *x, int B, int H, int W, int C, const float *w
     const long long xbytes = (long long)B * H * W * C * 4;
     MPSR_REQUIRE(xbytes + (long long)(W + 1) * C * 4 < 0x7ff00000LL && winograd4_scratch_floats(C, N) * 4 < 0x7ff00000ULL,
                  "conv3x3_winograd4: tensor exceeds the 2 GiB this kernel's offsets address; split the batch");
-    // position-split kernel: N a multiple of 128 and room for the partial outputs -- the caller's `part`, or the rest
-    // of `ws` behind the transformed filters
-    const size_t ufl = align_up(winograd4_scratch_floats(C, N), 64), need = winograd4_split_floats(B, H, W, N);
+    const FilterPlace f = place_filters(ex, w, winograd4_scratch_floats(C, N), FILTER_FORM_WINO4, ws, ws_floats);
+    float *u = f.u;
+    // position-split kernel: N a multiple of 128 and room for the partial outputs -- the caller's `part`, or what the
+    // filters leave of `ws`
+    const size_t need = winograd4_split_floats(B, H, W, N);
     const long long obytes = (long long)B * H * W * N * 4;
     bool split = g_wino4_split.load() != 0 && N % 128 == 0 && obytes < 0x7ff00000LL;
     if (split && !(part && part_floats >= need)) {
-        if (ws_floats >= ufl + need) {
-            part = ws + ufl;
-            part_floats = ws_floats - ufl;
-        } else {
-            split = false;
-        }
+        part = f.rest;
+        split = f.rest_floats >= need;
     }
-    // the caller's filter cache (mpsr_net_opts), if the network entry point offered a slot for this layer
-    float *u = ws;
-    bool ready = false;
-    if (g_filter_cache_slot.w == w && g_filter_cache_slot.u && g_filter_cache_slot.floats >= winograd4_scratch_floats(C, N)) {
-        u = g_filter_cache_slot.u;
-        ready = g_filter_cache_slot.holds(FILTER_FORM_WINO4);
-    }
-    g_filter_cache_slot = FilterCacheSlot();
-    if (!ready) {
+    if (!f.ready) {
         const long long total = (long long)N * C;
         hipLaunchKernelGGL(wino4_filter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, N, C, u);
         MPSR_CHECK_LAUNCH("wino4_filter_kernel");
@@ -914,31 +904,13 @@ int conv3x3_winograd4(const float *x, int B, int H, int W, int C, const float *w
         p.sync = reinterpret_cast<int *>(part + align_up((size_t)B * H * W * N, 64));
         p.pbytes = (unsigned)obytes;
         MPSR_CHECK_HIP(hipMemsetAsync(p.sync, 0, 2 * pairs * sizeof(int), s));
-        const size_t lds = LDSF * sizeof(float) + 16;
-        const void *kfn = in_c8 ? (out_c8 ? reinterpret_cast<const void *>(wino4s_conv_kernel<true, true>)
-                                          : reinterpret_cast<const void *>(wino4s_conv_kernel<true, false>))
-                                : (out_c8 ? reinterpret_cast<const void *>(wino4s_conv_kernel<false, true>)
-                                          : reinterpret_cast<const void *>(wino4s_conv_kernel<false, false>));
-        MPSR_CHECK_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (in_c8 && out_c8) hipLaunchKernelGGL((wino4s_conv_kernel<true, true>), grid, block, lds, s, p);
-        else if (in_c8) hipLaunchKernelGGL((wino4s_conv_kernel<true, false>), grid, block, lds, s, p);
-        else if (out_c8) hipLaunchKernelGGL((wino4s_conv_kernel<false, true>), grid, block, lds, s, p);
-        else hipLaunchKernelGGL((wino4s_conv_kernel<false, false>), grid, block, lds, s, p);
-        MPSR_CHECK_LAUNCH("wino4s_conv_kernel");
-        return MPSR_OK;
+        const auto kern = in_c8 ? (out_c8 ? wino4s_conv_kernel<true, true> : wino4s_conv_kernel<true, false>)
+                                : (out_c8 ? wino4s_conv_kernel<false, true> : wino4s_conv_kernel<false, false>);
+        return launch_dynamic_lds("wino4s_conv_kernel", kern, grid, block, LDSF * sizeof(float) + 16, s, p);
     }
-    // (set on every call: cheap, idempotent, and right for whichever device is current)
-    const void *kfn = in_c8 ? (out_c8 ? reinterpret_cast<const void *>(wino4_conv_kernel<true, true>)
-                                      : reinterpret_cast<const void *>(wino4_conv_kernel<true, false>))
-                            : (out_c8 ? reinterpret_cast<const void *>(wino4_conv_kernel<false, true>)
-                                      : reinterpret_cast<const void *>(wino4_conv_kernel<false, false>));
-    MPSR_CHECK_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDSF * sizeof(float))));
-    if (in_c8 && out_c8) hipLaunchKernelGGL((wino4_conv_kernel<true, true>), grid, block, LDSF * sizeof(float), s, p);
-    else if (in_c8) hipLaunchKernelGGL((wino4_conv_kernel<true, false>), grid, block, LDSF * sizeof(float), s, p);
-    else if (out_c8) hipLaunchKernelGGL((wino4_conv_kernel<false, true>), grid, block, LDSF * sizeof(float), s, p);
-    else hipLaunchKernelGGL((wino4_conv_kernel<false, false>), grid, block, LDSF * sizeof(float), s, p);
-    MPSR_CHECK_LAUNCH("wino4_conv_kernel");
-    return MPSR_OK;
+    const auto kern = in_c8 ? (out_c8 ? wino4_conv_kernel<true, true> : wino4_conv_kernel<true, false>)
+                            : (out_c8 ? wino4_conv_kernel<false, true> : wino4_conv_kernel<false, false>);
+    return launch_dynamic_lds("wino4_conv_kernel", kern, grid, block, LDSF * sizeof(float), s, p);
 }
 
 }  // namespace mpsr

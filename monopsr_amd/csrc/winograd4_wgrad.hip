@@ -322,11 +322,9 @@ int conv3x3_wgrad_winograd4(const float *x, const float *dy, int B, int H, int W
     p.steps = sl.steps;
     p.nslices = sl.nslices;
     MPSR_CHECK_HIP(hipMemsetAsync(ws, 0, need * sizeof(float), s));
-    MPSR_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(wino4_wgrad_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDSF * sizeof(float))));
     const unsigned grid = (unsigned)(((p.nslices + 7) / 8) * 8 * blocks);
-    hipLaunchKernelGGL(wino4_wgrad_kernel, dim3(grid), dim3(512), LDSF * sizeof(float), s, p);
-    MPSR_CHECK_LAUNCH("wino4_wgrad_kernel");
+    if (int rc = launch_dynamic_lds("wino4_wgrad_kernel", wino4_wgrad_kernel, dim3(grid), dim3(512), LDSF * sizeof(float), s, p))
+        return rc;
     const long long total = (long long)N * C;
     hipLaunchKernelGGL(wino4_wgrad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ws, N, C, dw);
     MPSR_CHECK_LAUNCH("wino4_wgrad_finish_kernel");
