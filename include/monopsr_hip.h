@@ -1354,6 +1354,59 @@ int mpsr_shape_scores(const float *a, const float *mask_a, int P, const float *b
                       const double *thresholds, int T, void *workspace, size_t workspace_bytes, int *counts,
                       double *sums, float *table, float *dist_a, float *dist_b, mpsr_stream_t stream);
 
+/* ---- Shape scores against surfaces (additive to ABI 13) ----
+ * mpsr_shape_scores' statistics, the distance of a valid point taken to the other side's SURFACE: its valid points
+ * and its kept triangles.  n boxes, each with two grids a and b (n, h, w, 3) float32, h, w >= 1, row-major (point i at
+ * row i / w, column i % w); mask_a and mask_b (n, h w) float32 or null.  By convention a is the prediction and b the
+ * ground truth.  Valid point: mpsr_shape_scores' rule (mask entry > 0, a null mask is all ones, a NaN entry is not
+ * valid, and the three coordinates are finite).
+ * Triangles of a grid: mpsr_scene_surface_render's indexing.  Cell (i, j), 0 <= i < h - 1, 0 <= j < w - 1, has the
+ * corners v00 = (i, j), v01 = (i, j + 1), v10 = (i + 1, j), v11 = (i + 1, j + 1) and gives k = 0: (v00, v01, v10) and
+ * k = 1: (v11, v10, v01), with the id t = ((i (w - 1)) + j) 2 + k within the box.  A triangle (A, B, C) is KEPT if and
+ * only if its three vertices are valid and each of its edges (A, B), (B, C), (C, A) has (double) len2 <= max_edge *
+ * max_edge, len2 the float32 squared length in mpsr_nn_distance_fwd's arithmetic, float differences, float products,
+ * (dx dx + dy dy) + dz dz (an overflow to +inf is kept by max_edge = +inf alone); the product max_edge * max_edge and
+ * the compare are fp64.  max_edge: a host double >= 0, +inf allowed.  The rule is a 3-D edge length, the same in every
+ * frame; it is not mpsr_scene_surface_render's max_edge_dz / max_span_px, which are properties of one view.
+ * Distance of a valid query q of one side against the other side:
+ *   d = min((double) d_point, min over the kept triangles (A, B, C) of their edge and face terms),
+ * d_point exactly mpsr_shape_scores' float32 nearest-valid-point distance (+inf where the other side has no valid
+ * point); the terms in fp64 on the coordinates converted exactly, every dot product x.y = (x0 y0 + x1 y1) + x2 y2,
+ * every product and sum rounded once, nothing contracted:
+ *   edge (U, V) for (A, B), (B, C), (C, A): e = V - U, w = q - U, ee = e.e, t = w.e; if ee > 0 && t > 0 && t < ee:
+ *     s = t / ee, r = w - s e (r_k = w_k - s e_k), the term is r.r; otherwise no term.
+ *   face: e0 = B - A, e1 = C - A, n = e0 x e1 = (e0_1 e1_2 - e0_2 e1_1, e0_2 e1_0 - e0_0 e1_2, e0_0 e1_1 - e0_1 e1_0),
+ *     nn = n.n, d00 = e0.e0, d01 = e0.e1, d11 = e1.e1, den = d00 d11 - d01 d01, w = q - A, d20 = w.e0, d21 = w.e1,
+ *     v = d11 d20 - d01 d21, u = d00 d21 - d01 d20; if nn > 0 && den > 0 && v > 0 && u > 0 && v + u < den:
+ *     hq = w.n, the term is (hq hq) / nn; otherwise no term.
+ * A minimum does not depend on its order and no term is NaN or -0 (float32 coordinates cannot overflow these fp64
+ * expressions), so d is defined bit for bit.  Consequences: a valid point that no kept triangle uses stays part of the
+ * surface, as a point; d <= (double) d_point always; at max_edge = 0 every d equals (double) d_point bit for bit (a
+ * kept triangle then has three equal corners, ee = nn = 0, and adds nothing -- short of distinct corners less than
+ * 2^-74 apart, whose float32 squares underflow to 0 while their fp64 ones do not); a degenerate triangle (ee = 0 on an
+ * edge, nn = 0 or den <= 0) adds no term of that kind and divides nothing by zero.
+ * thresholds: as mpsr_shape_scores takes them.  counts (n, 2 + 2T) int32: n_a, n_b, within_a[t] = the number of valid
+ * a_i with d_a[i] <= thresholds[t] * thresholds[t] (fp64), within_b[t].  sums (n, 6) fp64: sum of sqrt(d_a), sum of
+ * d_a, the same two for b, max d_a, max d_b (fp64).  table (n, 5 + 3T) float32: mpsr_shape_scores' formulas on these
+ * counts and sums, hausdorff = sqrt(max(max d_a, max d_b)).  dist_a, dist_b (n, h w) FP64, or null: every point's d,
+ * NaN at the points that are not valid.  tri_counts (n, 2) int32: the kept triangles of a and of b.
+ * Empty side (n_a == 0 or n_b == 0): the six sums and the table row NaN, the within counts 0, the dist rows NaN; n_a,
+ * n_b and tri_counts are still reported.  A side with valid points and no kept triangle is not empty: it is a cloud.
+ * Every output element is written on every call; n == 0 is a no-op that returns MPSR_OK.  workspace: 8-byte aligned,
+ * mpsr_surface_scores_workspace_bytes(n, h, w, T) bytes (0 for n <= 0 and for refused sizes), overwritten.
+ * MPSR_ERR_INVALID_ARG before any launch: n < 0, h or w < 1, a null grid or output pointer with n > 0, T outside
+ * [0, MPSR_SHAPE_MAX_THRESHOLDS], thresholds mpsr_shape_scores would refuse, max_edge NaN or < 0, h w > 2^30 or
+ * n h w >= 2^31.  MPSR_ERR_WORKSPACE: a workspace that is too small.
+ * One workgroup per (box, direction, slab of 512 queries) takes the point minimum, then works out and compacts the
+ * searched grid's kept triangle records 256 ids at a time in LDS (ranks from ballots) and runs its queries over them;
+ * a second kernel adds the slabs' partials in slab order.  No floating-point atomics: two calls on the same inputs
+ * return the same bytes.  Cost to know: every (query, kept triangle) pair is evaluated, nothing is pruned. */
+size_t mpsr_surface_scores_workspace_bytes(int n, int h, int w, int T);
+int mpsr_surface_scores(const float *a, const float *mask_a, const float *b, const float *mask_b, int n, int h, int w,
+                        const double *thresholds, int T, double max_edge, void *workspace, size_t workspace_bytes,
+                        int *counts, double *sums, float *table, double *dist_a, double *dist_b, int *tri_counts,
+                        mpsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -266,6 +266,10 @@ SIGNATURES = {
     # thresholds: a host array
     "mpsr_shape_scores": (c_i, [c_f, c_f, c_i, c_f, c_f, c_i, c_i, ctypes.POINTER(ctypes.c_double), c_i, c_f, c_sz,
                                 c_f, c_f, c_f, c_f, c_f, c_f]),
+    "mpsr_surface_scores_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    # thresholds: a host array; max_edge: a host double
+    "mpsr_surface_scores": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_double), c_i,
+                                  ctypes.c_double, c_f, c_sz, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),
 }
 
 

@@ -80,6 +80,17 @@ prefixes 'shape_' and 'placed_'), with predictions_base_dir one line each in met
 and placed_metrics_<split>.csv (save_scene_stats' format), and with breakdown the kinds 'shape' and 'placed'.  METRIC_EMD
 and METRIC_CHAMFER, the reference's two shape numbers over all 48 x 48 points, are not changed by it.
 
+shape_surface_metrics: None, or a dict of options ({} for the defaults), 'val' mode only,
+independent of shape_metrics: 'thresholds' (default DEFAULT_SHAPE_THRESHOLDS), 'max_edge' (default
+distance_metrics.DEFAULT_SHAPE_MAX_EDGE: 0.5 m, an assumption of this package) and 'placed' (default False).  The same
+clouds and masks as shape_metrics, after the optional centroid fit and before chunk_hook, but the distance of a point
+is taken to the other map's triangulated surface (core/distance_metrics.py chunk_surface_scores, one
+mpsr_surface_scores launch per chunk): at thresholds as tight as the grid's spacing the point scores measure how the
+two grids interleave.  result['shape_surface_stats'] and result['placed_surface_stats'] under NAN_RULE_ENTRY (the
+prefixes 'shape_surface_' and 'placed_surface_'; after the metrics two more columns, triangles_a and triangles_b: the
+kept triangles of the prediction and of the ground truth), metrics/<split>/shape_surface_metrics_<split>.csv and
+placed_surface_metrics_<split>.csv, and with breakdown the kinds 'shape_surface' and 'placed_surface'.
+
 Not built: TF summaries and metrics_to_show.
 """
 import argparse
@@ -114,6 +125,9 @@ _BREAKDOWN_OPTIONS = dict(depth_edges=evaluator_utils.DEFAULT_DEPTH_EDGES,
 
 # what Evaluator(shape_metrics={...}) may hold
 _SHAPE_METRICS_OPTIONS = ('thresholds', 'placed')
+
+# what Evaluator(shape_surface_metrics={...}) may hold
+_SHAPE_SURFACE_OPTIONS = ('thresholds', 'max_edge', 'placed')
 
 # what Evaluator(ap_slices={...}) may hold, with the defaults
 _AP_SLICES_OPTIONS = dict(ious=('standard', 'low'), depth_edges=evaluator_utils.DEFAULT_DEPTH_EDGES)
@@ -171,7 +185,7 @@ class Evaluator:
     def __init__(self, model, dataset, score_threshold=0.1, predictions_base_dir=None, batch_size=8,
                  project_3d_box=False, iou='standard', compute_metrics=True, compute_losses=True, metric_stats=False,
                  skip_evaluated_checkpoints=True, scene_metrics=False, breakdown=None, ap_slices=None,
-                 shape_metrics=None, centroid_fit=None, chunk_hook=None):
+                 shape_surface_metrics=None, shape_metrics=None, centroid_fit=None, chunk_hook=None):
         if iou not in kitti_eval.MIN_OVERLAP:
             raise ValueError('iou must be one of %s' % sorted(kitti_eval.MIN_OVERLAP))
         if ap_slices is not None:
@@ -229,6 +243,26 @@ class Evaluator:
         # of the pass; placed_table the same in the camera frame (None without 'placed')
         self.shape_table = None
         self.placed_table = None
+        if shape_surface_metrics is not None:
+            from monopsr_amd.core import distance_metrics
+            if getattr(dataset, 'train_val_test', None) != 'val':
+                raise ValueError("shape_surface_metrics scores the predicted maps against the ground-truth maps: it "
+                                 "needs a 'val'-mode dataset, got %r" % (getattr(dataset, 'train_val_test', None),))
+            unknown = set(shape_surface_metrics) - set(_SHAPE_SURFACE_OPTIONS)
+            if unknown:
+                raise ValueError('shape_surface_metrics: unknown options %s' % sorted(unknown))
+            shape_surface_metrics = dict(
+                thresholds=distance_metrics.check_thresholds(
+                    shape_surface_metrics.get('thresholds', distance_metrics.DEFAULT_SHAPE_THRESHOLDS)),
+                max_edge=distance_metrics.check_max_edge(
+                    shape_surface_metrics.get('max_edge', distance_metrics.DEFAULT_SHAPE_MAX_EDGE)),
+                placed=bool(shape_surface_metrics.get('placed', False)))
+        # None, or {'thresholds': (...), 'max_edge': float, 'placed': bool}: the shape scores against surfaces
+        self.shape_surface_metrics = shape_surface_metrics
+        # after a run_once with shape_surface_metrics: shape_table's form, the table with two more columns (the kept
+        # triangles of a and of b); placed_surface_table the same in the camera frame (None without 'placed')
+        self.shape_surface_table = None
+        self.placed_surface_table = None
         # after a run_once with breakdown: (table (n,9) float32 in evaluator_utils.PAIR_COLUMNS' order, overlaps (n,4)
         # float64, bins (n,3) int32 in evaluator_utils.BREAKDOWN_AXES' order, frame (n,) int32) on the device
         self.pair_table = None
@@ -272,7 +306,8 @@ class Evaluator:
         the surface scores in the same form (counts (N,5)), else None; with breakdown the pair table (table (N,9) float32,
         overlaps (N,4) float64, bins (N,3) int32), else None; with shape_metrics the shape scores (table (N, 5 + 3T)
         float32, counts (N, 2 + 2T) int32, sums (N,6) float64), else None; with its 'placed' the same in the camera
-        frame, else None), all on the device."""
+        frame, else None; with shape_surface_metrics and its 'placed' the same two against surfaces, the tables with
+        two more columns), all on the device."""
         ds, model = self.dataset, self.model
         dev = ds.device
         # the frames in split order, whatever the epoch's shuffle made of sample_list
@@ -287,6 +322,7 @@ class Evaluator:
         scene_parts, surface_parts, pair_parts = [], [], []
         self._fits = []
         shape_parts, placed_parts = [], []
+        shape_surface_parts, placed_surface_parts = [], []
         if with_losses or with_table:
             # the 'val'-mode graph of the same net: method by method, with the ground truth and the offsets
             from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
@@ -310,6 +346,14 @@ class Evaluator:
                                                                                  **self.shape_metrics)):
                         if scores is not None:
                             parts.append((scores.table, scores.counts, scores.sums))
+                if self.shape_surface_metrics is not None:
+                    from monopsr_amd.core import distance_metrics
+                    for parts, scores in zip((shape_surface_parts, placed_surface_parts),
+                                             distance_metrics.chunk_surface_scores(model, samples, outs,
+                                                                                   **self.shape_surface_metrics)):
+                        if scores is not None:
+                            parts.append((torch.cat([scores.table, scores.tri_counts.float()], 1), scores.counts,
+                                          scores.sums))
                 if self.chunk_hook is not None:
                     self.chunk_hook(rows, samples, outs)
                 if self.scene_metrics:
@@ -379,7 +423,11 @@ class Evaluator:
                 tuple(torch.cat(part).contiguous() for part in zip(*surface_parts)) if self.surface_metrics else None,
                 tuple(torch.cat(part).contiguous() for part in zip(*pair_parts)) if pair_parts else None,
                 tuple(torch.cat(part).contiguous() for part in zip(*shape_parts)) if shape_parts else None,
-                tuple(torch.cat(part).contiguous() for part in zip(*placed_parts)) if placed_parts else None)
+                tuple(torch.cat(part).contiguous() for part in zip(*placed_parts)) if placed_parts else None,
+                tuple(torch.cat(part).contiguous() for part in zip(*shape_surface_parts))
+                if shape_surface_parts else None,
+                tuple(torch.cat(part).contiguous() for part in zip(*placed_surface_parts))
+                if placed_surface_parts else None)
 
     def _rows_to_host(self, b3, b2, frame):
         """One launch, one compaction, one copy: -> (rows (m,14) float64, class index (m,), frame (m,)) of the kept
@@ -403,7 +451,8 @@ class Evaluator:
 
     def run_once(self, global_step=None):
         ds = self.dataset
-        b3, b2, frame, sums, loss_names, loss_sums, table, scene, surface, pairs, shape, placed = self._predict()
+        (b3, b2, frame, sums, loss_names, loss_sums, table, scene, surface, pairs, shape, placed, shape_surface,
+         placed_surface) = self._predict()
         rows, cls, frame_h = self._rows_to_host(b3, b2, frame)
         names = ds.sample_names
         per_frame = {}
@@ -449,11 +498,19 @@ class Evaluator:
             from monopsr_amd.core import distance_metrics
             shape_names = distance_metrics.shape_metric_names(self.shape_metrics['thresholds'], 'shape_')
             placed_names = distance_metrics.shape_metric_names(self.shape_metrics['thresholds'], 'placed_')
+        shape_surface_names, placed_surface_names = (), ()
+        if self.shape_surface_metrics is not None:
+            from monopsr_amd.core import distance_metrics
+            shape_surface_names, placed_surface_names = (
+                distance_metrics.shape_metric_names(self.shape_surface_metrics['thresholds'], prefix) +
+                (prefix + 'triangles_a', prefix + 'triangles_b') for prefix in ('shape_surface_', 'placed_surface_'))
         for kind, metric_names, parts, save in (
                 ('scene', SCENE_METRIC_NAMES, scene, evaluator_utils.save_scene_stats),
                 ('surface', SURFACE_METRIC_NAMES, surface, evaluator_utils.save_surface_stats),
                 ('shape', shape_names, shape, evaluator_utils.save_shape_stats),
-                ('placed', placed_names, placed, evaluator_utils.save_placed_stats)):
+                ('placed', placed_names, placed, evaluator_utils.save_placed_stats),
+                ('shape_surface', shape_surface_names, shape_surface, evaluator_utils.save_shape_surface_stats),
+                ('placed_surface', placed_surface_names, placed_surface, evaluator_utils.save_placed_surface_stats)):
             if parts is None:
                 continue
             setattr(self, kind + '_table', parts + (frame,))
@@ -473,7 +530,9 @@ class Evaluator:
                 kept.append(('metrics', METRIC_NAMES, table, COLUMN_METRIC))
             for kind, metric_names, parts in (('scene', SCENE_METRIC_NAMES, scene),
                                               ('surface', SURFACE_METRIC_NAMES, surface),
-                                              ('shape', shape_names, shape), ('placed', placed_names, placed)):
+                                              ('shape', shape_names, shape), ('placed', placed_names, placed),
+                                              ('shape_surface', shape_surface_names, shape_surface),
+                                              ('placed_surface', placed_surface_names, placed_surface)):
                 if parts is not None:
                     kept.append((kind, metric_names, parts[0], range(len(metric_names))))
             # one launch per table, one copy for all of them
@@ -659,6 +718,44 @@ def shape_metrics_options(ap, args):
             options['thresholds'] = distance_metrics.check_thresholds(args.shape_thresholds)
         except ValueError as e:
             ap.error('--shape-thresholds: %s' % e)
+    return options
+
+
+def add_shape_surface_arguments(ap):
+    """run_evaluation's --shape-surface-metrics, --shape-surface-thresholds, --shape-max-edge and
+    --shape-surface-placed."""
+    ap.add_argument('--shape-surface-metrics', action='store_true',
+                    help='also score every predicted instance map against the ground-truth map as surfaces: the '
+                         'distance of a point to the other map\'s triangles, not to its nearest point (DESIGN.md '
+                         'section 7.15)')
+    ap.add_argument('--shape-surface-thresholds', type=float, nargs='+', default=None, metavar='M',
+                    help='the distance thresholds of precision / recall / F-score in metres (default 0.05 0.1 0.2)')
+    ap.add_argument('--shape-max-edge', type=float, default=None, metavar='M',
+                    help='--shape-surface-metrics: the longest 3-D edge of a triangle in metres (default 0.5; inf '
+                         'keeps every triangle of valid points, 0 none)')
+    ap.add_argument('--shape-surface-placed', action='store_true',
+                    help='--shape-surface-metrics: also in the camera frame, the maps placed with the predicted (or '
+                         'fitted) centroid')
+
+
+def shape_surface_options(ap, args):
+    """The Evaluator's shape_surface_metrics of a command line's --shape-surface-metrics, --shape-surface-thresholds,
+    --shape-max-edge and --shape-surface-placed (None without --shape-surface-metrics)."""
+    if (args.shape_surface_thresholds is not None or args.shape_max_edge is not None or args.shape_surface_placed) \
+            and not args.shape_surface_metrics:
+        ap.error('--shape-surface-thresholds, --shape-max-edge and --shape-surface-placed require '
+                 '--shape-surface-metrics')
+    if not args.shape_surface_metrics:
+        return None
+    from monopsr_amd.core import distance_metrics
+    options = dict(placed=args.shape_surface_placed)
+    try:
+        if args.shape_surface_thresholds is not None:
+            options['thresholds'] = distance_metrics.check_thresholds(args.shape_surface_thresholds)
+        if args.shape_max_edge is not None:
+            options['max_edge'] = distance_metrics.check_max_edge(args.shape_max_edge)
+    except ValueError as e:
+        ap.error('--shape-surface-metrics: %s' % e)
     return options
 
 

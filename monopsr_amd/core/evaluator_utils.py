@@ -341,8 +341,9 @@ def save_metric_stats(predictions_base_dir, data_split, global_step, metric_stat
 
 
 def _save_prefixed_stats(prefix, predictions_base_dir, data_split, global_step, names, stats):
-    """save_scene_stats ('scene_'), save_surface_stats ('surface_'), save_shape_stats ('shape_') and save_placed_stats
-    ('placed_'): <prefix>metrics_<split>.csv."""
+    """save_scene_stats ('scene_'), save_surface_stats ('surface_'), save_shape_stats ('shape_'), save_placed_stats
+    ('placed_'), save_shape_surface_stats ('shape_surface_') and save_placed_surface_stats ('placed_surface_'):
+    <prefix>metrics_<split>.csv."""
     out_dir = metrics_dir(predictions_base_dir, data_split)
     os.makedirs(out_dir, exist_ok=True)
     path = os.path.join(out_dir, '%smetrics_%s.csv' % (prefix, data_split))
@@ -388,6 +389,18 @@ def save_shape_stats(predictions_base_dir, data_split, global_step, names, shape
 def save_placed_stats(predictions_base_dir, data_split, global_step, names, placed_stats):
     """save_shape_stats for the scores in the camera frame: placed_metrics_<split>.csv, the prefix 'placed_'."""
     return _save_prefixed_stats('placed_', predictions_base_dir, data_split, global_step, names, placed_stats)
+
+
+def save_shape_surface_stats(predictions_base_dir, data_split, global_step, names, stats):
+    """save_shape_stats for the scores against surfaces: shape_surface_metrics_<split>.csv,
+    the prefix 'shape_surface_'; `names` ends with the two columns of kept-triangle counts."""
+    return _save_prefixed_stats('shape_surface_', predictions_base_dir, data_split, global_step, names, stats)
+
+
+def save_placed_surface_stats(predictions_base_dir, data_split, global_step, names, stats):
+    """save_shape_surface_stats in the camera frame: placed_surface_metrics_<split>.csv, the prefix
+    'placed_surface_'."""
+    return _save_prefixed_stats('placed_surface_', predictions_base_dir, data_split, global_step, names, stats)
 
 
 def kitti_label_rows(box_3d, box_2d, classes, score_threshold, image_boxes=None, keep=None):

@@ -22,6 +22,10 @@ only (accuracy, completeness, Chamfer-L1, squared Chamfer and Hausdorff in metre
 --shape-thresholds, default 0.05 0.1 0.2 m): one line per metric and checkpoint after the report and
 metrics/<split>/shape_metrics_<split>.csv; with --shape-placed the same in the camera frame, the maps placed with the
 predicted (or, with --fit-centroids, fitted) centroid: placed_metrics_<split>.csv.
+With --shape-surface-metrics the same scores with the distance of a point taken to the other map's triangulated surface
+(triangles with a 3-D edge longer than --shape-max-edge, default 0.5 m, are left out), at --shape-surface-thresholds:
+shape_surface_metrics_<split>.csv and, with --shape-surface-placed, placed_surface_metrics_<split>.csv (DESIGN.md
+section 7.15).
 """
 import argparse
 import sys
@@ -55,6 +59,7 @@ def build_parser():
     evaluator.add_breakdown_arguments(ap)
     evaluator.add_ap_slices_arguments(ap)
     evaluator.add_shape_metrics_arguments(ap)
+    evaluator.add_shape_surface_arguments(ap)
     return ap
 
 
@@ -67,7 +72,9 @@ def format_result(result):
         lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
             name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
     for name, st in (list(result.get('scene_stats', {}).items()) + list(result.get('surface_stats', {}).items()) +
-                     list(result.get('shape_stats', {}).items()) + list(result.get('placed_stats', {}).items())):
+                     list(result.get('shape_stats', {}).items()) + list(result.get('placed_stats', {}).items()) +
+                     list(result.get('shape_surface_stats', {}).items()) +
+                     list(result.get('placed_surface_stats', {}).items())):
         lines.append('%-24s n %6d  mean %12.5f  std %12.5f  mean|x| %12.5f  std|x| %12.5f  dropped %d\n' % (
             name, st['count'], st['mean'], st['std'], st['mean_abs'], st['std_abs'], st['dropped']))
     for name, st in result.get('breakdown', {}).get('all', {}).get('object', {}).items():
@@ -88,6 +95,7 @@ def main(argv=None):
     breakdown = evaluator.breakdown_options(ap, args)
     ap_slices = evaluator.ap_slices_options(ap, args)
     shape_metrics = evaluator.shape_metrics_options(ap, args)
+    shape_surface_metrics = evaluator.shape_surface_options(ap, args)
     from monopsr_amd.core import config_utils
     from monopsr_amd.core.models.monopsr.monopsr_model import MonoPSRModel
     from monopsr_amd.datasets.kitti.kitti_dataset import KittiDataset
@@ -102,7 +110,7 @@ def main(argv=None):
                              iou='low' if args.low_iou else 'standard', metric_stats=True,
                              scene_metrics='surface' if args.surface_metrics else args.scene_metrics,
                              centroid_fit=centroid_fit, breakdown=breakdown, ap_slices=ap_slices,
-                             shape_metrics=shape_metrics)
+                             shape_metrics=shape_metrics, shape_surface_metrics=shape_surface_metrics)
     if args.repeat:
         max_iterations = getattr(train_config, 'max_iterations', None)
         if max_iterations is None and args.max_idle is None:

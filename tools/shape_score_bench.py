@@ -6,6 +6,10 @@ The composition: tf_nndistance.nn_distance on the same clouds, the points that a
 the roots and of the squares, the maxima, the counts within each threshold, and the table's arithmetic.  It is checked
 against the fused call's table before it is timed.  Each window runs for at least --seconds after a warm-up; the time
 of a call is the events' span over the number of calls queued between them.  Numbers: DESIGN.md section 7.14.
+
+--surface times mpsr_surface_scores next to mpsr_shape_scores on the same clouds instead: 32
+and 256 boxes of 48 x 48, a bumpy sheet with a spacing of 8 cm (a car's) and the same sheet with 3 cm of noise, with a
+~25 % mask and with null masks, at max_edge 0.5 m and +inf.  It prints the kept triangles per side next to the times.
 """
 import argparse
 import os
@@ -60,11 +64,39 @@ def composed(a, b, mask_a, mask_b, thresholds):
     return torch.cat([head, torch.stack([p, r, f], 2).reshape(len(acc), -1)], 1).float()
 
 
+def surface(seconds, dev):
+    """mpsr_surface_scores against mpsr_shape_scores on sheets of 48 x 48 points."""
+    thr = distance_metrics.DEFAULT_SHAPE_THRESHOLDS
+    i, j = torch.meshgrid(torch.arange(48.0, device=dev), torch.arange(48.0, device=dev), indexing='ij')
+    sheet = torch.stack([0.08 * i, 0.08 * j, 0.3 * torch.sin(0.4 * i) * torch.cos(0.3 * j)], -1)
+    for n in (32, 256):
+        for masked in (True, False):
+            g = torch.Generator(device=dev).manual_seed(n + masked)
+            pa = (sheet[None] + torch.randn((n, 48, 48, 3), device=dev, generator=g) * 0.01).contiguous()
+            pb = pa + torch.randn((n, 48, 48, 3), device=dev, generator=g) * 0.03
+            ma = (torch.rand((n, POINTS), device=dev, generator=g) < 0.25).float() if masked else None
+            mb = (torch.rand((n, POINTS), device=dev, generator=g) < 0.25).float() if masked else None
+            point_us = window(lambda: distance_metrics.shape_scores(pa, pb, ma, mb, thr), seconds)
+            for max_edge in (0.5, float('inf')):
+                s = distance_metrics.surface_scores(pa, pb, ma, mb, thr, max_edge)
+                tris = s.tri_counts.double().mean(0).cpu().tolist()
+                # (with null masks a call takes milliseconds: two to a batch keep the window near its length)
+                us = window(lambda: distance_metrics.surface_scores(pa, pb, ma, mb, thr, max_edge), seconds, batch=2)
+                print('%3d boxes of 48 x 48, %s, max_edge %3g: mpsr_surface_scores %9.1f us (%6.0f and %6.0f triangles '
+                      'a box), mpsr_shape_scores %8.1f us' % (n, 'a ~25 % mask' if masked else 'null masks  ', max_edge,
+                                                             us, tris[0], tris[1], point_us))
+    return 0
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument('--seconds', type=float, default=1.0, help='length of a timing window (default 1 s)')
+    p.add_argument('--surface', action='store_true',
+                   help='time mpsr_surface_scores against mpsr_shape_scores instead (DESIGN.md section 7.15)')
     a = p.parse_args(argv)
     dev = torch.device('cuda', torch.cuda.current_device())
+    if a.surface:
+        return surface(a.seconds, dev)
     thr = distance_metrics.DEFAULT_SHAPE_THRESHOLDS
     for n, masked in ((32, True), (32, False), (256, True)):
         g = torch.Generator(device=dev).manual_seed(n + masked)
