@@ -9,6 +9,7 @@ import torch
 
 import mscnn_split
 import scene_score_restatement
+import shape_score_calls as calls
 import shape_score_cases as cases
 import shape_score_restatement as restatement
 from monopsr_amd import _lib
@@ -22,16 +23,6 @@ THRESHOLD = 0.1
 OUTPUTS = ('counts', 'sums', 'table', 'dist_a', 'dist_b')
 
 
-def _device(array, offset):
-    """The array on the device, `offset` elements into a larger allocation with one more element behind it."""
-    if array is None:
-        return None, None
-    t = torch.from_numpy(np.array(array)).reshape(-1)
-    whole = torch.zeros(t.numel() + offset + 1, dtype=t.dtype).cuda()
-    whole[offset:offset + t.numel()] = t.cuda()
-    return whole, whole[offset:offset + t.numel()]
-
-
 def _call(c, poison=False, offset=0, thresholds=None, workspace_short=0):
     """One mpsr_shape_scores call through the C entry point.  Every output sits `offset` elements into an allocation
     with a guard element behind it; poison fills outputs and workspace with NaN / 0xFF first (else with zeros).
@@ -39,35 +30,18 @@ def _call(c, poison=False, offset=0, thresholds=None, workspace_short=0):
     n, P, Q = c['a'].shape[0], c['a'].shape[1], c['b'].shape[1]
     thr = tuple(c['thresholds'] if thresholds is None else thresholds)
     T = len(thr)
-    keep = [_device(c[k], offset) for k in ('a', 'mask_a', 'b', 'mask_b')]
-    (_, a), (_, ma), (_, b), (_, mb) = keep
     shapes = dict(counts=((n, 2 + 2 * T), torch.int32), sums=((n, 6), torch.float64),
                   table=((n, 5 + 3 * T), torch.float32), dist_a=((n, P), torch.float32), dist_b=((n, Q), torch.float32))
-    whole, view = {}, {}
-    for name, (shape, dtype) in shapes.items():
-        size = int(np.prod(shape))
-        fill = (-1 if dtype == torch.int32 else float('nan')) if poison else 0
-        whole[name] = torch.full((size + offset + 1,), fill, dtype=dtype, device='cuda')
-        view[name] = whole[name][offset:offset + size]
     lib = _lib.lib()
     need = int(lib.mpsr_shape_scores_workspace_bytes(n, P, Q, T))
     assert need % 8 == 0 and (need > 0) == (n > 0 and T <= dm.MAX_THRESHOLDS)
-    ws_whole = torch.full((need // 8 + offset + 1,), -1 if poison else 0, dtype=torch.int64, device='cuda')
-    ws = ws_whole[offset:offset + need // 8]
-    before = {k: v.clone() for k, v in whole.items()}
-    p = lambda t: None if t is None else t.data_ptr()
-    status = lib.mpsr_shape_scores(p(a), p(ma), P, p(b), p(mb), Q, n, (ctypes.c_double * max(T, 1))(*thr), T, p(ws),
-                                   need - workspace_short, p(view['counts']), p(view['sums']), p(view['table']),
-                                   p(view['dist_a']), p(view['dist_b']), _lib.stream())
-    torch.cuda.synchronize()
-    out = {k: view[k].cpu().numpy().reshape(shapes[k][0]) for k in shapes}
-    # the guard elements around every output and the workspace keep their fill
-    for k in shapes:
-        for at in list(range(offset)) + [-1]:
-            assert restatement.same_bits(whole[k][at].cpu().numpy(), before[k][at].cpu().numpy()), (k, at)
-    for at in list(range(offset)) + [-1]:
-        assert int(ws_whole[at]) == (-1 if poison else 0)
-    return status, out, before
+
+    def launch(inputs, out, ws):
+        a, ma, b, mb = inputs
+        return lib.mpsr_shape_scores(a, ma, P, b, mb, Q, n, (ctypes.c_double * max(T, 1))(*thr), T, ws,
+                                     need - workspace_short, out['counts'], out['sums'], out['table'], out['dist_a'],
+                                     out['dist_b'], _lib.stream())
+    return calls.guarded_call([c[k] for k in ('a', 'mask_a', 'b', 'mask_b')], shapes, need, launch, poison, offset)
 
 
 @pytest.fixture(scope='module')
@@ -83,16 +57,6 @@ def _result(device_results, name):
     return device_results[name]
 
 
-def _neighbours(got, want):
-    """got is want or one of its float32 neighbours, NaN for NaN"""
-    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
-    nan = np.isnan(want)
-    if not np.array_equal(nan, np.isnan(got)):
-        return False
-    lo, hi = np.nextafter(want, np.float32(-np.inf)), np.nextafter(want, np.float32(np.inf))
-    return bool(((got[~nan] >= lo[~nan]) & (got[~nan] <= hi[~nan])).all())
-
-
 @pytest.mark.parametrize('name', cases.NAMES)
 def test_catalogue_equals_the_restatement(device_results, name):
     """counts, dist_a, dist_b and the two maxima bit for bit; the four sums within (m + 2) 2^-52 sum |term| (one ulp per
@@ -103,17 +67,9 @@ def test_catalogue_equals_the_restatement(device_results, name):
     for key in ('counts', 'dist_a', 'dist_b'):
         assert restatement.same_bits(got[key], want[key]), (name, key)
     assert restatement.same_bits(got['sums'][:, 4:6], want['sums'][:, 4:6]), name
-    gs, ws = got['sums'][:, 0:4], want['sums'][:, 0:4]
-    special = ~np.isfinite(ws)  # an empty side's NaN, an overflow's +inf
-    assert restatement.same_bits(np.where(special, gs, 0.0), np.where(special, ws, 0.0)), name
-    bound = restatement.sum_bound(want['terms'], np.where(special, 0.0, want['abs_sums']))
-    err = np.abs(np.where(special, 0.0, gs) - np.where(special, 0.0, ws))
-    print('%s: largest sum error %.3g of its bound' % (name, float((err / np.maximum(bound, 1e-300)).max())))
-    assert bool((err <= bound).all()), (name, float(err.max()))
-    if name in cases.EXACT_SUM_NAMES:
-        assert restatement.same_bits(gs, ws), name
+    calls.assert_sums_within_the_bound(name, got['sums'], want, (0, 1, 2, 3) if name in cases.EXACT_SUM_NAMES else ())
     own = restatement.table(got['counts'], got['sums'], T)
-    assert _neighbours(got['table'], own), name
+    assert calls.neighbours(got['table'], own), name
     # NaN exactly where defined: the rows of an empty side, the points that are not valid
     empty = (want['counts'][:, 0] == 0) | (want['counts'][:, 1] == 0)
     assert np.array_equal(np.isnan(got['table']).all(1), empty) and np.array_equal(np.isnan(got['table']).any(1), empty)
@@ -133,18 +89,14 @@ def test_null_masks_give_nn_distance(device_results, name):
     assert restatement.same_bits(got['dist_b'], d2.cpu().numpy()), name
 
 
-def _bytes(out):
-    return b''.join(out[k].tobytes() for k in OUTPUTS)
-
-
 @pytest.mark.parametrize('name', ('hostile', 'frame', 'empty_sides'))
 def test_two_runs_poison_and_odd_offsets_return_the_same_bytes(device_results, name):
     """The same bytes from a second run, from zeroed instead of NaN / 0xFF-filled outputs and workspace, and from
     pointers one and three elements into larger allocations; the elements around every buffer keep their values."""
-    first = _bytes(_result(device_results, name))
+    first = calls.output_bytes(_result(device_results, name), OUTPUTS)
     for kw in (dict(poison=True), dict(poison=False), dict(poison=True, offset=1), dict(poison=False, offset=3)):
         status, out, _ = _call(cases.case(name), **kw)
-        assert status == 0 and _bytes(out) == first, (name, kw)
+        assert status == 0 and calls.output_bytes(out, OUTPUTS) == first, (name, kw)
 
 
 def test_null_dist_pointers_and_empty_sizes():
@@ -212,7 +164,7 @@ def test_more_work_items_than_the_grid_has_workgroups():
     own[:, 0], own[:, 1], own[:, 2], own[:, 3], own[:, 4] = r0, r2, (r0 + r2) / 2, d64 + d64, np.sqrt(d64)
     own[:, 5], own[:, 6], own[:, 7] = hit, hit, hit  # p = r = 0 or 1: the F-score is 0 or 2 / 2
     own[~both] = np.nan
-    assert _neighbours(got['table'], own.astype(np.float32))
+    assert calls.neighbours(got['table'], own.astype(np.float32))
 
 
 def test_argument_errors_leave_the_outputs_untouched():
@@ -276,7 +228,7 @@ def _assert_table_and_stats(kept, want, stats, names):
     live = np.isfinite(want['sums'][:, 0:4])
     err = np.abs(np.where(live, sums[:, 0:4].cpu().numpy(), 0.0) - np.where(live, want['sums'][:, 0:4], 0.0))
     assert bool((err <= restatement.sum_bound(want['terms'], np.where(live, want['abs_sums'], 0.0))).all())
-    assert _neighbours(table.cpu().numpy(), want['table'])
+    assert calls.neighbours(table.cpu().numpy(), want['table'])
     want_stats = scene_score_restatement.stats(want['table'])
     assert list(stats) == list(names) and len(names) == want['table'].shape[1]
     # the statistics of the evaluator's OWN table: only fp64 summation order separates the two (numpy adds pairwise,
@@ -298,23 +250,6 @@ def _assert_table_and_stats(kept, want, stats, names):
         for j, key in enumerate(('mean', 'std', 'mean_abs', 'std_abs')):
             w = want_stats[k, 1 + j]
             assert np.isnan(st[key]) if np.isnan(w) else abs(st[key] - w) <= tol, (name, key, st[key], w)
-
-
-def _same_elsewhere(plain, scored, extra, val):
-    assert set(scored) - set(plain) == extra
-    for key in plain:
-        if key in ('kitti_predictions_dir', 'metrics_csv', 'breakdown_csv'):
-            continue
-        if key == 'kitti':
-            assert scored['report'] == plain['report']
-            continue
-        assert repr(scored[key]) == repr(plain[key]), key
-    for name in val.split_sample_names:
-        with open(os.path.join(plain['kitti_predictions_dir'], name + '.txt'), 'rb') as a, \
-                open(os.path.join(scored['kitti_predictions_dir'], name + '.txt'), 'rb') as b:
-            assert a.read() == b.read(), name
-    for a, b in zip(plain['metrics_csv'], scored['metrics_csv']):
-        assert open(a, 'rb').read() == open(b, 'rb').read()
 
 
 @pytest.fixture(scope='module')
@@ -354,7 +289,7 @@ def test_evaluator_shape_stats_equal_the_restatement(setup, unfitted):
         assert float(fields[2]) == float('%.5f' % stats[kind + '_accuracy']['mean'])
         assert not os.path.exists(path.replace(str(base / 'scored'), str(base / 'plain')))
     # everything else is what it is without shape_metrics
-    _same_elsewhere(plain, scored, {'shape_stats', 'placed_stats', 'shape_metrics_csv', 'placed_metrics_csv'}, val)
+    calls.same_elsewhere(plain, scored, {'shape_stats', 'placed_stats', 'shape_metrics_csv', 'placed_metrics_csv'}, val)
     assert 'shape_stats' not in plain
     with pytest.raises(ValueError):
         evaluator.Evaluator(model, test, THRESHOLD, shape_metrics={})

@@ -188,6 +188,11 @@ def test_symbols_are_declared_and_bound():
     assert re.search(r'^[^\n]*\bsurface_score\.o[^\n]*:[^\n]*\n\t\$\(HIPCC\) \$\(FLAGS\) \$\(NOFMA\)', mk, re.M)
     src = open(os.path.join(ROOT, 'monopsr_amd', 'csrc', 'surface_score.hip')).read()
     assert '#pragma clang fp contract(off)' in src and not re.search(r'\batomic\w*\s*\(', src)
+    # what it shares with mpsr_shape_scores lives in the core header, under the same rule
+    assert '#include "shape_score_core.h"' in src
+    assert re.search(r'^[^\n]*\bsurface_score\.o[^\n]*:[^\n]*\bshape_score_core\.h\b', mk, re.M)
+    core = open(os.path.join(ROOT, 'monopsr_amd', 'csrc', 'shape_score_core.h')).read()
+    assert '#pragma clang fp contract(off)' in core and not re.search(r'\batomic\w*\s*\(', core)
     assert '#include "common.h"' in src and not re.search(r'^\s*extern\s+(?!"C")', src, re.M)
 
 

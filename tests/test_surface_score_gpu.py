@@ -14,6 +14,7 @@ import torch
 
 import mscnn_split
 import scene_score_restatement
+import shape_score_calls as calls
 import surface_score_cases as cases
 import surface_score_restatement as restatement
 from monopsr_amd import _lib
@@ -27,16 +28,6 @@ THRESHOLD = 0.1
 OUTPUTS = ('counts', 'sums', 'table', 'dist_a', 'dist_b', 'tri_counts')
 
 
-def _device(array, offset):
-    """The array on the device, `offset` elements into a larger allocation with one more element behind it."""
-    if array is None:
-        return None, None
-    t = torch.from_numpy(np.array(array)).reshape(-1)
-    whole = torch.zeros(t.numel() + offset + 1, dtype=t.dtype).cuda()
-    whole[offset:offset + t.numel()] = t.cuda()
-    return whole, whole[offset:offset + t.numel()]
-
-
 def _call(c, poison=False, offset=0, thresholds=None, workspace_short=0, max_edge=None):
     """One mpsr_surface_scores call through the C entry point.  Every output sits `offset` elements into an allocation
     with a guard element behind it; poison fills outputs and workspace with NaN / 0xFF first (else with zeros).
@@ -45,37 +36,20 @@ def _call(c, poison=False, offset=0, thresholds=None, workspace_short=0, max_edg
     P = h * w
     thr = tuple(c['thresholds'] if thresholds is None else thresholds)
     T = len(thr)
-    keep = [_device(c[k], offset) for k in ('a', 'mask_a', 'b', 'mask_b')]
-    (_, a), (_, ma), (_, b), (_, mb) = keep
     shapes = dict(counts=((n, 2 + 2 * T), torch.int32), sums=((n, 6), torch.float64),
                   table=((n, 5 + 3 * T), torch.float32), dist_a=((n, P), torch.float64), dist_b=((n, P), torch.float64),
                   tri_counts=((n, 2), torch.int32))
-    whole, view = {}, {}
-    for name, (shape, dtype) in shapes.items():
-        size = int(np.prod(shape))
-        fill = (-1 if dtype == torch.int32 else float('nan')) if poison else 0
-        whole[name] = torch.full((size + offset + 1,), fill, dtype=dtype, device='cuda')
-        view[name] = whole[name][offset:offset + size]
     lib = _lib.lib()
     need = int(lib.mpsr_surface_scores_workspace_bytes(n, h, w, T))
     assert need % 8 == 0 and (need > 0) == (n > 0 and T <= dm.MAX_THRESHOLDS)
-    ws_whole = torch.full((need // 8 + offset + 1,), -1 if poison else 0, dtype=torch.int64, device='cuda')
-    ws = ws_whole[offset:offset + need // 8]
-    before = {k: v.clone() for k, v in whole.items()}
-    p = lambda t: None if t is None else t.data_ptr()
-    status = lib.mpsr_surface_scores(
-        p(a), p(ma), p(b), p(mb), n, h, w, (ctypes.c_double * max(T, 1))(*thr), T,
-        float(c['max_edge'] if max_edge is None else max_edge), p(ws), need - workspace_short, p(view['counts']),
-        p(view['sums']), p(view['table']), p(view['dist_a']), p(view['dist_b']), p(view['tri_counts']), _lib.stream())
-    torch.cuda.synchronize()
-    out = {k: view[k].cpu().numpy().reshape(shapes[k][0]) for k in shapes}
-    # the guard elements around every output and the workspace keep their fill
-    for k in shapes:
-        for at in list(range(offset)) + [-1]:
-            assert restatement.same_bits(whole[k][at].cpu().numpy(), before[k][at].cpu().numpy()), (k, at)
-    for at in list(range(offset)) + [-1]:
-        assert int(ws_whole[at]) == (-1 if poison else 0)
-    return status, out, before
+
+    def launch(inputs, out, ws):
+        a, ma, b, mb = inputs
+        return lib.mpsr_surface_scores(
+            a, ma, b, mb, n, h, w, (ctypes.c_double * max(T, 1))(*thr), T,
+            float(c['max_edge'] if max_edge is None else max_edge), ws, need - workspace_short, out['counts'],
+            out['sums'], out['table'], out['dist_a'], out['dist_b'], out['tri_counts'], _lib.stream())
+    return calls.guarded_call([c[k] for k in ('a', 'mask_a', 'b', 'mask_b')], shapes, need, launch, poison, offset)
 
 
 @pytest.fixture(scope='module')
@@ -91,30 +65,6 @@ def _result(device_results, name):
     return device_results[name]
 
 
-def _neighbours(got, want):
-    """got is want or one of its float32 neighbours, NaN for NaN"""
-    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
-    nan = np.isnan(want)
-    if not np.array_equal(nan, np.isnan(got)):
-        return False
-    lo, hi = np.nextafter(want, np.float32(-np.inf)), np.nextafter(want, np.float32(np.inf))
-    return bool(((got[~nan] >= lo[~nan]) & (got[~nan] <= hi[~nan])).all())
-
-
-def _assert_sums_within_the_bound(name, got_sums, want, exact=()):
-    """The four sums within section 7.14's (m + 2) 2^-52 sum |term|; NaN and +inf where the restatement has them; the
-    columns of `exact` bit for bit."""
-    gs, ws = got_sums[:, 0:4], want['sums'][:, 0:4]
-    special = ~np.isfinite(ws)
-    assert restatement.same_bits(np.where(special, gs, 0.0), np.where(special, ws, 0.0)), name
-    bound = restatement.sum_bound(want['terms'], np.where(special, 0.0, want['abs_sums']))
-    err = np.abs(np.where(special, 0.0, gs) - np.where(special, 0.0, ws))
-    print('%s: largest sum error %.3g of its bound' % (name, float((err / np.maximum(bound, 1e-300)).max())))
-    assert bool((err <= bound).all()), (name, float(err.max()))
-    for k in exact:
-        assert restatement.same_bits(gs[:, k], ws[:, k]), (name, k)
-
-
 @pytest.mark.parametrize('name', cases.NAMES)
 def test_catalogue_equals_the_restatement(device_results, name):
     """counts, tri_counts, dist_a, dist_b and the two maxima bit for bit (every operation is an IEEE float32 or fp64
@@ -126,9 +76,9 @@ def test_catalogue_equals_the_restatement(device_results, name):
     for key in ('counts', 'tri_counts', 'dist_a', 'dist_b'):
         assert restatement.same_bits(got[key], want[key]), (name, key)
     assert restatement.same_bits(got['sums'][:, 4:6], want['sums'][:, 4:6]), name
-    _assert_sums_within_the_bound(name, got['sums'], want, cases.EXACT_SUMS.get(name, ()))
+    calls.assert_sums_within_the_bound(name, got['sums'], want, cases.EXACT_SUMS.get(name, ()))
     own = restatement.table(got['counts'], got['sums'], T)
-    assert _neighbours(got['table'], own), name
+    assert calls.neighbours(got['table'], own), name
     empty = (want['counts'][:, 0] == 0) | (want['counts'][:, 1] == 0)
     assert np.array_equal(np.isnan(got['table']).all(1), empty) and np.array_equal(np.isnan(got['table']).any(1), empty)
     assert np.array_equal(np.isnan(got['sums']).all(1), empty) and np.array_equal(np.isnan(got['sums']).any(1), empty)
@@ -183,18 +133,14 @@ def test_max_edge_zero_is_mpsr_shape_scores(name):
     assert bool((err <= restatement.sum_bound(m, np.where(special, 0.0, ws))).all()), name
 
 
-def _bytes(out):
-    return b''.join(out[k].tobytes() for k in OUTPUTS)
-
-
 @pytest.mark.parametrize('name', ('hostile', 'random_masks', 'empty_sides', 'holes'))
 def test_two_runs_poison_and_odd_offsets_return_the_same_bytes(device_results, name):
     """The same bytes from a second run, from zeroed instead of NaN / 0xFF-filled outputs and workspace, and from
     pointers one and three elements into larger allocations; the elements around every buffer keep their values."""
-    first = _bytes(_result(device_results, name))
+    first = calls.output_bytes(_result(device_results, name), OUTPUTS)
     for kw in (dict(poison=True), dict(poison=False), dict(poison=True, offset=1), dict(poison=False, offset=3)):
         status, out, _ = _call(cases.case(name), **kw)
-        assert status == 0 and _bytes(out) == first, (name, kw)
+        assert status == 0 and calls.output_bytes(out, OUTPUTS) == first, (name, kw)
 
 
 def test_wrapper_null_dist_pointers_and_refusals():
@@ -254,7 +200,7 @@ def test_more_work_items_than_the_grid_has_workgroups():
         assert np.array_equal(np.isnan(got['sums'][:, k]), ~both)
         assert bool((err <= restatement.sum_bound(1, np.where(both, root, 0.0))).all())
     own = restatement.table(got['counts'], got['sums'], 1)
-    assert _neighbours(got['table'], own)
+    assert calls.neighbours(got['table'], own)
 
 
 def test_argument_errors_leave_the_outputs_untouched():
@@ -334,7 +280,7 @@ def _assert_table_and_stats(kept, want, stats, names):
     err = np.abs(np.where(live, sums[:, 0:4].cpu().numpy(), 0.0) - np.where(live, want['sums'][:, 0:4], 0.0))
     assert bool((err <= restatement.sum_bound(want['terms'], np.where(live, want['abs_sums'], 0.0))).all())
     host = table.cpu().numpy()
-    assert _neighbours(host[:, :-2], want['table'])
+    assert calls.neighbours(host[:, :-2], want['table'])
     assert np.array_equal(host[:, -2:], want['tri_counts'].astype(np.float32))
     want_table = np.concatenate([want['table'], want['tri_counts'].astype(np.float32)], 1)
     assert list(stats) == list(names) and len(names) == want_table.shape[1]
@@ -349,23 +295,6 @@ def _assert_table_and_stats(kept, want, stats, names):
         for j, key in enumerate(('mean', 'std', 'mean_abs', 'std_abs')):
             for w, bound in ((own_stats[k, 1 + j], tight), (want_stats[k, 1 + j], tol)):
                 assert np.isnan(st[key]) if np.isnan(w) else abs(st[key] - w) <= bound, (name, key, st[key], w)
-
-
-def _same_elsewhere(plain, scored, extra, val):
-    assert set(scored) - set(plain) == extra
-    for key in plain:
-        if key in ('kitti_predictions_dir', 'metrics_csv', 'breakdown_csv'):
-            continue
-        if key == 'kitti':
-            assert scored['report'] == plain['report']
-            continue
-        assert repr(scored[key]) == repr(plain[key]), key
-    for name in val.split_sample_names:
-        with open(os.path.join(plain['kitti_predictions_dir'], name + '.txt'), 'rb') as a, \
-                open(os.path.join(scored['kitti_predictions_dir'], name + '.txt'), 'rb') as b:
-            assert a.read() == b.read(), name
-    for a, b in zip(plain['metrics_csv'], scored['metrics_csv']):
-        assert open(a, 'rb').read() == open(b, 'rb').read()
 
 
 def _names(thr, prefix):
@@ -413,7 +342,7 @@ def test_evaluator_surface_stats_equal_the_restatement(setup, unfitted, restated
         assert [c.strip() for c in lines[0].split(',')][-3] == 'triangles_b_count'
         assert not os.path.exists(path.replace(str(base / 'scored'), str(base / 'plain')))
     # everything else is what it is without shape_surface_metrics
-    _same_elsewhere(plain, scored, {'shape_surface_stats', 'placed_surface_stats', 'shape_surface_metrics_csv',
+    calls.same_elsewhere(plain, scored, {'shape_surface_stats', 'placed_surface_stats', 'shape_surface_metrics_csv',
                                     'placed_surface_metrics_csv'}, val)
     assert 'shape_surface_stats' not in plain and 'shape_stats' not in scored
     with pytest.raises(ValueError):
